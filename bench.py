@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Caption-training throughput of the native Swin-V2 -> T5 path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload caption|cfg3|spanmask|cfg5]
+    python bench.py --gpus N --steps K --warmup W [--workload caption|cfg3|spanmask|cfg5] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...; without a launcher in the
      environment `python bench.py --gpus N` starts those N ranks itself as a child process, or fails -- it never measures one rank)
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds what takes work beyond that: the per-kernel
+roofline (HIP-event probes in the timed steps, three more probe steps after them), the per-rank spread and replica check
+at N > 1, and the CPU oracle baseline (unless --no-cpu-baseline).  --dump-outputs DIR writes what the last timed step handed
+its caller (loss, updated weights, Adam moments) as .npy files, before anything else runs; that step then starts from the seeded initial
+weights and optimizer state (restored outside the clock), so that runs with the same arguments compute it from the same inputs.
 
 One step = what ref/train.py:58-67 does per iteration: loss = model(images, src, tgt); loss.backward();
 optimizer.step(); optimizer.zero_grad()  -- forward + backward of MyModel (libklab_mm.so engine), the
@@ -163,6 +169,46 @@ def _traffic(key):
         return None
 
 
+DUMP_SAMPLE = 1 << 22  # values kept per array by --dump-outputs (16 MB each; T5-large alone has ~740 M weights)
+
+
+def dump_outputs(d, loss, params, optimizer):
+    """--dump-outputs: what the last timed step leaves its caller -- the loss, and the same fixed, seeded sample (parameters()
+    order) of the trainable weights its optimizer step wrote and of that step's Adam moments exp_avg / exp_avg_sq (these carry
+    the magnitudes of the step's gradients: from the restored state below, exp_avg = (1 - beta1) g, exp_avg_sq = (1 - beta2) g^2)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    params = list(params)
+    st = optimizer.state_dict()["state"]  # per parameter, in param_groups order (= parameters() order)
+    n = sum(p.numel() for p in params)
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values.to(params[0].device)
+
+    def save(name, ts):
+        flat = torch.cat([t.detach().reshape(-1).float() for t in ts])
+        np.save(os.path.join(d, name), (flat if idx is None else flat[idx]).cpu().numpy())
+
+    np.save(os.path.join(d, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    save("transformer_param_sample.npy", params)
+    save("adam_exp_avg_sample.npy", [st[i]["exp_avg"] for i in range(len(params))])
+    save("adam_exp_avg_sq_sample.npy", [st[i]["exp_avg_sq"] for i in range(len(params))])
+
+
+def restore_initial_state(params, init, optimizer):
+    """weights back to `init` (the copy bumps the parameters' versions: the next forward re-casts its bf16 copies), optimizer
+    state back to that of a fresh optimizer"""
+    with torch.no_grad():
+        for p, w in zip(params, init):
+            p.copy_(w)
+    if getattr(optimizer, "_m", None) is not None:  # klab FusedAdam: moments in two flat buffers, step count on the host
+        optimizer._m.zero_()
+        optimizer._v.zero_()
+        optimizer._steps = 0
+    else:
+        optimizer.state.clear()
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -208,7 +254,10 @@ def main():
                     help="caption = BASELINE configs[1] (the headline metric); cfg3 / spanmask / cfg5 = per-GPU slices of configs[2..4]")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the workload's, configs[1]: 64)")
     ap.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16", help="fp8: per-tensor-scaled fp8 MFMA GEMMs (configs[4])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the per-kernel roofline, the per-rank spread / replica check (N > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss and updated weights to DIR/*.npy")
     ap.add_argument("--optimizer", choices=["klab", "torch"], default="klab",
                     help="klab: klab_multimodalmodel_amd.optim.FusedAdam (same update rule as torch.optim.Adam, one kernel); torch: torch.optim.Adam(fused=True)")
     ap.add_argument("--step-in-backward", action="store_true",
@@ -220,6 +269,8 @@ def main():
     wl = WORKLOADS[a.workload]
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:  # before ANY GPU call of this process
         sys.exit(self_launch(a.gpus, sys.argv[1:]))
     # stdout carries exactly ONE JSON line: everything else that writes to file descriptor 1 while the bench runs (RCCL's
@@ -271,6 +322,11 @@ def main():
     else:                      # ref/train.py:28 verbatim (torch's own fused multi-tensor kernel)
         optimizer = torch.optim.Adam(core.transformer.parameters(), lr=lr, fused=True)
     core.transformer.train()                                               # ref/train.py:52
+    # --dump-outputs: the last timed step starts again from the seeded initial weights and optimizer state, so that every run feeds
+    # it identical inputs.  (Float atomics in the engine's reductions round differently from run to run, and training carries that
+    # into every later step: after 30 steps two runs' losses differed by 12 % and their Adam moments by 118 % rel-L2, against a
+    # bit-identical loss and moments within 3e-3 for the restored step -- profiles/bench_dump_reproducibility.txt.)
+    init = [p.detach().clone() for p in core.transformer.parameters()] if a.dump_outputs else None
 
     B, Ls, Lt = (a.batch or wl["B"]), wl["Ls"], wl["Lt"]
     synth = synth_spanmask_batch if wl["span"] else synth_batch
@@ -287,14 +343,21 @@ def main():
     for _ in range(a.warmup):
         step()
     eng = core._engine
-    eng.probe_enable(True)
+    if a.full:
+        eng.probe_enable(True)
     if ddp is not None:
         ddp.reducer.reset_stats()
     if dist_on:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for i in range(a.steps):
+        if init is not None and i == a.steps - 1:  # (outside the clock)
+            torch.cuda.synchronize()
+            t_pause = time.perf_counter()
+            restore_initial_state(core.transformer.parameters(), init, optimizer)
+            torch.cuda.synchronize()
+            t0 += time.perf_counter() - t_pause
         loss = step()
     host_ms = (time.perf_counter() - t0) / a.steps * 1e3  # host time to ENQUEUE a step (no device wait): < ms_per_step => GPU-bound
     torch.cuda.synchronize()
@@ -307,22 +370,28 @@ def main():
         print(f"[bench] closing barrier took {(time.perf_counter() - t_sync) * 1e3:.2f} ms", file=sys.stderr, flush=True)
     rank_ms = None
     if dist_on:
-        # per-rank wall time of the K steps up to the rank's own synchronize (before the closing barrier): the spread shows stragglers
-        own = torch.tensor([(t_sync - t0) / a.steps * 1e3], device=dev, dtype=torch.float64)
-        allr = [torch.zeros_like(own) for _ in range(dist.get_world_size())]
-        dist.all_gather(allr, own)
-        rank_ms = [round(float(x.item()), 3) for x in allr]
+        if a.full:
+            # per-rank wall time of the K steps up to the rank's own synchronize (before the closing barrier): the spread shows stragglers
+            own = torch.tensor([(t_sync - t0) / a.steps * 1e3], device=dev, dtype=torch.float64)
+            allr = [torch.zeros_like(own) for _ in range(dist.get_world_size())]
+            dist.all_gather(allr, own)
+            rank_ms = [round(float(x.item()), 3) for x in allr]
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    probes = [eng.probe_read(ch) for ch in (0, 1)]
-    eng.probe_enable(False)
+    probes = []
+    if a.full:
+        probes = [eng.probe_read(ch) for ch in (0, 1)]
+        eng.probe_enable(False)
     lossv = float(loss.item())
     reducer_stats = ddp.reducer.stats() if ddp is not None else None  # (of the timed steps only: the probe steps below reduce too)
+    if a.dump_outputs and rank == 0:  # before the probe steps below move the weights on
+        dump_outputs(a.dump_outputs, loss, core.transformer.parameters(), optimizer)
     # OUTSIDE the timed region: three more steps with HIP events around every klab_gemm launch -> the whole GEMM family's
     # sum(2 M N K) / sum(duration) (every Linear / dgrad / LM-head product of the step; the grouped weight gradients are channel 1)
     family = None
-    if rank == 0:
+    in_sync = None
+    if a.full and rank == 0:
         import ctypes as C
         from klab_multimodalmodel_amd import _lib as L
         lib = L.load()
@@ -335,12 +404,11 @@ def main():
             if lib.klab_gemm_probe_read(C.byref(n), C.byref(tms), C.byref(fl)) == 0 and n.value > 0 and tms.value > 0:
                 family = (n.value / fam_steps, tms.value / fam_steps, fl.value / fam_steps)
             lib.klab_gemm_probe_enable(0)
-    elif dist_on:
+    elif a.full and dist_on:
         for _ in range(3):  # keep the ranks' collectives paired with rank 0's probe steps
             step()
         torch.cuda.synchronize()
-    in_sync = None
-    if dist_on:  # (outside the timed region) after K optimizer steps every replica must hold the same weights
+    if a.full and dist_on:  # (outside the timed region) after K optimizer steps every replica must hold the same weights
         chk = torch.stack([p.detach().double().sum() for p in core.transformer.parameters()]).sum().view(1)
         lo, hi = chk.clone(), chk.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
@@ -402,7 +470,7 @@ def main():
             if len(rl) > 1:
                 out["roofline_secondary"] = rl[1:]
         print(f"[bench] gpu leg done: {value:.1f} samples/s, {ms:.2f} ms/step", file=sys.stderr, flush=True)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         sys.stdout.flush()
         os.dup2(_stdout_fd, 1)

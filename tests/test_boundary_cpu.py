@@ -324,3 +324,15 @@ def test_bench_refuses_to_measure_fewer_ranks_than_asked_for():
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
+
+
+@pytest.mark.parametrize("steps,warmup", [("0", "1"), ("2", "-1")])
+def test_bench_refuses_a_run_without_timed_steps(steps, warmup):
+    """--steps sets the number of timed steps: fewer than one (or a negative warm-up) is refused before any GPU work."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", warmup],
+                       cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+    assert not [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]

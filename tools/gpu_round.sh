@@ -16,7 +16,7 @@ if [ "$SUITE" = "suite" ]; then
   echo "[gpu_round] pytest rc=$rc"
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 fi
-timeout -k 10 400 python bench.py --steps 30 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; rc=$?
+timeout -k 10 400 python bench.py --steps 30 --warmup 5 --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; rc=$?
 echo "[gpu_round] bench rc=$rc"; cat $OUT/${TAG}_bench.json | cut -c1-400
 if [ $rc -ne 0 ]; then tail -n 20 $OUT/${TAG}_bench.err; exit $rc; fi
 if [ "$TRACE" = "trace" ]; then
