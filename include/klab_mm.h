@@ -433,6 +433,64 @@ int klab_engine_decode_step(klab_engine* e, int t, const long long* prev_tokens,
 /* one query row per (batch, head) against cached keys / values (element strides; bias_row [H, bias_ld] or NULL) */
 int klab_t5_decode_attn(int dtype, const void* q, long q_bstride, const void* k, const void* v, long kv_bstride, long ldk,
                         const float* bias_row, long bias_ld, void* ctx, long ctx_bstride, int B, int H, int Lk, int dk, void* stream);
+/* the same for R = B*k beam rows.  Key j of query row r is read at row  s*kv_bstride + j*ldk  (element offsets from k / v) where
+ * s = kv_slot[r*slot_ld + j] when kv_slot (int32 [R, slot_ld]) is given, else s = r / kv_group (cross-attention: k beams share
+ * their sample's encoder K/V).  kv_group 1 and kv_slot NULL is klab_t5_decode_attn, bit for bit.                          */
+int klab_t5_beam_decode_attn(int dtype, const void* q, long q_bstride, const void* k, const void* v, long kv_bstride, long ldk,
+                             int kv_group, const int* kv_slot, long slot_ld, const float* bias_row, long bias_ld, void* ctx,
+                             long ctx_bstride, int R, int H, int Lk, int dk, void* stream);
+
+/* ---- beam search (HF `_beam_search`, transformers/generation/utils.py; csrc/beam.hip) ------------------------------------
+ * klab_beam_topk: per sample b, the 2k best of  log_softmax(logits row b*k+j) + run_score[b*k+j]  over all j < k and tokens,
+ * as (score, flat index j*V + token), sorted descending; equal scores rank by the LOWER flat index.  Logits row r is read at
+ * logits + (r / row_div) * ld (row_div k: one row per sample, e.g. the prefill's).  row_score / row_idx: scratch [B*k, 2k];
+ * out_score / out_idx: [B, 2k].  1 <= k <= 16, V >= 2k.                                                                   */
+int klab_beam_topk(int dtype, const void* logits, long ld, int row_div, const float* run_score, int B, int k, int V, float* row_score,
+                   int* row_idx, float* out_score, int* out_idx, void* stream);
+/* fixed-shape beam state of B samples x k beams, rows r = b*k + j; sequences are [B*k, max_length] int64 (position 0 = the
+ * decoder start token).  *_in / *_out are the previous and the next step's buffers (ping-pong); slot_in / slot_out: the key-slot
+ * tables of klab_t5_beam_decode_attn (both NULL: none).  early_stopping: 0 False, 1 True, 2 "never".                        */
+typedef struct {
+  int B, k, V, max_length, eos_id, early_stopping;
+  float length_penalty;
+  const float* cand_score; const int* cand_idx;         /* [B, 2k] from klab_beam_topk */
+  const long long* run_seq_in; long long* run_seq_out;  /* running hypotheses */
+  float* run_score;                                     /* [B*k] running scores (HF running_beam_scores) */
+  const long long* fin_seq_in; long long* fin_seq_out;  /* finished pool (HF sequences) */
+  float* fin_score; int* fin_flag; int* fin_len;        /* [B*k] HF beam_scores, is_sent_finished, generated tokens */
+  int* unsat;                                           /* [B] HF is_early_stop_heuristic_unsatisfied */
+  const int* slot_in; int* slot_out;                    /* [B*k, max_length] or NULL */
+  long long* prev_tokens; int* parent;                  /* [B*k] next decoder input ids; parent row of every new beam */
+  int* stop_word;                                       /* [max_length]: bits OR-ed into stop_word[cur_len] */
+} klab_beam_update_args;
+/* one step of HF's bookkeeping at cur_len (1 <= cur_len < max_length; the candidates' tokens go to position cur_len):
+ * running beams, finished pool, early-stop heuristic.  stop_word[cur_len] |= 1 (some sample's heuristic is unsatisfied),
+ * 2 (some sample's pool holds an unfinished entry), 4 (some candidate did not hit EOS / max_length).  The search goes on
+ * iff bit 1 and bit 4 are set and, with early_stopping True, bit 2.                                                       */
+int klab_beam_update(const klab_beam_update_args* a, int cur_len, void* stream);
+/* the state before the first update (writes run_seq_in / fin_seq_in = start_id then fill_id, slot_in[r][0] = r, the scores,
+ * flags, unsat and every stop word): HF's running_beam_scores 0 / -1e9, beam_scores -1e9, nothing finished               */
+int klab_beam_init(const klab_beam_update_args* a, int start_id, int fill_id, void* stream);
+/* dst row r = src row r / src_div (elem_bytes 2, 4 or 8; element strides) */
+int klab_beam_copy_rows(int elem_bytes, const void* src, long src_ld, int src_div, void* dst, long dst_ld, int rows, int cols,
+                        void* stream);
+/* Beam-search generation on an engine binding.  The workspace (klab_engine_beam_workspace_bytes) is caller-owned and separate from
+ * the binding's: decoder scratch for B*k rows, the per-layer self-attention cache [B*k*max_length, 3*inner], the beam logits
+ * [B*k, V], the key-slot tables and the beam state.
+ * beam_begin: after a klab_engine_forward in evaluation mode at B rows with Lt >= max_length - 1; copies position 0's self K/V
+ *   into every beam's cache slot, initialises the state and runs HF's first step (cur_len 1) on the prefill's logits.
+ *   fill_id: HF's output fill value (pad_token_id, or eos when that is 0).
+ * beam_step(t): the decoder over position t (1 <= t <= max_length - 2) for all B*k beams, then top-2k and the update at
+ *   cur_len t + 1.  Three launches beyond klab_engine_decode_step's chain.
+ * beam_stop_word: device address of the stop word of cur_len (read after the step; see klab_beam_update).
+ * beam_result: the first n of each sample's finished pool (sorted by score): seq [B*n, max_length] int64, scores [B*n] f32,
+ *   len [B*n] int32 (generated tokens, the start token excluded).                                                          */
+size_t klab_engine_beam_workspace_bytes(klab_engine* e, int num_beams, int max_length);
+int klab_engine_beam_begin(klab_engine* e, int num_beams, int max_length, float length_penalty, int early_stopping_mode, int eos_id,
+                           int fill_id, void* ws, void* stream);
+int klab_engine_beam_step(klab_engine* e, int t, void* ws, void* stream);
+const int* klab_engine_beam_stop_word(klab_engine* e, void* ws, int cur_len);
+int klab_engine_beam_result(klab_engine* e, void* ws, int num_return_sequences, long long* seq, float* scores, int* len, void* stream);
 /* segment 0: LM head + decoder + tied embedding; 1: encoder; 2: Swin (no-op unless train_swin).
  * dloss_dev: device scalar d(objective)/d(loss) (NULL = 1).                                       */
 int klab_engine_backward(klab_engine* e, int segment, const float* dloss_dev, void* stream);

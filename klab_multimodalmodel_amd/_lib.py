@@ -50,6 +50,13 @@ class SwinAttnArgs(C.Structure):
                 ("v_bias", vp), ("dv_bias", vp)]
 
 
+class BeamUpdateArgs(C.Structure):  # klab_beam_update_args
+    _fields_ = [("B", i32), ("k", i32), ("V", i32), ("max_length", i32), ("eos_id", i32), ("early_stopping", i32), ("length_penalty", f32),
+                ("cand_score", vp), ("cand_idx", vp), ("run_seq_in", vp), ("run_seq_out", vp), ("run_score", vp),
+                ("fin_seq_in", vp), ("fin_seq_out", vp), ("fin_score", vp), ("fin_flag", vp), ("fin_len", vp), ("unsat", vp),
+                ("slot_in", vp), ("slot_out", vp), ("prev_tokens", vp), ("parent", vp), ("stop_word", vp)]
+
+
 # every exported entry point of include/klab_mm.h: name -> argtypes (restype is always int)
 SIGNATURES = {
     "klab_version": [],
@@ -74,6 +81,11 @@ SIGNATURES = {
     "klab_t5_attn_bwd": [C.POINTER(AttnArgs), vp],
     "klab_t5_attn_fused_fwd": [C.POINTER(AttnFusedArgs), vp],
     "klab_t5_decode_attn": [i32, vp, i64, vp, vp, i64, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp],
+    "klab_t5_beam_decode_attn": [i32, vp, i64, vp, vp, i64, i64, i32, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp],
+    "klab_beam_topk": [i32, vp, i64, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp],
+    "klab_beam_update": [C.POINTER(BeamUpdateArgs), i32, vp],
+    "klab_beam_init": [C.POINTER(BeamUpdateArgs), i32, i32, vp],
+    "klab_beam_copy_rows": [i32, vp, i64, i32, vp, i64, i32, i32, vp],
     "klab_dbias_reduce": [vp, i32, vp, i32, i32, i32, i32, vp],
     "klab_swin_mlp_fused": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "klab_gemm_grouped": [vp, i32, vp],

@@ -373,19 +373,24 @@ extern "C" int klab_dbias_reduce(const void* ds_ws, int dtype, float* dbias, int
 //   bias_row: [H, bias_ld] values for THIS query position (relative-position bias row t), NULL for cross-attention
 // Lanes split the keys (online softmax per lane, merged by a wave reduction); head dim 16 / 32 / 64 / 128, T = f32 | bf16.
 namespace klab {
-template <typename T, int DK>
+// Beam rows (klab_t5_beam_decode_attn): key j of query row r sits at row s*kv_bstride + j*ldk with s = kv_slot[r*slot_ld + j]
+// (SLOT) or s = r / kv_group; the greedy call is kv_group 1 without a table (the same addresses, the same arithmetic).
+template <typename T, int DK, bool SLOT>
 __global__ __launch_bounds__(64) void decode_attn_kernel(const T* __restrict__ q, long q_bstride, const T* __restrict__ k, const T* __restrict__ v,
-                                                         long kv_bstride, long ldk, const float* __restrict__ bias_row, long bias_ld,
-                                                         T* __restrict__ ctx, long ctx_bstride, int H, int Lk) {
+                                                         long kv_bstride, long ldk, int kv_group, const int* __restrict__ kv_slot, long slot_ld,
+                                                         const float* __restrict__ bias_row, long bias_ld, T* __restrict__ ctx, long ctx_bstride,
+                                                         int H, int Lk) {
   const int b = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x;
   const T* qr = q + (long)b * q_bstride + h * DK;
+  const int kb = b / kv_group;
   float qv[DK], o[DK];
 #pragma unroll
   for (int c = 0; c < DK; ++c) { qv[c] = to_f32(qr[c]); o[c] = 0.f; }
   float m = -INFINITY, l = 0.f;
   for (int j = lane; j < Lk; j += 64) {
-    const T* kr = k + (long)b * kv_bstride + (long)j * ldk + h * DK;
-    const T* vr = v + (long)b * kv_bstride + (long)j * ldk + h * DK;
+    const long srow = SLOT ? (long)kv_slot[(long)b * slot_ld + j] : (long)kb;
+    const T* kr = k + srow * kv_bstride + (long)j * ldk + h * DK;
+    const T* vr = v + srow * kv_bstride + (long)j * ldk + h * DK;
     float s = 0.f;
 #pragma unroll
     for (int c = 0; c < DK; ++c) s += qv[c] * to_f32(kr[c]);  // unscaled scores (HF/t5:196-197)
@@ -414,11 +419,16 @@ __global__ __launch_bounds__(64) void decode_attn_kernel(const T* __restrict__ q
   }
 }
 template <typename T>
-static int launch_decode_attn(const void* q, long q_bstride, const void* k, const void* v, long kv_bstride, long ldk, const float* bias_row,
-                              long bias_ld, void* ctx, long ctx_bstride, int B, int H, int Lk, int dk, hipStream_t s) {
+static int launch_decode_attn(const void* q, long q_bstride, const void* k, const void* v, long kv_bstride, long ldk, int kv_group,
+                              const int* kv_slot, long slot_ld, const float* bias_row, long bias_ld, void* ctx, long ctx_bstride, int B,
+                              int H, int Lk, int dk, hipStream_t s) {
 #define DEC_LAUNCH(D)                                                                                                              \
-  hipLaunchKernelGGL((decode_attn_kernel<T, D>), dim3(B * H), dim3(64), 0, s, (const T*)q, q_bstride, (const T*)k, (const T*)v, kv_bstride, \
-                     ldk, bias_row, bias_ld, (T*)ctx, ctx_bstride, H, Lk)
+  if (kv_slot)                                                                                                                     \
+    hipLaunchKernelGGL((decode_attn_kernel<T, D, true>), dim3(B * H), dim3(64), 0, s, (const T*)q, q_bstride, (const T*)k, (const T*)v, \
+                       kv_bstride, ldk, kv_group, kv_slot, slot_ld, bias_row, bias_ld, (T*)ctx, ctx_bstride, H, Lk);              \
+  else                                                                                                                             \
+    hipLaunchKernelGGL((decode_attn_kernel<T, D, false>), dim3(B * H), dim3(64), 0, s, (const T*)q, q_bstride, (const T*)k, (const T*)v, \
+                       kv_bstride, ldk, kv_group, kv_slot, slot_ld, bias_row, bias_ld, (T*)ctx, ctx_bstride, H, Lk)
   switch (dk) {
     case 16: DEC_LAUNCH(16); break;
     case 32: DEC_LAUNCH(32); break;
@@ -438,7 +448,24 @@ extern "C" int klab_t5_decode_attn(int dtype, const void* q, long q_bstride, con
   using namespace klab;
   if (!q || !k || !v || !ctx || B <= 0 || H <= 0 || Lk <= 0) return KLAB_ERR_BADARG;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == KLAB_BF16) return launch_decode_attn<bf16_t>(q, q_bstride, k, v, kv_bstride, ldk, bias_row, bias_ld, ctx, ctx_bstride, B, H, Lk, dk, s);
-  if (dtype == KLAB_F32) return launch_decode_attn<float>(q, q_bstride, k, v, kv_bstride, ldk, bias_row, bias_ld, ctx, ctx_bstride, B, H, Lk, dk, s);
+  if (dtype == KLAB_BF16)
+    return launch_decode_attn<bf16_t>(q, q_bstride, k, v, kv_bstride, ldk, 1, nullptr, 0, bias_row, bias_ld, ctx, ctx_bstride, B, H, Lk, dk, s);
+  if (dtype == KLAB_F32)
+    return launch_decode_attn<float>(q, q_bstride, k, v, kv_bstride, ldk, 1, nullptr, 0, bias_row, bias_ld, ctx, ctx_bstride, B, H, Lk, dk, s);
+  return KLAB_ERR_BADARG;
+}
+
+extern "C" int klab_t5_beam_decode_attn(int dtype, const void* q, long q_bstride, const void* k, const void* v, long kv_bstride, long ldk,
+                                        int kv_group, const int* kv_slot, long slot_ld, const float* bias_row, long bias_ld, void* ctx,
+                                        long ctx_bstride, int R, int H, int Lk, int dk, void* stream) {
+  using namespace klab;
+  if (!q || !k || !v || !ctx || R <= 0 || H <= 0 || Lk <= 0 || kv_group < 1 || (kv_slot && slot_ld < Lk)) return KLAB_ERR_BADARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == KLAB_BF16)
+    return launch_decode_attn<bf16_t>(q, q_bstride, k, v, kv_bstride, ldk, kv_group, kv_slot, slot_ld, bias_row, bias_ld, ctx, ctx_bstride, R, H,
+                                      Lk, dk, s);
+  if (dtype == KLAB_F32)
+    return launch_decode_attn<float>(q, q_bstride, k, v, kv_bstride, ldk, kv_group, kv_slot, slot_ld, bias_row, bias_ld, ctx, ctx_bstride, R, H,
+                                     Lk, dk, s);
   return KLAB_ERR_BADARG;
 }

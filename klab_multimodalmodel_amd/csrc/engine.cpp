@@ -131,6 +131,8 @@ struct klab_engine {
   // greedy decoding with a K/V cache (klab_engine_decode_step): one position per sample, contiguous [B, .] rows
   float* dc_h[2] = {nullptr, nullptr}; float* dc_rstd = nullptr;
   void *dc_xn = nullptr, *dc_q = nullptr, *dc_ctx = nullptr, *dc_hmid = nullptr, *dc_out = nullptr, *dc_logits = nullptr;
+  // beam search (klab_engine_beam_*): parameters of the search begun last on this binding, cur_len of its last update
+  int bm_k = 0, bm_len = 0, bm_mode = 0, bm_eos = 1, bm_cur = 0; float bm_lp = 1.f;
   // lang scratch (no grad => reused across layers)
   void* kv_all = nullptr; void* dkv_all = nullptr;
   void* logits = nullptr; float *loss_row = nullptr, *inv_n = nullptr, *loss = nullptr;
@@ -1799,6 +1801,73 @@ extern "C" const void* klab_engine_buffer(const klab_engine* e, const char* name
   return nullptr;
 }
 
+namespace {
+// The rows of one decoder step over the self-attention K/V cache: greedy decoding (B rows; layer i's cache is the binding's
+// q|k|v buffer, row block b at b*Lt) or beam search (B*k rows; layer i's cache at cache + i*cache_layer, slot block s at
+// s*max_length, key j of row r in slot kv_slot[r][j]; the k beams of a sample share its cross-attention K/V).
+struct DecodeRows {
+  int M;
+  float* h[2]; float* rstd;
+  void *xn, *q, *ctx, *hmid, *out, *logits;
+  void* cache = nullptr; long cache_layer = 0; int cache_rows = 0;
+  int kv_group = 1; const int* kv_slot = nullptr; long slot_ld = 0;
+};
+
+// the decoder over position t for r.M rows whose input ids are tokens [M], logits -> r.logits [M, vocab]
+int decode_rows(klab_engine* e, const Ctx& c, int t, const long long* tokens, const DecodeRows& r) {
+  const klab_t5_cfg& cfg = e->cfg.main;
+  const auto& P = e->P[2];
+  const auto& W = e->W[2];
+  const int M = r.M, Lt = e->Lt, Le = e->Le, d = cfg.d_model, H = cfg.n_heads, dk = cfg.d_kv, inner = H * dk, ff = cfg.d_ff;
+  const int nld = cfg.n_dec_layers;
+  const long kv_ld = (long)nld * 2 * inner;
+  const long self_ld = (long)(r.cache ? r.cache_rows : Lt) * 3 * inner;  // elements between the row blocks of two slots
+  RC(klab_embed_fwd(tokens, 0, 1, cfg.start_id, cfg.pad_id, W[e->mi.shared], cfg.vocab, r.h[0], M, d, 0.f, nullptr, 0, e->err_dev,
+                    c.ws()));
+  float* h = r.h[0];
+  float* h2 = r.h[1];
+  auto proj_res = [&](const void* x, int K, long woffv) -> int {  // h2 = h + x @ W^T  (f32 residual stream)
+    klab_gemm_args g = G0(c, M, d, K, x, K, 1, woff(c, woffv), K, 1, h2, d, KLAB_F32);
+    g.residual = h; g.ldr = d; g.r_dtype = KLAB_F32;
+    RC(fwd_gemm(c, g, woffv));
+    float* tmp = h; h = h2; h2 = tmp;
+    return 0;
+  };
+  for (int i = 0; i < nld; ++i) {
+    const T5LayerIdx& l = e->mi.dec[i];
+    void* qkv = r.cache ? eoff(c, r.cache, (long)i * r.cache_layer) : e->dec.L[i].qkv;
+    // self attention over the cache
+    RC(klab_rmsnorm_fwd(h, W[l.ln0], r.xn, c.dt, nullptr, r.rstd, M, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
+    {
+      klab_gemm_args g = G0(c, M, 3 * inner, d, r.xn, d, 1, woff(c, P[l.q].warena_off), d, 1, eoff(c, qkv, (long)t * 3 * inner), self_ld, c.dt);
+      RC(fwd_gemm(c, g, P[l.q].warena_off));
+    }
+    RC(klab_t5_beam_decode_attn(c.dt, eoff(c, qkv, (long)t * 3 * inner), self_ld, eoff(c, qkv, inner), eoff(c, qkv, 2 * inner), self_ld,
+                                3 * inner, 1, r.kv_slot, r.slot_ld, e->dec.bias + (long)t * Lt, (long)Lt * Lt, r.ctx, inner, M, H, t + 1, dk,
+                                c.ws()));
+    RC(proj_res(r.ctx, inner, P[l.o].warena_off));
+    // cross attention over the encoder K/V projected at prefill
+    RC(klab_rmsnorm_fwd(h, W[l.ln1], r.xn, c.dt, nullptr, r.rstd, M, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
+    RC(linear_fwd(c, r.xn, M, d, P[l.cq].warena_off, inner, r.q, inner, c.dt));
+    RC(klab_t5_beam_decode_attn(c.dt, r.q, inner, eoff(c, e->kv_all, (long)i * 2 * inner), eoff(c, e->kv_all, (long)i * 2 * inner + inner),
+                                (long)Le * kv_ld, kv_ld, r.kv_group, nullptr, 0, nullptr, 0, r.ctx, inner, M, H, Le, dk, c.ws()));
+    RC(proj_res(r.ctx, inner, P[l.co].warena_off));
+    // feed forward
+    RC(klab_rmsnorm_fwd(h, W[l.ln2], r.xn, c.dt, nullptr, r.rstd, M, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
+    RC(linear_fwd(c, r.xn, M, d, P[l.wi].warena_off, ff, r.hmid, ff, c.dt, nullptr, KLAB_ACT_RELU));
+    RC(proj_res(r.hmid, ff, P[l.wo].warena_off));
+  }
+  RC(klab_rmsnorm_fwd(h, W[e->mi.dec_final], r.out, c.dt, nullptr, r.rstd, M, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
+  {
+    const int V = cfg.vocab;
+    klab_gemm_args g = G0(c, M, V, d, r.out, d, 1, woff(c, P[e->mi.shared].warena_off), d, 1, r.logits, V, c.dt);
+    g.alpha = cfg.scale_decoder_outputs ? 1.f / sqrtf((float)d) : 1.f;  // HF/t5:1044-1045
+    RC(fwd_gemm(c, g, P[e->mi.shared].warena_off));
+  }
+  return 0;
+}
+}  // namespace
+
 // Greedy decoding with a K/V cache (ref/models/model.py:27-28 -> generate; HF/t5:308-332): the decoder over ONE new position
 // t >= 1 per sample.  Precondition: a klab_engine_forward in evaluation mode on this binding (the prefill: encoder output,
 // cross-attention K/V of all layers, the decoder's position-bias table, and -- position 0 being the start token whatever the
@@ -1809,56 +1878,131 @@ extern "C" const void* klab_engine_buffer(const klab_engine* e, const char* name
 extern "C" int klab_engine_decode_step(klab_engine* e, int t, const long long* prev_tokens, void* stream) {
   if (!e || !e->bound || !prev_tokens || t < 1 || t >= e->Lt) return KLAB_ERR_BADARG;
   Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
+  DecodeRows r;
+  r.M = e->B;
+  r.h[0] = e->dc_h[0]; r.h[1] = e->dc_h[1]; r.rstd = e->dc_rstd;
+  r.xn = e->dc_xn; r.q = e->dc_q; r.ctx = e->dc_ctx; r.hmid = e->dc_hmid; r.out = e->dc_out; r.logits = e->dc_logits;
+  return decode_rows(e, c, t, prev_tokens, r);
+}
+
+// ---- beam search (HF `_beam_search`): a workspace of its own, owned by the caller ------------------------------------------
+namespace {
+struct BeamWs {
+  DecodeRows rows;
+  int* slot[2]; float *row_score, *cand_score; int *row_idx, *cand_idx;
+  long long* prev; int* parent; long long* run_seq[2]; float* run_score; long long* fin_seq[2];
+  float* fin_score; int *fin_flag, *fin_len, *unsat, *stop;
+};
+size_t plan_beam(const klab_engine* e, int k, int Lm, void* base, BeamWs& w) {
+  Bump b(base);
   const klab_t5_cfg& cfg = e->cfg.main;
-  const auto& P = e->P[2];
-  const auto& W = e->W[2];
-  const int B = e->B, Lt = e->Lt, Le = e->Le, d = cfg.d_model, H = cfg.n_heads, dk = cfg.d_kv, inner = H * dk, ff = cfg.d_ff;
-  const int nld = cfg.n_dec_layers;
-  const long kv_ld = (long)nld * 2 * inner;
-  RC(klab_embed_fwd(prev_tokens, 0, 1, cfg.start_id, cfg.pad_id, W[e->mi.shared], cfg.vocab, e->dc_h[0], B, d, 0.f, nullptr, 0, e->err_dev,
-                    c.ws()));
-  float* h = e->dc_h[0];
-  float* h2 = e->dc_h[1];
-  auto proj_res = [&](const void* x, int K, long woffv) -> int {  // h2 = h + x @ W^T  (f32 residual stream)
-    klab_gemm_args g = G0(c, B, d, K, x, K, 1, woff(c, woffv), K, 1, h2, d, KLAB_F32);
-    g.residual = h; g.ldr = d; g.r_dtype = KLAB_F32;
-    RC(fwd_gemm(c, g, woffv));
-    float* tmp = h; h = h2; h2 = tmp;
-    return 0;
-  };
-  for (int i = 0; i < nld; ++i) {
-    const T5LayerIdx& l = e->mi.dec[i];
-    T5LayerBufs& b = e->dec.L[i];
-    // self attention over the cache
-    RC(klab_rmsnorm_fwd(h, W[l.ln0], e->dc_xn, c.dt, nullptr, e->dc_rstd, B, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
-    {
-      klab_gemm_args g = G0(c, B, 3 * inner, d, e->dc_xn, d, 1, woff(c, P[l.q].warena_off), d, 1, eoff(c, b.qkv, (long)t * 3 * inner),
-                            (long)Lt * 3 * inner, c.dt);
-      RC(fwd_gemm(c, g, P[l.q].warena_off));
-    }
-    RC(klab_t5_decode_attn(c.dt, eoff(c, b.qkv, (long)t * 3 * inner), (long)Lt * 3 * inner, eoff(c, b.qkv, inner), eoff(c, b.qkv, 2 * inner),
-                           (long)Lt * 3 * inner, 3 * inner, e->dec.bias + (long)t * Lt, (long)Lt * Lt, e->dc_ctx, inner, B, H, t + 1, dk,
-                           c.ws()));
-    RC(proj_res(e->dc_ctx, inner, P[l.o].warena_off));
-    // cross attention over the encoder K/V projected at prefill
-    RC(klab_rmsnorm_fwd(h, W[l.ln1], e->dc_xn, c.dt, nullptr, e->dc_rstd, B, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
-    RC(linear_fwd(c, e->dc_xn, B, d, P[l.cq].warena_off, inner, e->dc_q, inner, c.dt));
-    RC(klab_t5_decode_attn(c.dt, e->dc_q, inner, eoff(c, e->kv_all, (long)i * 2 * inner), eoff(c, e->kv_all, (long)i * 2 * inner + inner),
-                           (long)Le * kv_ld, kv_ld, nullptr, 0, e->dc_ctx, inner, B, H, Le, dk, c.ws()));
-    RC(proj_res(e->dc_ctx, inner, P[l.co].warena_off));
-    // feed forward
-    RC(klab_rmsnorm_fwd(h, W[l.ln2], e->dc_xn, c.dt, nullptr, e->dc_rstd, B, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
-    RC(linear_fwd(c, e->dc_xn, B, d, P[l.wi].warena_off, ff, e->dc_hmid, ff, c.dt, nullptr, KLAB_ACT_RELU));
-    RC(proj_res(e->dc_hmid, ff, P[l.wo].warena_off));
+  const size_t es = e->es;
+  const long M = (long)e->B * k, d = cfg.d_model, inner = (long)cfg.n_heads * cfg.d_kv, ff = cfg.d_ff, V = cfg.vocab;
+  DecodeRows& r = w.rows;
+  r.M = (int)M;
+  r.h[0] = (float*)b.take(M * d * 4); r.h[1] = (float*)b.take(M * d * 4); r.rstd = (float*)b.take(M * 4);
+  r.xn = b.take(M * d * es); r.q = b.take(M * inner * es); r.ctx = b.take(M * inner * es); r.hmid = b.take(M * ff * es);
+  r.out = b.take(M * d * es); r.logits = b.take(M * V * es);
+  r.cache_layer = M * Lm * 3 * inner; r.cache_rows = Lm;
+  r.cache = b.take((size_t)cfg.n_dec_layers * r.cache_layer * es);
+  r.kv_group = k; r.slot_ld = Lm;
+  for (int p = 0; p < 2; ++p) {
+    w.slot[p] = (int*)b.take(M * Lm * 4);
+    w.run_seq[p] = (long long*)b.take(M * Lm * 8);
+    w.fin_seq[p] = (long long*)b.take(M * Lm * 8);
   }
-  RC(klab_rmsnorm_fwd(h, W[e->mi.dec_final], e->dc_out, c.dt, nullptr, e->dc_rstd, B, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
-  {
-    const int V = cfg.vocab;
-    klab_gemm_args g = G0(c, B, V, d, e->dc_out, d, 1, woff(c, P[e->mi.shared].warena_off), d, 1, e->dc_logits, V, c.dt);
-    g.alpha = cfg.scale_decoder_outputs ? 1.f / sqrtf((float)d) : 1.f;  // HF/t5:1044-1045
-    RC(fwd_gemm(c, g, P[e->mi.shared].warena_off));
-  }
+  w.row_score = (float*)b.take(M * 2 * k * 4); w.row_idx = (int*)b.take(M * 2 * k * 4);
+  w.cand_score = (float*)b.take((long)e->B * 2 * k * 4); w.cand_idx = (int*)b.take((long)e->B * 2 * k * 4);
+  w.prev = (long long*)b.take(M * 8); w.parent = (int*)b.take(M * 4); w.run_score = (float*)b.take(M * 4);
+  w.fin_score = (float*)b.take(M * 4); w.fin_flag = (int*)b.take(M * 4); w.fin_len = (int*)b.take(M * 4);
+  w.unsat = (int*)b.take((long)e->B * 4); w.stop = (int*)b.take((long)Lm * 4);
+  return b.off;
+}
+// the update arguments of cur_len c: reads the buffers of parity c+1, writes those of parity c
+klab_beam_update_args beam_args(const klab_engine* e, const BeamWs& w, int c) {
+  klab_beam_update_args a;
+  memset(&a, 0, sizeof(a));
+  a.B = e->B; a.k = e->bm_k; a.V = e->cfg.main.vocab; a.max_length = e->bm_len; a.eos_id = e->bm_eos; a.early_stopping = e->bm_mode;
+  a.length_penalty = e->bm_lp;
+  a.cand_score = w.cand_score; a.cand_idx = w.cand_idx;
+  a.run_seq_in = w.run_seq[(c + 1) & 1]; a.run_seq_out = w.run_seq[c & 1]; a.run_score = w.run_score;
+  a.fin_seq_in = w.fin_seq[(c + 1) & 1]; a.fin_seq_out = w.fin_seq[c & 1];
+  a.fin_score = w.fin_score; a.fin_flag = w.fin_flag; a.fin_len = w.fin_len; a.unsat = w.unsat;
+  a.slot_in = w.slot[(c + 1) & 1]; a.slot_out = w.slot[c & 1];
+  a.prev_tokens = w.prev; a.parent = w.parent; a.stop_word = w.stop;
+  return a;
+}
+bool beam_shape_ok(const klab_engine* e, int k, int Lm) {
+  return e && e->bound && k >= 1 && k <= 16 && Lm >= 2 && Lm - 1 <= e->Lt && e->cfg.main.vocab >= 2 * k;
+}
+}  // namespace
+
+extern "C" size_t klab_engine_beam_workspace_bytes(klab_engine* e, int num_beams, int max_length) {
+  if (!beam_shape_ok(e, num_beams, max_length)) return 0;
+  BeamWs w;
+  return plan_beam(e, num_beams, max_length, nullptr, w);
+}
+
+// Precondition: klab_engine_forward in evaluation mode on this binding (the prefill; its logits row b*Lt is position 0 of sample b)
+extern "C" int klab_engine_beam_begin(klab_engine* e, int num_beams, int max_length, float length_penalty, int early_stopping_mode,
+                                      int eos_id, int fill_id, void* ws, void* stream) {
+  if (!beam_shape_ok(e, num_beams, max_length) || !ws || early_stopping_mode < 0 || early_stopping_mode > 2) return KLAB_ERR_BADARG;
+  Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
+  const klab_t5_cfg& cfg = e->cfg.main;
+  const int k = num_beams, Lm = max_length, B = e->B, V = cfg.vocab, inner = cfg.n_heads * cfg.d_kv;
+  e->bm_k = k; e->bm_len = Lm; e->bm_mode = early_stopping_mode; e->bm_eos = eos_id; e->bm_lp = length_penalty; e->bm_cur = 0;
+  BeamWs w;
+  plan_beam(e, k, Lm, ws, w);
+  klab_beam_update_args a = beam_args(e, w, 1);
+  RC(klab_beam_init(&a, cfg.start_id, fill_id, c.ws()));
+  // position 0 (the start token) of every beam: the prefill's self q|k|v row of its sample, copied into the beam's own slot
+  for (int i = 0; i < cfg.n_dec_layers; ++i)
+    RC(klab_beam_copy_rows((int)e->es, e->dec.L[i].qkv, (long)e->Lt * 3 * inner, k, eoff(c, w.rows.cache, (long)i * w.rows.cache_layer),
+                           (long)Lm * 3 * inner, B * k, 3 * inner, c.ws()));
+  // HF's first step (cur_len 1) on the prefill's position-0 logits, shared by the k beams of a sample
+  RC(klab_beam_topk(c.dt, e->logits, (long)e->Lt * V, k, w.run_score, B, k, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws()));
+  RC(klab_beam_update(&a, 1, c.ws()));
+  e->bm_cur = 1;
   return 0;
+}
+
+// the decoder over position t for every beam (inputs: the tokens the last update chose), then top-2k and the update at cur_len t+1
+extern "C" int klab_engine_beam_step(klab_engine* e, int t, void* ws, void* stream) {
+  if (!e || !e->bound || !ws || e->bm_k < 1 || t < 1 || t != e->bm_cur || t > e->bm_len - 2 || !beam_shape_ok(e, e->bm_k, e->bm_len))
+    return KLAB_ERR_BADARG;
+  Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
+  const int k = e->bm_k, B = e->B, V = e->cfg.main.vocab;
+  BeamWs w;
+  plan_beam(e, k, e->bm_len, ws, w);
+  DecodeRows r = w.rows;
+  r.kv_slot = w.slot[t & 1];
+  RC(decode_rows(e, c, t, w.prev, r));
+  RC(klab_beam_topk(c.dt, r.logits, V, 1, w.run_score, B, k, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws()));
+  klab_beam_update_args a = beam_args(e, w, t + 1);
+  RC(klab_beam_update(&a, t + 1, c.ws()));
+  e->bm_cur = t + 1;
+  return 0;
+}
+
+extern "C" const int* klab_engine_beam_stop_word(klab_engine* e, void* ws, int cur_len) {
+  if (!e || !ws || e->bm_k < 1 || cur_len < 1 || cur_len >= e->bm_len) return nullptr;
+  BeamWs w;
+  plan_beam(e, e->bm_k, e->bm_len, ws, w);
+  return w.stop + cur_len;
+}
+
+extern "C" int klab_engine_beam_result(klab_engine* e, void* ws, int num_return_sequences, long long* seq, float* scores, int* len,
+                                       void* stream) {
+  const int n = num_return_sequences;
+  if (!e || !ws || e->bm_cur < 1 || n < 1 || n > e->bm_k || !seq || !scores || !len) return KLAB_ERR_BADARG;
+  BeamWs w;
+  plan_beam(e, e->bm_k, e->bm_len, ws, w);
+  const size_t Lm = e->bm_len, k = e->bm_k, B = e->B;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t rc = hipMemcpy2DAsync(seq, n * Lm * 8, w.fin_seq[e->bm_cur & 1], k * Lm * 8, n * Lm * 8, B, hipMemcpyDeviceToDevice, s);
+  if (rc == hipSuccess) rc = hipMemcpy2DAsync(scores, n * 4, w.fin_score, k * 4, n * 4, B, hipMemcpyDeviceToDevice, s);
+  if (rc == hipSuccess) rc = hipMemcpy2DAsync(len, n * 4, w.fin_len, k * 4, n * 4, B, hipMemcpyDeviceToDevice, s);
+  return (int)rc;
 }
 
 // segment 0: LM head + decoder + shared embedding; 1: encoder; 2: Swin

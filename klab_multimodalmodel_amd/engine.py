@@ -117,6 +117,11 @@ ENGINE_SIGS = {
                           C.POINTER(C.c_void_p), C.c_void_p], C.c_int),
     "klab_engine_forward": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p], C.c_int),
     "klab_engine_decode_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+    "klab_engine_beam_workspace_bytes": ([C.c_void_p, C.c_int, C.c_int], C.c_size_t),
+    "klab_engine_beam_begin": ([C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+    "klab_engine_beam_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+    "klab_engine_beam_stop_word": ([C.c_void_p, C.c_void_p, C.c_int], C.c_void_p),
+    "klab_engine_beam_result": ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_backward": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_set_graph": ([C.c_void_p, C.c_int], C.c_int),
     "klab_engine_get_rng": ([C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p], C.c_int),
@@ -357,6 +362,40 @@ class Engine:
     def decode_step(self, t, prev_tokens):
         """decoder over position t (>= 1) only, self-attention K/V from the binding's cache; logits -> buffer("logits_step")"""
         L.check(self._lib.klab_engine_decode_step(self._h, int(t), prev_tokens.data_ptr(), L.stream_ptr()), "klab_engine_decode_step")
+
+    # ---- beam search (HF `_beam_search`); the workspace is the caller's, the binding's is untouched -------------------
+    EARLY_STOPPING = {False: 0, True: 1, "never": 2}
+
+    def beam_workspace_bytes(self, num_beams, max_length):
+        return int(self._lib.klab_engine_beam_workspace_bytes(self._h, int(num_beams), int(max_length)))
+
+    def beam_begin(self, num_beams, max_length, length_penalty, early_stopping, eos_id, fill_id, ws):
+        """after an evaluation-mode forward (the prefill): state init + HF's first step on the prefill's position-0 logits"""
+        mode = self.EARLY_STOPPING[early_stopping]
+        L.check(self._lib.klab_engine_beam_begin(self._h, int(num_beams), int(max_length), float(length_penalty), mode, int(eos_id), int(fill_id),
+                                                 ws.data_ptr(), L.stream_ptr()), "klab_engine_beam_begin")
+
+    def beam_step(self, t, ws):
+        """decoder over position t for all beams, then top-2k and the update at cur_len t + 1"""
+        L.check(self._lib.klab_engine_beam_step(self._h, int(t), ws.data_ptr(), L.stream_ptr()), "klab_engine_beam_step")
+
+    def beam_stop_word(self, ws, cur_len):
+        """int32 view of the stop word the update at cur_len ORs into (bits: 1 improvable, 2 open pool entry, 4 live candidate)"""
+        p = self._lib.klab_engine_beam_stop_word(self._h, ws.data_ptr(), int(cur_len))
+        if not p:
+            raise ValueError("klab: bad argument to klab_engine_beam_stop_word")
+        off = p - ws.data_ptr()
+        return ws[off:off + 4].view(torch.int32)
+
+    def beam_result(self, ws, num_return_sequences, max_length):
+        """(sequences [B*n, max_length] int64, scores [B*n] f32, generated lengths [B*n] int32) of the finished pools"""
+        B, n = self.shape[0], int(num_return_sequences)
+        seq = torch.empty(B * n, int(max_length), dtype=torch.int64, device=ws.device)
+        scores = torch.empty(B * n, dtype=torch.float32, device=ws.device)
+        lens = torch.empty(B * n, dtype=torch.int32, device=ws.device)
+        L.check(self._lib.klab_engine_beam_result(self._h, ws.data_ptr(), n, seq.data_ptr(), scores.data_ptr(), lens.data_ptr(), L.stream_ptr()),
+                "klab_engine_beam_result")
+        return seq, scores, lens
 
     def backward(self, segment, dloss=None):
         L.check(self._lib.klab_engine_backward(self._h, segment, dloss.data_ptr() if dloss is not None else None, L.stream_ptr()),

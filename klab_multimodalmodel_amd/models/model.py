@@ -366,12 +366,23 @@ class MyModel(nn.Module):
         return self.generate(pixels, src)
 
     @torch.no_grad()
-    def generate(self, pixels, src, max_length=20, kv_cache=True):
+    def generate(self, pixels, src, max_length=20, kv_cache=True, num_beams=1, length_penalty=1.0, early_stopping=False,
+                 num_return_sequences=1, return_scores=False):
         """greedy decoding with HF's default generation settings (ref/models/model.py:28: max_length 20, no sampling).
         Prefill = one evaluation-mode forward (Swin, both encoders, the cross K/V of all layers, decoder position 0); every
         further token runs the decoder over ONE new position against the per-layer K/V cache (`klab_engine_decode_step`,
         SURVEY §8 row f-3; HF/t5:308-332).  kv_cache=False keeps the round-1 form -- decoder + LM head over the whole prefix per
-        token -- as the cross-check of the cache."""
+        token -- as the cross-check of the cache.
+        num_beams > 1: HF's beam search (`_beam_search`, `generate(num_beams=...)`) on the device -- see _generate_beam."""
+        if num_return_sequences > num_beams:
+            raise ValueError(f"`num_return_sequences` ({num_return_sequences}) has to be smaller or equal to `num_beams` ({num_beams}).")
+        if num_beams > 1:
+            if not kv_cache:
+                raise ValueError("beam search runs on the K/V cache only: kv_cache=False needs num_beams=1")
+            return self._generate_beam(pixels, src, max_length, num_beams, length_penalty, early_stopping, num_return_sequences,
+                                       return_scores)
+        if return_scores:
+            raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence scores)")
         B = src.shape[0]
         cfg = self.main_cfg
         steps = max_length - 1
@@ -400,6 +411,44 @@ class MyModel(nn.Module):
             self.transformer.train(was_training)
         start = torch.full((B, 1), cfg.decoder_start_token_id, dtype=torch.int64, device=src.device)
         return torch.cat([start, tgt], dim=1)
+
+    def _generate_beam(self, pixels, src, max_length, num_beams, length_penalty, early_stopping, num_return_sequences, return_scores):
+        """One prefill at B rows (Swin, both encoders and the cross K/V run once per sample, not per beam), then the beam state
+        lives on the device: every step is the decoder over B*num_beams rows, top-2k and HF's bookkeeping
+        (`klab_engine_beam_step`); the host reads one stop word per step.  Returns [B*num_return_sequences, L] int64 (start
+        token, pads after EOS, cropped to the longest returned hypothesis), and its scores when return_scores."""
+        if early_stopping not in (False, True, "never"):
+            raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
+        if max_length < 2:
+            raise ValueError("max_length must count the start token and at least one generated token")
+        B = src.shape[0]
+        cfg = self.main_cfg
+        k = int(num_beams)
+        tgt = torch.full((B, max_length - 1), cfg.pad_token_id, dtype=torch.int64, device=src.device)
+        # HF's fill value of unfinished positions: `pad_token_id or eos_token_id` (a pad id of 0 yields to EOS)
+        fill = cfg.pad_token_id or cfg.eos_token_id
+        was_training = self.transformer.training
+        self.transformer.eval()
+        try:
+            eng = self._engine_for(pixels, src, tgt)
+            eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
+            nbytes = eng.beam_workspace_bytes(k, max_length)
+            if nbytes == 0:
+                raise ValueError(f"beam search: unsupported num_beams={k} / max_length={max_length} for this model")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+            eng.beam_begin(k, max_length, length_penalty, early_stopping, cfg.eos_token_id, fill, ws)
+            cur = 1
+            while True:
+                w = int(eng.beam_stop_word(ws, cur).item())  # the one host sync per step
+                if not ((w & 1) and (w & 4) and (early_stopping is not True or (w & 2))) or cur >= max_length - 1:
+                    break
+                eng.beam_step(cur, ws)
+                cur += 1
+            seq, scores, lens = eng.beam_result(ws, num_return_sequences, max_length)
+        finally:
+            self.transformer.train(was_training)
+        seq = seq[:, :1 + int(lens.max())]
+        return (seq, scores) if return_scores else seq
 
     def _join_pending_update(self):
         """an optimizer update still running on its own stream (optim.FusedAdam(step_in_backward=True)) writes the weights:
