@@ -178,6 +178,19 @@ typedef struct klab_attn_fused_args {
   klab_attn_args attn;
 } klab_attn_fused_args;
 int klab_t5_attn_fused_fwd(const klab_attn_fused_args* a, void* stream);
+/* Back half of a T5 attention sub-layer in ONE launch (backward): the o / co projection dgrad dctx_h = dy W[:, h*dk : h*dk+dk]
+ * (K = d_model; bf16-rounded as the klab_gemm output, kept on chip, never written) -> delta = rowsum(dctx_h * ctx) -> the attention
+ * backward (dq | dk | dv, and dS to attn.ds_ws / attn.dbias exactly as klab_t5_attn_bwd), one workgroup per (sample, head).
+ * Replaces the projection klab_gemm + klab_t5_attn_bwd; attn.dctx / attn.lddo are ignored.  Envelope: bf16, d_model = 512,
+ * head dim 64, H * dk = 512, 1 <= Lq, Lk <= 64, no score_scale / bias_mod; otherwise KLAB_ERR_UNSUPPORTED and the caller issues
+ * the two launches.                                                                                                            */
+typedef struct klab_attn_bwd_fused_args {
+  const void* dy; long lddy; /* [B*Lq, d_model] bf16: gradient of the projection's output */
+  const void* w;             /* [d_model, H*dk] bf16: the o / co projection weight (nn.Linear layout) */
+  int d_model;
+  klab_attn_args attn;
+} klab_attn_bwd_fused_args;
+int klab_t5_attn_bwd_fused(const klab_attn_bwd_fused_args* a, void* stream);
 /* dbias[H,Lq,Lk] += sum over nbatch slabs of ds_ws [nbatch, H, Lq, roundup(Lk,32)] (bf16), in a fixed order */
 int klab_dbias_reduce(const void* ds_ws, int dtype, float* dbias, int nbatch, int H, int Lq, int Lk, void* stream);
 

@@ -42,6 +42,10 @@ class AttnFusedArgs(C.Structure):  # klab_attn_fused_args
                 ("cross", i32), ("attn", AttnArgs)]
 
 
+class AttnBwdFusedArgs(C.Structure):  # klab_attn_bwd_fused_args
+    _fields_ = [("dy", vp), ("lddy", i64), ("w", vp), ("d_model", i32), ("attn", AttnArgs)]
+
+
 class SwinAttnArgs(C.Structure):
     _fields_ = [("dtype", i32), ("qkv", vp), ("ctx", vp), ("bias", vp), ("logit_scale", vp), ("lse", vp),
                 ("B", i32), ("R", i32), ("w", i32), ("shift", i32), ("H", i32), ("C", i32),
@@ -80,6 +84,7 @@ SIGNATURES = {
     "klab_t5_attn_fwd": [C.POINTER(AttnArgs), vp],
     "klab_t5_attn_bwd": [C.POINTER(AttnArgs), vp],
     "klab_t5_attn_fused_fwd": [C.POINTER(AttnFusedArgs), vp],
+    "klab_t5_attn_bwd_fused": [C.POINTER(AttnBwdFusedArgs), vp],
     "klab_t5_decode_attn": [i32, vp, i64, vp, vp, i64, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp],
     "klab_t5_beam_decode_attn": [i32, vp, i64, vp, vp, i64, i64, i32, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp],
     "klab_beam_topk": [i32, vp, i64, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp],

@@ -743,6 +743,12 @@ static bool attn_fused_on() {
   static const bool on = [] { const char* v = getenv("KLAB_T5_ATTN_FUSED"); return !v || atoi(v) != 0; }();
   return on;
 }
+// A/B switch of the fused attention back half (klab_t5_attn_bwd_fused): KLAB_T5_ATTN_BWD_FUSED=0 keeps the o / co dgrad GEMM +
+// klab_t5_attn_bwd
+static bool attn_bwd_fused_on() {
+  static const bool on = [] { const char* v = getenv("KLAB_T5_ATTN_BWD_FUSED"); return !v || atoi(v) != 0; }();
+  return on;
+}
 
 // ------------------------------------------------------------------------------------------------
 // T5 stack forward (HF/t5:663-750); `h[0]` must already hold dropout(inputs_embeds)
@@ -933,6 +939,21 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
   else RC(hipMemsetAsync(s.dbias, 0, (size_t)H * Lq * Lq * 4, c.s));
   // final norm: y = drop(norm(h[j])); previous sub-layer output dropout = FFN_OUT of the last layer
   void* dy = next_dy();  // masked, compute-dtype gradient of the current sub-layer's GEMM output
+  // back half of an attention sub-layer: the o / co projection dgrad (dy -> dctx) + the attention backward.  One launch where the
+  // fused kernel's envelope allows (bf16, d_model 512, head dim 64, <= 64 tokens per sample); otherwise the dgrad GEMM (once) +
+  // klab_t5_attn_bwd.  KLAB_ERR_UNSUPPORTED of the attention kernel is returned for the caller's retry (ds_defer).
+  bool dctx_ready = false;
+  auto attn_bwd = [&](klab_attn_args& a, long wo_off) -> int {
+    if (attn_bwd_fused_on() && c.dt == KLAB_BF16) {
+      klab_attn_bwd_fused_args fb;
+      memset(&fb, 0, sizeof(fb));
+      fb.dy = dy; fb.lddy = d; fb.w = woff(c, wo_off); fb.d_model = d; fb.attn = a;
+      const int frc = klab_t5_attn_bwd_fused(&fb, c.ws());
+      if (frc != KLAB_ERR_UNSUPPORTED) return frc;
+    }
+    if (!dctx_ready) { RC(linear_dgrad(c, dy, d, M, d, wo_off, inner, e->dctx, c.dt)); dctx_ready = true; }
+    return klab_t5_attn_bwd(&a, c.ws());
+  };
   RC(rms_bwd(e->dxn, s.h[j], W[final_ln], s.rstd_f, nullptr, dh_cur, dy, final_ln, p, tag_of(stack_id, 0, SITE_FINAL), p,
              tag_of(stack_id, (int)L.size() - 1, SITE_FFN_OUT)));
   std::vector<int> pending_buckets;  // layers whose weight gradients are queued but not yet launched
@@ -989,7 +1010,7 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
       --j;
       void* dqc = e->dqc_pool[i];
       wq.push(dy, d, b.ctx2, inner, M, d, inner, G(l.co));
-      RC(linear_dgrad(c, dy, d, M, d, P[l.co].warena_off, inner, e->dctx, c.dt));
+      dctx_ready = false;
       klab_attn_args a;
       memset(&a, 0, sizeof(a));
       a.dtype = c.dt; a.q = b.qc; a.ldq = inner;
@@ -1000,7 +1021,7 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
       a.dctx = e->dctx; a.lddo = inner; a.dq = dqc; a.lddq = inner;
       a.dk_out = eoff(c, dkv_all, (long)i * 2 * inner); a.lddk = kv_ld;
       a.dv = eoff(c, dkv_all, (long)i * 2 * inner + inner); a.lddv = kv_ld;
-      RC(klab_t5_attn_bwd(&a, c.ws()));
+      RC(attn_bwd(a, P[l.co].warena_off));
       if (kv_in_queue) {  // this layer's k | v projection: its slice of d(k|v) is final, the product joins the layer's group
         wq.push(eoff(c, dkv_all, (long)i * 2 * inner), kv_ld, e->enc.out_t, d, B * Lkv, 2 * inner, d, Gflat + e->kvall_g_off + (long)i * 2 * inner * d);
         e->kv_wgrad_done = true;
@@ -1014,7 +1035,7 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
     // ---------------- self attention ----------------
     --j;
     wq.push(dy, d, b.ctx, inner, M, d, inner, G(l.o));
-    RC(linear_dgrad(c, dy, d, M, d, P[l.o].warena_off, inner, e->dctx, c.dt));
+    dctx_ready = false;
     {
       klab_attn_args a;
       memset(&a, 0, sizeof(a));
@@ -1029,10 +1050,10 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
       if (c.dt == KLAB_BF16 && deferred == (int)L.size() - 1 - i) {  // store dS per layer; ONE reduction after the stack
         a.ds_defer = 1;
         a.ds_ws = (char*)e->ds_ws + (size_t)deferred * B * H * Lq * ((Lq + 31) & ~31) * c.es;
-        arc = klab_t5_attn_bwd(&a, c.ws());
+        arc = attn_bwd(a, P[l.o].warena_off);
         if (arc == 0) ++deferred;
       }
-      if (arc == KLAB_ERR_UNSUPPORTED) { a.ds_defer = 0; a.ds_ws = nullptr; arc = klab_t5_attn_bwd(&a, c.ws()); }
+      if (arc == KLAB_ERR_UNSUPPORTED) { a.ds_defer = 0; a.ds_ws = nullptr; arc = attn_bwd(a, P[l.o].warena_off); }
       RC(arc);
     }
     wq.push(dqkv, 3 * inner, b.xn1, d, M, 3 * inner, d, G(l.q));  // q|k|v grads are adjacent

@@ -237,6 +237,23 @@ def t5_attn_bwd(q, k, v, ctx, lse, dctx, dq, dk_out, dv, *, B, H, Lq, Lk, dk, bi
     L.check(lib.klab_t5_attn_bwd(C.byref(a), L.stream_ptr()), "klab_t5_attn_bwd")
 
 
+def t5_attn_bwd_fused(dy, w, q, k, v, ctx, lse, dq, dk_out, dv, *, B, H, Lq, Lk, dk, bias=None, causal=False, dbias=None, ds_ws=None,
+                      ds_defer=False, drop_p=0.0, seed=None, tag=0, ldq=None, ldk=None, ldv=None, ldo=None, lddq=None, lddk=None, lddv=None):
+    """o / co projection dgrad (dy @ w, kept on chip) -> attention backward in one launch (klab_t5_attn_bwd_fused); NotImplementedError
+    outside the envelope (bf16, d_model 512, head dim 64, H * dk = 512, at most 64 queries / keys)"""
+    lib = L.load()
+    fb = L.AttnBwdFusedArgs()
+    fb.dy, fb.lddy, fb.w, fb.d_model = dy.data_ptr(), dy.stride(0), w.data_ptr(), dy.shape[1]
+    a = _attn_args(q, k, v, ctx, lse, bias, causal, B, H, Lq, Lk, dk, drop_p, seed, tag,
+                   ldq or q.stride(0), ldk or k.stride(0), ldv or v.stride(0), ldo or ctx.stride(0))
+    a.dq, a.lddq = dq.data_ptr(), lddq or dq.stride(0)
+    a.dk_out, a.lddk = dk_out.data_ptr(), lddk or dk_out.stride(0)
+    a.dv, a.lddv = dv.data_ptr(), lddv or dv.stride(0)
+    a.dbias, a.ds_ws, a.ds_defer = L.ptr(dbias), L.ptr(ds_ws), int(ds_defer)
+    fb.attn = a
+    L.check(lib.klab_t5_attn_bwd_fused(C.byref(fb), L.stream_ptr()), "klab_t5_attn_bwd_fused")
+
+
 def _swin_args(qkv, ctx, bias, logit_scale, lse, B, R, w, shift, H, Cc, bias_table=None, v_bias=None, dv_bias=None):
     a = L.SwinAttnArgs()
     a.v_bias, a.dv_bias = L.ptr(v_bias), L.ptr(dv_bias)
