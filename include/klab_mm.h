@@ -504,6 +504,48 @@ int klab_engine_beam_begin(klab_engine* e, int num_beams, int max_length, float 
 int klab_engine_beam_step(klab_engine* e, int t, void* ws, void* stream);
 const int* klab_engine_beam_stop_word(klab_engine* e, void* ws, int cur_len);
 int klab_engine_beam_result(klab_engine* e, void* ws, int num_return_sequences, long long* seq, float* scores, int* len, void* stream);
+
+/* ---- sampling (HF `_sample` with temperature -> top-k -> top-p; csrc/sample.hip) ------------------------------------------
+ * klab_sample_rows: one drawn token per row r < rows from logits row (r / row_div) (element stride ld), V <= 32768
+ * (KLAB_ERR_UNSUPPORTED above).  Scores = fp32 logits / temperature; top_k = 0 or >= V: no top-k, else every score below the
+ * k-th largest is removed (ties at it stay); top_p >= 1: no top-p, else token i stays iff the softmax mass of the top-k-kept
+ * tokens with a strictly larger score is < top_p (the arg-max always stays; unlike HF's sort-and-cumsum, a tie exactly at the
+ * boundary stays whole).  Draw: the smallest kept id j whose running kept probability (ascending id) exceeds u * (kept total);
+ * u = u_in[r] when given, else a counter hash of (seed, step, r) in [0, 1).
+ * Optional outputs (NULL: not written): warped [rows, ld_warped] f32, the processed scores (-inf = removed); done [rows]: a row
+ * with done[r] != 0 draws pad_id, a row that draws eos_id gets done[r] = 1; tokens [rows]: the token; seq: seq[r*ld_seq + pos]
+ * = the token (and seq[r*ld_seq] = start_id when pos == 1); stop_word: set to 1 by every row still unfinished (the caller
+ * clears it).                                                                                                              */
+typedef struct {
+  int dtype;
+  const void* logits; long ld; int row_div;
+  int rows, V;
+  float temperature; int top_k; float top_p;
+  unsigned long long seed; int step;
+  const float* u_in;
+  float* warped; long ld_warped;
+  int* done; int eos_id, pad_id, start_id;
+  long long* tokens;
+  long long* seq; long ld_seq; int pos;
+  int* stop_word;
+} klab_sample_args;
+int klab_sample_rows(const klab_sample_args* a, void* stream);
+/* Sampling generation on an engine binding, the beam pattern at B*n rows (row b*n + j = sample j of image b, HF's
+ * `_expand_inputs_for_generation`).  The workspace (klab_engine_sample_workspace_bytes) is caller-owned and separate from the
+ * binding's: decoder scratch and logits for B*n rows, the per-layer self-attention cache [B*n*max_length, 3*inner] (row r reads
+ * its own slot), the sequences [B*n, max_length] int64, the next decoder inputs, the done flags and the stop words.
+ * sample_begin: after a klab_engine_forward in evaluation mode at B rows with Lt >= max_length - 1; copies position 0's self K/V
+ *   into every row's slot and samples position 1 from the prefill's position-0 logits (the n rows of an image share them).
+ * sample_step(t): the decoder over position t (1 <= t <= max_length - 2) for all B*n rows (cross-attention K/V shared by the n
+ *   rows of an image), then one klab_sample_rows for position t + 1.
+ * sample_stop_word: device address of the stop word of position pos (1 while some row is unfinished after sampling pos).
+ * sample_result: the first `length` columns of the sequences into seq [B*n, length] int64.                                 */
+size_t klab_engine_sample_workspace_bytes(klab_engine* e, int num_return_sequences, int max_length);
+int klab_engine_sample_begin(klab_engine* e, int num_return_sequences, int max_length, float temperature, int top_k, float top_p,
+                             unsigned long long seed, int eos_id, int pad_id, void* ws, void* stream);
+int klab_engine_sample_step(klab_engine* e, int t, void* ws, void* stream);
+const int* klab_engine_sample_stop_word(klab_engine* e, void* ws, int pos);
+int klab_engine_sample_result(klab_engine* e, void* ws, long long* seq, int length, void* stream);
 /* segment 0: LM head + decoder + tied embedding; 1: encoder; 2: Swin (no-op unless train_swin).
  * dloss_dev: device scalar d(objective)/d(loss) (NULL = 1).                                       */
 int klab_engine_backward(klab_engine* e, int segment, const float* dloss_dev, void* stream);

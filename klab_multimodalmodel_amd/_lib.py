@@ -61,6 +61,13 @@ class BeamUpdateArgs(C.Structure):  # klab_beam_update_args
                 ("slot_in", vp), ("slot_out", vp), ("prev_tokens", vp), ("parent", vp), ("stop_word", vp)]
 
 
+class SampleArgs(C.Structure):  # klab_sample_args
+    _fields_ = [("dtype", i32), ("logits", vp), ("ld", i64), ("row_div", i32), ("rows", i32), ("V", i32),
+                ("temperature", f32), ("top_k", i32), ("top_p", f32), ("seed", C.c_uint64), ("step", i32),
+                ("u_in", vp), ("warped", vp), ("ld_warped", i64), ("done", vp), ("eos_id", i32), ("pad_id", i32), ("start_id", i32),
+                ("tokens", vp), ("seq", vp), ("ld_seq", i64), ("pos", i32), ("stop_word", vp)]
+
+
 # every exported entry point of include/klab_mm.h: name -> argtypes (restype is always int)
 SIGNATURES = {
     "klab_version": [],
@@ -91,6 +98,7 @@ SIGNATURES = {
     "klab_beam_update": [C.POINTER(BeamUpdateArgs), i32, vp],
     "klab_beam_init": [C.POINTER(BeamUpdateArgs), i32, i32, vp],
     "klab_beam_copy_rows": [i32, vp, i64, i32, vp, i64, i32, i32, vp],
+    "klab_sample_rows": [C.POINTER(SampleArgs), vp],
     "klab_dbias_reduce": [vp, i32, vp, i32, i32, i32, i32, vp],
     "klab_swin_mlp_fused": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "klab_gemm_grouped": [vp, i32, vp],

@@ -133,6 +133,9 @@ struct klab_engine {
   void *dc_xn = nullptr, *dc_q = nullptr, *dc_ctx = nullptr, *dc_hmid = nullptr, *dc_out = nullptr, *dc_logits = nullptr;
   // beam search (klab_engine_beam_*): parameters of the search begun last on this binding, cur_len of its last update
   int bm_k = 0, bm_len = 0, bm_mode = 0, bm_eos = 1, bm_cur = 0; float bm_lp = 1.f;
+  // sampling (klab_engine_sample_*): parameters of the run begun last on this binding, the last position sampled
+  int sp_n = 0, sp_len = 0, sp_cur = 0, sp_topk = 0, sp_eos = 1, sp_pad = 0; float sp_temp = 1.f, sp_topp = 1.f;
+  unsigned long long sp_seed = 0;
   // lang scratch (no grad => reused across layers)
   void* kv_all = nullptr; void* dkv_all = nullptr;
   void* logits = nullptr; float *loss_row = nullptr, *inv_n = nullptr, *loss = nullptr;
@@ -2024,6 +2027,104 @@ extern "C" int klab_engine_beam_result(klab_engine* e, void* ws, int num_return_
   if (rc == hipSuccess) rc = hipMemcpy2DAsync(scores, n * 4, w.fin_score, k * 4, n * 4, B, hipMemcpyDeviceToDevice, s);
   if (rc == hipSuccess) rc = hipMemcpy2DAsync(len, n * 4, w.fin_len, k * 4, n * 4, B, hipMemcpyDeviceToDevice, s);
   return (int)rc;
+}
+
+// ---- sampling (HF `_sample`): a workspace of its own, owned by the caller ------------------------------------------------------
+namespace {
+struct SampleWs {
+  DecodeRows rows;
+  long long *seq, *prev; int *done, *stop;
+};
+size_t plan_sample(const klab_engine* e, int n, int Lm, void* base, SampleWs& w) {
+  Bump b(base);
+  const klab_t5_cfg& cfg = e->cfg.main;
+  const size_t es = e->es;
+  const long M = (long)e->B * n, d = cfg.d_model, inner = (long)cfg.n_heads * cfg.d_kv, ff = cfg.d_ff, V = cfg.vocab;
+  DecodeRows& r = w.rows;
+  r.M = (int)M;
+  r.h[0] = (float*)b.take(M * d * 4); r.h[1] = (float*)b.take(M * d * 4); r.rstd = (float*)b.take(M * 4);
+  r.xn = b.take(M * d * es); r.q = b.take(M * inner * es); r.ctx = b.take(M * inner * es); r.hmid = b.take(M * ff * es);
+  r.out = b.take(M * d * es); r.logits = b.take(M * V * es);
+  r.cache_layer = M * Lm * 3 * inner; r.cache_rows = Lm;
+  r.cache = b.take((size_t)cfg.n_dec_layers * r.cache_layer * es);
+  r.kv_group = n;  // (kv_slot NULL: row r's self-attention keys are its own slot r)
+  w.seq = (long long*)b.take(M * Lm * 8); w.prev = (long long*)b.take(M * 8);
+  w.done = (int*)b.take(M * 4); w.stop = (int*)b.take((long)Lm * 4);
+  return b.off;
+}
+bool sample_shape_ok(const klab_engine* e, int n, int Lm) {
+  return e && e->bound && n >= 1 && Lm >= 2 && Lm - 1 <= e->Lt && e->cfg.main.vocab <= 32768;
+}
+// one klab_sample_rows for position pos over the B*n rows (logits row r / row_div)
+int sample_pos(klab_engine* e, const Ctx& c, const SampleWs& w, const void* logits, long ld, int row_div, int pos) {
+  klab_sample_args a;
+  memset(&a, 0, sizeof(a));
+  a.dtype = c.dt; a.logits = logits; a.ld = ld; a.row_div = row_div;
+  a.rows = e->B * e->sp_n; a.V = e->cfg.main.vocab;
+  a.temperature = e->sp_temp; a.top_k = e->sp_topk; a.top_p = e->sp_topp;
+  a.seed = e->sp_seed; a.step = pos;
+  a.done = w.done; a.eos_id = e->sp_eos; a.pad_id = e->sp_pad; a.start_id = e->cfg.main.start_id;
+  a.tokens = w.prev; a.seq = w.seq; a.ld_seq = e->sp_len; a.pos = pos; a.stop_word = w.stop + pos;
+  return klab_sample_rows(&a, c.ws());
+}
+}  // namespace
+
+extern "C" size_t klab_engine_sample_workspace_bytes(klab_engine* e, int num_return_sequences, int max_length) {
+  if (!sample_shape_ok(e, num_return_sequences, max_length)) return 0;
+  SampleWs w;
+  return plan_sample(e, num_return_sequences, max_length, nullptr, w);
+}
+
+// Precondition: klab_engine_forward in evaluation mode on this binding (the prefill; its logits row b*Lt is position 0 of sample b)
+extern "C" int klab_engine_sample_begin(klab_engine* e, int num_return_sequences, int max_length, float temperature, int top_k,
+                                        float top_p, unsigned long long seed, int eos_id, int pad_id, void* ws, void* stream) {
+  if (!sample_shape_ok(e, num_return_sequences, max_length) || !ws || !(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f && top_p <= 1.f))
+    return KLAB_ERR_BADARG;
+  Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
+  const klab_t5_cfg& cfg = e->cfg.main;
+  const int n = num_return_sequences, Lm = max_length, B = e->B, V = cfg.vocab, inner = cfg.n_heads * cfg.d_kv;
+  e->sp_n = n; e->sp_len = Lm; e->sp_temp = temperature; e->sp_topk = top_k; e->sp_topp = top_p; e->sp_seed = seed;
+  e->sp_eos = eos_id; e->sp_pad = pad_id; e->sp_cur = 0;
+  SampleWs w;
+  plan_sample(e, n, Lm, ws, w);
+  RC((int)hipMemsetAsync(w.done, 0, (size_t)B * n * 4, c.s));
+  RC((int)hipMemsetAsync(w.stop, 0, (size_t)Lm * 4, c.s));
+  // position 0 (the start token) of every row: the prefill's self q|k|v row of its image, copied into the row's own slot
+  for (int i = 0; i < cfg.n_dec_layers; ++i)
+    RC(klab_beam_copy_rows((int)e->es, e->dec.L[i].qkv, (long)e->Lt * 3 * inner, n, eoff(c, w.rows.cache, (long)i * w.rows.cache_layer),
+                           (long)Lm * 3 * inner, B * n, 3 * inner, c.ws()));
+  // position 1 from the prefill's position-0 logits, shared by the n rows of an image
+  RC(sample_pos(e, c, w, e->logits, (long)e->Lt * V, n, 1));
+  e->sp_cur = 1;
+  return 0;
+}
+
+// the decoder over position t for every row (inputs: the tokens sampled at t), then the draw of position t + 1
+extern "C" int klab_engine_sample_step(klab_engine* e, int t, void* ws, void* stream) {
+  if (!e || !e->bound || !ws || e->sp_n < 1 || t < 1 || t != e->sp_cur || t > e->sp_len - 2 || !sample_shape_ok(e, e->sp_n, e->sp_len))
+    return KLAB_ERR_BADARG;
+  Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
+  SampleWs w;
+  plan_sample(e, e->sp_n, e->sp_len, ws, w);
+  RC(decode_rows(e, c, t, w.prev, w.rows));
+  RC(sample_pos(e, c, w, w.rows.logits, e->cfg.main.vocab, 1, t + 1));
+  e->sp_cur = t + 1;
+  return 0;
+}
+
+extern "C" const int* klab_engine_sample_stop_word(klab_engine* e, void* ws, int pos) {
+  if (!e || !ws || e->sp_n < 1 || pos < 1 || pos >= e->sp_len) return nullptr;
+  SampleWs w;
+  plan_sample(e, e->sp_n, e->sp_len, ws, w);
+  return w.stop + pos;
+}
+
+extern "C" int klab_engine_sample_result(klab_engine* e, void* ws, long long* seq, int length, void* stream) {
+  if (!e || !ws || e->sp_cur < 1 || !seq || length < 1 || length > e->sp_cur + 1) return KLAB_ERR_BADARG;
+  SampleWs w;
+  plan_sample(e, e->sp_n, e->sp_len, ws, w);
+  const size_t Lm = e->sp_len, rows = (size_t)e->B * e->sp_n;
+  return (int)hipMemcpy2DAsync(seq, (size_t)length * 8, w.seq, Lm * 8, (size_t)length * 8, rows, hipMemcpyDeviceToDevice, (hipStream_t)stream);
 }
 
 // segment 0: LM head + decoder + shared embedding; 1: encoder; 2: Swin

@@ -122,6 +122,12 @@ ENGINE_SIGS = {
     "klab_engine_beam_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_beam_stop_word": ([C.c_void_p, C.c_void_p, C.c_int], C.c_void_p),
     "klab_engine_beam_result": ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "klab_engine_sample_workspace_bytes": ([C.c_void_p, C.c_int, C.c_int], C.c_size_t),
+    "klab_engine_sample_begin": ([C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_void_p], C.c_int),
+    "klab_engine_sample_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+    "klab_engine_sample_stop_word": ([C.c_void_p, C.c_void_p, C.c_int], C.c_void_p),
+    "klab_engine_sample_result": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
     "klab_engine_backward": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_set_graph": ([C.c_void_p, C.c_int], C.c_int),
     "klab_engine_get_rng": ([C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p], C.c_int),
@@ -396,6 +402,35 @@ class Engine:
         L.check(self._lib.klab_engine_beam_result(self._h, ws.data_ptr(), n, seq.data_ptr(), scores.data_ptr(), lens.data_ptr(), L.stream_ptr()),
                 "klab_engine_beam_result")
         return seq, scores, lens
+
+    # ---- sampling (HF `_sample`); the workspace is the caller's, the binding's is untouched ----------------------------
+    def sample_workspace_bytes(self, num_return_sequences, max_length):
+        return int(self._lib.klab_engine_sample_workspace_bytes(self._h, int(num_return_sequences), int(max_length)))
+
+    def sample_begin(self, num_return_sequences, max_length, temperature, top_k, top_p, seed, eos_id, pad_id, ws):
+        """after an evaluation-mode forward (the prefill): position 1 of every row from the prefill's position-0 logits"""
+        L.check(self._lib.klab_engine_sample_begin(self._h, int(num_return_sequences), int(max_length), float(temperature), int(top_k),
+                                                   float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(eos_id), int(pad_id), ws.data_ptr(),
+                                                   L.stream_ptr()), "klab_engine_sample_begin")
+
+    def sample_step(self, t, ws):
+        """decoder over position t for all rows, then the draw of position t + 1"""
+        L.check(self._lib.klab_engine_sample_step(self._h, int(t), ws.data_ptr(), L.stream_ptr()), "klab_engine_sample_step")
+
+    def sample_stop_word(self, ws, pos):
+        """int32 view of the stop word of position pos (1 while some row is unfinished)"""
+        p = self._lib.klab_engine_sample_stop_word(self._h, ws.data_ptr(), int(pos))
+        if not p:
+            raise ValueError("klab: bad argument to klab_engine_sample_stop_word")
+        off = p - ws.data_ptr()
+        return ws[off:off + 4].view(torch.int32)
+
+    def sample_result(self, ws, rows, length):
+        """the first `length` columns of the sampled sequences, [rows, length] int64"""
+        seq = torch.empty(int(rows), int(length), dtype=torch.int64, device=ws.device)
+        L.check(self._lib.klab_engine_sample_result(self._h, ws.data_ptr(), seq.data_ptr(), int(length), L.stream_ptr()),
+                "klab_engine_sample_result")
+        return seq
 
     def backward(self, segment, dloss=None):
         L.check(self._lib.klab_engine_backward(self._h, segment, dloss.data_ptr() if dloss is not None else None, L.stream_ptr()),

@@ -367,13 +367,31 @@ class MyModel(nn.Module):
 
     @torch.no_grad()
     def generate(self, pixels, src, max_length=20, kv_cache=True, num_beams=1, length_penalty=1.0, early_stopping=False,
-                 num_return_sequences=1, return_scores=False):
+                 num_return_sequences=1, return_scores=False, do_sample=False, temperature=1.0, top_k=50, top_p=1.0):
         """greedy decoding with HF's default generation settings (ref/models/model.py:28: max_length 20, no sampling).
         Prefill = one evaluation-mode forward (Swin, both encoders, the cross K/V of all layers, decoder position 0); every
         further token runs the decoder over ONE new position against the per-layer K/V cache (`klab_engine_decode_step`,
         SURVEY §8 row f-3; HF/t5:308-332).  kv_cache=False keeps the round-1 form -- decoder + LM head over the whole prefix per
         token -- as the cross-check of the cache.
-        num_beams > 1: HF's beam search (`_beam_search`, `generate(num_beams=...)`) on the device -- see _generate_beam."""
+        num_beams > 1: HF's beam search (`_beam_search`, `generate(num_beams=...)`) on the device -- see _generate_beam.
+        do_sample=True: HF's `_sample` with temperature -> top-k -> top-p on the device -- see _generate_sample."""
+        if do_sample:
+            if num_beams > 1:
+                raise NotImplementedError("beam sampling (do_sample=True with num_beams > 1) is not supported")
+            if not kv_cache:
+                raise ValueError("sampling runs on the K/V cache only: do_sample=True needs kv_cache=True")
+            if return_scores:
+                raise ValueError("return_scores needs num_beams > 1 (sampling keeps no sequence scores)")
+            if not isinstance(temperature, (int, float)) or not temperature > 0:
+                raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float, otherwise your next token "
+                                 "scores will be invalid.")
+            if not isinstance(top_k, int) or top_k < 0:
+                raise ValueError(f"`top_k` has to be a non-negative integer (0 disables it), but is {top_k}")
+            if not isinstance(top_p, (int, float)) or top_p < 0 or top_p > 1.0:
+                raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+            if num_return_sequences < 1:
+                raise ValueError(f"`num_return_sequences` has to be a positive integer, but is {num_return_sequences}")
+            return self._generate_sample(pixels, src, max_length, num_return_sequences, float(temperature), int(top_k), float(top_p))
         if num_return_sequences > num_beams:
             raise ValueError(f"`num_return_sequences` ({num_return_sequences}) has to be smaller or equal to `num_beams` ({num_beams}).")
         if num_beams > 1:
@@ -449,6 +467,38 @@ class MyModel(nn.Module):
             self.transformer.train(was_training)
         seq = seq[:, :1 + int(lens.max())]
         return (seq, scores) if return_scores else seq
+
+    def _generate_sample(self, pixels, src, max_length, num_return_sequences, temperature, top_k, top_p):
+        """One prefill at B rows, then B*n rows (row b*n + j: sample j of image b, HF's `_expand_inputs_for_generation`) on the
+        device: every step is the decoder over B*n rows and one sampling kernel that applies HF's warpers, draws, and does
+        greedy's bookkeeping (`klab_engine_sample_step`); the host reads one stop word per step.  The draws come from a counter
+        hash of one 64-bit seed taken from torch's default CPU generator per call (torch.manual_seed reproduces a call).
+        Returns [B*n, L] int64: start token, pad after EOS, cropped when every row is done."""
+        if max_length < 2:
+            raise ValueError("max_length must count the start token and at least one generated token")
+        B = src.shape[0]
+        cfg = self.main_cfg
+        n = int(num_return_sequences)
+        seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (), dtype=torch.int64)) & 0xFFFFFFFFFFFFFFFF
+        tgt = torch.full((B, max_length - 1), cfg.pad_token_id, dtype=torch.int64, device=src.device)
+        was_training = self.transformer.training
+        self.transformer.eval()
+        try:
+            eng = self._engine_for(pixels, src, tgt)
+            eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
+            nbytes = eng.sample_workspace_bytes(n, max_length)
+            if nbytes == 0:
+                raise ValueError(f"sampling: unsupported num_return_sequences={n} / max_length={max_length} for this model")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+            eng.sample_begin(n, max_length, temperature, top_k, top_p, seed, cfg.eos_token_id, cfg.pad_token_id, ws)
+            cur = 1
+            while cur < max_length - 1 and int(eng.sample_stop_word(ws, cur).item()):  # the one host sync per step
+                eng.sample_step(cur, ws)
+                cur += 1
+            seq = eng.sample_result(ws, B * n, cur + 1)
+        finally:
+            self.transformer.train(was_training)
+        return seq
 
     def _join_pending_update(self):
         """an optimizer update still running on its own stream (optim.FusedAdam(step_in_backward=True)) writes the weights:
