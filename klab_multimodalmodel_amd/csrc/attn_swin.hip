@@ -773,12 +773,8 @@ __host__ inline SwinBwdWs swin_bwd_ws(int B, int R, int w, int H, int C) {
   o.ds = off; off += large ? 0 : al((size_t)B * nW * H * n * 64 * 2);
   o.biasw = off; off += large ? 0 : al(nW * H * n * n * 4);
   // large windows: per-workgroup partials of d(bias table), [B*nW * ceil(n/64), H, (2w-1)^2] f32
-  // (sized for both forms of the table gradient: partial tables [.., ceil(n/64), H, (2w-1)^2] f32, or dS [.., H, n, roundup32(n)] bf16)
-  {
-    const size_t part = (size_t)B * nW * ((n + 63) / 64) * H * (size_t)(2 * w - 1) * (2 * w - 1) * 4;
-    const size_t dsb = (size_t)B * nW * H * n * ((n + 31) & ~(size_t)31) * 2;
-    o.dtp = off; off += large ? al(part > dsb ? part : dsb) : 0;
-  }
+  const size_t part = (size_t)B * nW * ((n + 63) / 64) * H * (size_t)(2 * w - 1) * (2 * w - 1) * 4;
+  o.dtp = off; off += large ? al(part) : 0;
   o.total = off;
   return o;
 }
@@ -1035,8 +1031,7 @@ extern "C" int klab_swin_attn_fwd(const klab_swin_attn_args* a, void* stream) {
 static bool swin_bwd_mfma_ok(int dtype, int w, int H, int C) { return dtype == KLAB_BF16 && C == H * 32 && w * w <= 64 && H <= 64; }
 // windows of more than 64 tokens on the matrix cores: streaming kernels over window-major copies (bf16, head dim 32, bias table)
 static bool swin_flash_ok(int dtype, int w, int H, int C) {
-  static const bool on = [] { const char* e = getenv("KLAB_SWIN_FLASH"); return !e || atoi(e) != 0; }();
-  return on && dtype == KLAB_BF16 && C == H * 32 && H <= 64 && (C & 7) == 0 && w > 0;
+  return dtype == KLAB_BF16 && C == H * 32 && H <= 64 && (C & 7) == 0 && w > 0;
 }
 
 extern "C" size_t klab_swin_attn_bwd_ws_bytes(int dtype, int B, int R, int w, int H, int C) {

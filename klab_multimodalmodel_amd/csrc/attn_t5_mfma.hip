@@ -227,7 +227,6 @@ struct AttnFusedP {
   bf16_t* xn; float* rstd;     // [B * Lq, 512], [B * Lq]
   bf16_t* proj; long ldproj;   // SELF: [B * Lq, 3 * inner]; CROSS: [B * Lq, inner]
   AttnMP a;
-  int ablate;  // diagnostics (KLAB_AF_ABLATE): 1 = no attention core, 2 = no projection MFMAs / weight stream, 4 = no q|k|v copy-out
 };
 constexpr int AF_D = 512, AF_DK = 64, AF_S = 3;
 template <bool CROSS>
@@ -271,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void t5_attn_fused_fwd(AttnFusedP f) {
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc[i] + kt * 64),
                                        (__attribute__((address_space(3))) void*)(st + (wave * LPW + i) * 1024), 16, 0, 0);
   };
-  if (!(f.ablate & 2)) { issue(0); issue(1); }
+  issue(0); issue(1);
   // 1. T5LayerNorm into MFMA fragments.  A wave reads its 16 rows as whole rows -- two fully coalesced 1-KiB loads per row, lane l
   //    holding columns 4 l .. + 3 and 256 + 4 l .. + 3 (loading each lane's fragment columns directly made every load touch
   //    half-lines of 16 rows: +5 us per launch) --, reduces the sum of squares per row across the wave, and passes the normalised
@@ -337,7 +336,6 @@ __global__ __launch_bounds__(256, 2) void t5_attn_fused_fwd(AttnFusedP f) {
   f32x4 acc[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (!(f.ablate & 2))
 #pragma unroll
   for (int kt = 0; kt < D / 64; ++kt) {
     if (kt + 1 < D / 64) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPW) : "memory");
@@ -384,24 +382,22 @@ __global__ __launch_bounds__(256, 2) void t5_attn_fused_fwd(AttnFusedP f) {
     stage<DK, DK, false, true>(p.v, p.ldv, b, h, Lk, Lkp, nullptr, 0, Vt);
   }
   __syncthreads();
-  if (!(f.ablate & 4)) {
-    constexpr int NB = CROSS ? 1 : 3;
+  constexpr int NB = CROSS ? 1 : 3;
 #pragma unroll
-    for (int blk = 0; blk < NB; ++blk) {
-      const char* img = blk == 0 ? Qr : (blk == 1 ? Kr : Vr);
+  for (int blk = 0; blk < NB; ++blk) {
+    const char* img = blk == 0 ? Qr : (blk == 1 ? Kr : Vr);
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int ch = tid + u * 256, row = ch >> 3, cc = ch & 7;
-        if (row < Lq)
-          *reinterpret_cast<bf16x8*>(f.proj + ((long)b * Lq + row) * f.ldproj + (long)blk * inner + h * DK + cc * 8) =
-              *reinterpret_cast<const bf16x8*>(img + row * KPITCH + cc * 16);
-      }
+    for (int u = 0; u < 2; ++u) {
+      const int ch = tid + u * 256, row = ch >> 3, cc = ch & 7;
+      if (row < Lq)
+        *reinterpret_cast<bf16x8*>(f.proj + ((long)b * Lq + row) * f.ldproj + (long)blk * inner + h * DK + cc * 8) =
+            *reinterpret_cast<const bf16x8*>(img + row * KPITCH + cc * 16);
     }
   }
 
   // 4. attention of the wave's 16 queries
   const int q0 = wave * 16;
-  if (q0 >= Lq || (f.ablate & 1)) return;
+  if (q0 >= Lq) return;
   bf16x8 qf[2];
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) qf[ks] = row_frag(Qr, KPITCH, q0, ks, lane);
@@ -747,14 +743,12 @@ __device__ __forceinline__ void stage_blk(const bf16_t* __restrict__ g, long ld,
 }
 
 template <int DK, int BIAS>
-__global__ __launch_bounds__(256) void flash_fwd_kernel(FlashP p) {
+__global__ __launch_bounds__(256) void flash_fwd_kernel(FlashP p) {  // BIAS 0 / 1 (the Swin table form is flash_fwd_swin_kernel)
+  static_assert(BIAS == 0 || BIAS == 1, "dense or no bias");
   constexpr int KS = (DK + 31) / 32, DKP = KS * 32, DT = DK / 16, KPITCH = DKP * 2 + 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Kr = smem;
   char* Vt = Kr + FKB * KPITCH;
-  int* kcode = reinterpret_cast<int*>(Vt + TrImg<DKP>::bytes(FKB));
-  int* kreg = kcode + FKB;
-  float* tab = reinterpret_cast<float*>(kreg + FKB);
   const int Lq = p.Lq, Lk = p.Lk;
   const int bt = blockIdx.y / p.H, h = blockIdx.y % p.H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
@@ -763,15 +757,6 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(FlashP p) {
   const bool active = q0 < Lq;
   const int q = q0 + (lane & 15);
   const int qc = q < Lq ? q : Lq - 1;
-  const int win = BIAS == 2 ? bt % p.nW : 0;
-  int qreg = 0, coff = 0;
-  if constexpr (BIAS == 2) {
-    const int ntab = (2 * p.w - 1) * (2 * p.w - 1);
-    for (int t = threadIdx.x; t < ntab; t += 256) tab[t] = p.btab[(long)t * p.H + h];
-    int qcode;
-    flash_tok(p, win, qc, qcode, qreg);
-    coff = qcode + 2 * p.w * (p.w - 1);
-  }
   bf16x8 qf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
@@ -793,14 +778,6 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(FlashP p) {
     __syncthreads();
     stage_blk<DK, DKP, true, false>(p.k, p.ldk, krow0, h, k0, Lk, Kr, KPITCH, nullptr);
     stage_blk<DK, DKP, false, true>(p.v, p.ldv, krow0, h, k0, Lk, nullptr, 0, Vt);
-    if constexpr (BIAS == 2) {
-      if (threadIdx.x < FKB) {
-        const int kk = k0 + threadIdx.x;
-        int c = 0, r = -1;
-        if (kk < Lk) flash_tok(p, win, kk, c, r);
-        kcode[threadIdx.x] = c; kreg[threadIdx.x] = r;
-      }
-    }
     __syncthreads();
     if (!active) continue;
     f32x4 s[4];
@@ -813,12 +790,10 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(FlashP p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int kl = t * 16 + g * 4 + r, key = k0 + kl;
-        // branch-free: every LDS read below is in range for any kl (kcode / kreg are filled for all 64 slots, code 0 for keys past
-        // the end), the result of an out-of-range key is discarded by the select.  (Sixteen per-element branches split this loop
-        // into a hundred basic blocks.)
+        // branch-free: the result of an out-of-range key is discarded by the select.  (Sixteen per-element branches split this
+        // loop into a hundred basic blocks.)
         float x = s[t][r] * sscale;
         if constexpr (BIAS == 1) x += brow[key < Lk ? key : Lk - 1];
-        if constexpr (BIAS == 2) x += tab[coff - kcode[kl]] + (kreg[kl] != qreg ? -200.f : 0.f);
         x = key < Lk ? x : -INFINITY;
         s[t][r] = x;
         mb = fmaxf(mb, x);
@@ -836,8 +811,7 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(FlashP p) {
       for (int r = 0; r < 4; ++r) {
         const float e = __expf(s[t][r] - mn);
         sum += e;
-        if constexpr (BIAS == 2) s[t][r] = e;  // (window attention has no probability dropout: HF/swinv2 attention_probs_dropout_prob = 0)
-        else s[t][r] = e * drop_mult32(dc, dbase + t * 16 + g * 4 + r);
+        s[t][r] = e * drop_mult32(dc, dbase + t * 16 + g * 4 + r);
       }
     l = l * corr + sum;
     m = mn;
@@ -856,13 +830,11 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(FlashP p) {
   const float inv = 1.f / l;
   if (q < Lq) {
     if (g == 0 && p.lse) p.lse[((long)bt * p.H + h) * Lq + q] = m + __logf(l);
-    const long trow = (BIAS == 2 && p.otok) ? flash_token_row(p, bt, q) : 0;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       const int d = dt * 16 + g * 4;
       const bf16x4 ov = bf16x4{(bf16_t)(o[dt][0] * inv), (bf16_t)(o[dt][1] * inv), (bf16_t)(o[dt][2] * inv), (bf16_t)(o[dt][3] * inv)};
       if (p.o) *reinterpret_cast<bf16x4*>(p.o + (qrow0 + q) * p.ldo + (long)h * DK + d) = ov;
-      if (BIAS == 2 && p.otok && trow >= 0) *reinterpret_cast<bf16x4*>(p.otok + trow * p.ldot + (long)h * DK + d) = ov;
     }
   }
 }
@@ -1084,12 +1056,11 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(FlashP p) {
   delta += __shfl_xor(delta, 32, 64);
   const float lq = p.lse[((long)bt * p.H + h) * Lq + qc];
   const float sscale = p.score_scale ? p.score_scale[h] : 1.f;
-  const bool want_dtab = (p.dbtab_part != nullptr || p.dbtab != nullptr) && p.ds_ws == nullptr;
+  const bool want_dtab = p.dbtab_part != nullptr || p.dbtab != nullptr;
   const float* brow = nullptr;
   if constexpr (BIAS == 1) brow = p.bias + (p.bias_mod > 0 ? (long)(bt % p.bias_mod) * p.H * Lq * Lk : 0L) + ((long)h * Lq + qc) * Lk;
-  // dS rows for a second-pass reduction: T5 position-bias gradient (BIAS 1) and, for Swin (BIAS 2), the table gradient -- summing
-  // dS per table entry with LDS float atomics cost 0.81 of 1.39 ms per stage-0 block (profiles/r02_swin_large_window_kernels_B8.txt)
-  bf16_t* dsrow = (BIAS != 0 && p.ds_ws && q < Lq) ? p.ds_ws + (((long)bt * p.H + h) * Lq + q) * Lkp : nullptr;
+  // dS rows for a second-pass reduction: T5 position-bias gradient (BIAS 1)
+  bf16_t* dsrow = (BIAS == 1 && p.ds_ws && q < Lq) ? p.ds_ws + (((long)bt * p.H + h) * Lq + q) * Lkp : nullptr;
   const DropCtx dc = drop_slab(make_drop(p.seed, p.tag, p.p), (uint32_t)(bt * p.H + h));
   f32x4 acc[DT];
 #pragma unroll
@@ -1156,9 +1127,7 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(FlashP p) {
     }
   }
   if constexpr (BIAS == 2) {
-    if (p.ds_ws) {
-      // the table gradient comes from the stored dS rows (swin_dtab_from_ds_kernel)
-    } else if (p.dbtab_part) {
+    if (p.dbtab_part) {
       __syncthreads();
       float* dst = p.dbtab_part + (((long)bt * gridDim.x + blockIdx.x) * p.H + h) * ntab;
       for (int t = threadIdx.x; t < ntab; t += 256) dst[t] = dtab[t] + dtab[ntab + t] + dtab[2 * ntab + t] + dtab[3 * ntab + t];
@@ -1335,7 +1304,8 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_dq_swin_kernel(FlashP p, int
 }
 
 template <int DK, int BIAS>
-__global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(FlashP p) {
+__global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(FlashP p) {  // BIAS 0 / 1 (the Swin table form is flash_bwd_dkv_swin_kernel)
+  static_assert(BIAS == 0 || BIAS == 1, "dense or no bias");
   constexpr int KS = (DK + 31) / 32, DKP = KS * 32, DT = DK / 16, KPITCH = DKP * 2 + 16, CPR = DKP / 8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Qr = smem;
@@ -1344,9 +1314,6 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(FlashP p) {
   char* dOt = Qt + TrImg<DKP>::bytes(FKB);
   float* delta = reinterpret_cast<float*>(dOt + TrImg<DKP>::bytes(FKB));
   float* lses = delta + FKB;
-  int* qcode = reinterpret_cast<int*>(lses + FKB);
-  int* qreg = qcode + FKB;
-  float* tab = reinterpret_cast<float*>(qreg + FKB);
   const int Lq = p.Lq, Lk = p.Lk;
   const int bt = blockIdx.y / p.H, h = blockIdx.y % p.H;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
@@ -1355,15 +1322,6 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(FlashP p) {
   const bool active = kt0 < Lk;
   const int key = kt0 + (lane & 15);
   const int kc = key < Lk ? key : Lk - 1;
-  const int win = BIAS == 2 ? bt % p.nW : 0;
-  int kreg_ = 0, koff = 0;
-  if constexpr (BIAS == 2) {
-    const int ntab = (2 * p.w - 1) * (2 * p.w - 1);
-    for (int t = threadIdx.x; t < ntab; t += 256) tab[t] = p.btab[(long)t * p.H + h];
-    int kcode_;
-    flash_tok(p, win, kc, kcode_, kreg_);
-    koff = 2 * p.w * (p.w - 1) - kcode_;
-  }
   bf16x8 kf[KS], vf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
@@ -1407,11 +1365,6 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(FlashP p) {
       if (c == 0) {
         delta[r] = a;
         lses[r] = i0 + r < Lq ? p.lse[((long)bt * p.H + h) * Lq + i0 + r] : INFINITY;  // padded queries: P = exp(-inf) = 0
-        if constexpr (BIAS == 2) {
-          int cc = 0, rr = -1;
-          if (i0 + r < Lq) flash_tok(p, win, i0 + r, cc, rr);
-          qcode[r] = cc; qreg[r] = rr;
-        }
       }
     }
     __syncthreads();
@@ -1432,12 +1385,7 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(FlashP p) {
         for (int r = 0; r < 4; ++r) {
           const int ql = qt * 16 + g * 4 + r, qq = i0 + ql;
           float pdv = 0.f, dsv = 0.f;
-          if constexpr (BIAS == 2) {  // branch-free (no dropout in window attention); padded queries carry lse = +inf => P = 0
-            const float x = st[r] * sscale + tab[qcode[ql] + koff] + (qreg[ql] != kreg_ ? -200.f : 0.f);
-            const float pr = (key < Lk && qq < Lq) ? __expf(x - lses[ql]) : 0.f;
-            pdv = pr;
-            dsv = pr * (dpt[r] - delta[ql]);
-          } else if (key < Lk && qq < Lq) {
+          if (key < Lk && qq < Lq) {
             float x = st[r] * sscale;
             if constexpr (BIAS == 1) x += biasp[(long)qq * Lk + key];
             const float pr = __expf(x - lses[ql]);
@@ -1623,20 +1571,15 @@ static int flash_launch(const FlashP& p, int which, hipStream_t s) {
   const size_t ntab = BIAS == 2 ? (size_t)(2 * p.w - 1) * (2 * p.w - 1) : 0;
   const size_t tr = TrImg<DKP>::bytes(FKB);
   int rc;
-  // KLAB_SWIN_FLASH_V2=0: round 2's Swin kernels (the generic streaming forms with the table look-up added)
-  static const bool v2 = [] { const char* e = getenv("KLAB_SWIN_FLASH_V2"); return !e || atoi(e) != 0; }();
   if (which == 0) {
     const size_t lds = (size_t)FKB * KPITCH + tr + 2 * FKB * 4 + ntab * 4;
     if constexpr (BIAS == 2) {
-      if (v2) {
-        rc = ensure_dyn_lds(reinterpret_cast<const void*>(flash_fwd_swin_kernel<DK>), lds); if (rc) return rc;
-        hipLaunchKernelGGL((flash_fwd_swin_kernel<DK>), dim3((p.Lq + 63) / 64, p.Bt * p.H), dim3(256), lds, s, p);
-        KLAB_LAUNCH_CHECK();
-        return KLAB_OK;
-      }
+      rc = ensure_dyn_lds(reinterpret_cast<const void*>(flash_fwd_swin_kernel<DK>), lds); if (rc) return rc;
+      hipLaunchKernelGGL((flash_fwd_swin_kernel<DK>), dim3((p.Lq + 63) / 64, p.Bt * p.H), dim3(256), lds, s, p);
+    } else {
+      rc = ensure_dyn_lds(reinterpret_cast<const void*>(flash_fwd_kernel<DK, BIAS>), lds); if (rc) return rc;
+      hipLaunchKernelGGL((flash_fwd_kernel<DK, BIAS>), dim3((p.Lq + 63) / 64, p.Bt * p.H), dim3(256), lds, s, p);
     }
-    rc = ensure_dyn_lds(reinterpret_cast<const void*>(flash_fwd_kernel<DK, BIAS>), lds); if (rc) return rc;
-    hipLaunchKernelGGL((flash_fwd_kernel<DK, BIAS>), dim3((p.Lq + 63) / 64, p.Bt * p.H), dim3(256), lds, s, p);
   } else if (which == 1) {
     const size_t lds = 2 * (size_t)FKB * KPITCH + tr + 2 * FKB * 4 + 5 * ntab * 4;
     rc = ensure_dyn_lds(reinterpret_cast<const void*>(flash_bwd_dq_kernel<DK, BIAS>), lds); if (rc) return rc;
@@ -1644,15 +1587,12 @@ static int flash_launch(const FlashP& p, int which, hipStream_t s) {
   } else {
     const size_t lds = 2 * (size_t)FKB * KPITCH + 2 * tr + 4 * FKB * 4 + ntab * 4;
     if constexpr (BIAS == 2) {
-      if (v2) {
-        rc = ensure_dyn_lds(reinterpret_cast<const void*>(flash_bwd_dkv_swin_kernel<DK>), lds); if (rc) return rc;
-        hipLaunchKernelGGL((flash_bwd_dkv_swin_kernel<DK>), dim3((p.Lk + 63) / 64, p.Bt * p.H), dim3(256), lds, s, p);
-        KLAB_LAUNCH_CHECK();
-        return KLAB_OK;
-      }
+      rc = ensure_dyn_lds(reinterpret_cast<const void*>(flash_bwd_dkv_swin_kernel<DK>), lds); if (rc) return rc;
+      hipLaunchKernelGGL((flash_bwd_dkv_swin_kernel<DK>), dim3((p.Lk + 63) / 64, p.Bt * p.H), dim3(256), lds, s, p);
+    } else {
+      rc = ensure_dyn_lds(reinterpret_cast<const void*>(flash_bwd_dkv_kernel<DK, BIAS>), lds); if (rc) return rc;
+      hipLaunchKernelGGL((flash_bwd_dkv_kernel<DK, BIAS>), dim3((p.Lk + 63) / 64, p.Bt * p.H), dim3(256), lds, s, p);
     }
-    rc = ensure_dyn_lds(reinterpret_cast<const void*>(flash_bwd_dkv_kernel<DK, BIAS>), lds); if (rc) return rc;
-    hipLaunchKernelGGL((flash_bwd_dkv_kernel<DK, BIAS>), dim3((p.Lk + 63) / 64, p.Bt * p.H), dim3(256), lds, s, p);
   }
   KLAB_LAUNCH_CHECK();
   return KLAB_OK;
@@ -1745,8 +1685,7 @@ static FlashP to_flash(const AttnMP& p) {
 }
 // sequences too long for the one-workgroup kernels (T5-large encoder, Le = 153 at head dim 64): the streaming forms
 static int t5_flash_fallback(const AttnMP& p, int dk, bool backward, hipStream_t s) {
-  static const bool on = [] { const char* e = getenv("KLAB_ATTN_FLASH"); return !e || atoi(e) != 0; }();
-  if (!on || p.causal || (dk != 32 && dk != 64)) return KLAB_ERR_UNSUPPORTED;
+  if (p.causal || (dk != 32 && dk != 64)) return KLAB_ERR_UNSUPPORTED;
   if (backward && p.dbias && !p.ds_ws) return KLAB_ERR_UNSUPPORTED;  // d bias only through the dS scratch
   const FlashP f = to_flash(p);
   const int bf = p.bias ? 1 : 0;
@@ -1775,8 +1714,6 @@ int t5_attn_fused_fwd_dispatch(const klab_attn_fused_args* fa, hipStream_t s) {
   f.x = fa->x; f.gamma = fa->gamma; f.eps = fa->eps; f.w = (const bf16_t*)fa->w; f.xn = (bf16_t*)fa->xn; f.rstd = fa->rstd;
   f.proj = (bf16_t*)fa->proj; f.ldproj = fa->ldproj;
   f.a = to_mp(a);
-  static const int abl = [] { const char* e = getenv("KLAB_AF_ABLATE"); return e ? atoi(e) : 0; }();
-  f.ablate = abl;
   const size_t images = 3 * (size_t)64 * (AF_DK * 2 + 16) + TrImg<AF_DK>::bytes(64);
   const size_t ring = (size_t)AF_S * (fa->cross ? 64 : 192) * 128;
   const size_t strips = fa->cross ? ring + 16384 : 0;  // (cross: the norm prologue's strips sit behind the small ring)
@@ -1814,31 +1751,6 @@ int t5_attn_bwd_mfma_dispatch(const klab_attn_args* a, hipStream_t s) {
 static int t5_flash_fallback_fwd(const AttnMP& p, int dk, hipStream_t s) { return t5_flash_fallback(p, dk, false, s); }
 
 // Swin-V2 large windows on window-major copies (attn_swin.hip): see FlashP
-// d(table)[c, h] += sum over sequences bt and query tokens i of dS[bt, h, i, j(i, c)]: table entry c = (dy, dx) pairs query
-// (iy, ix) with key (iy - dy, ix - dx) (HF/swinv2:480-490).  One thread per table entry, consecutive entries = consecutive dx =
-// consecutive keys of one dS row (coalesced 2-byte reads); blockIdx.z splits the sequences.
-__global__ __launch_bounds__(256) void swin_dtab_from_ds_kernel(const bf16_t* __restrict__ ds, float* __restrict__ dbtab, int Bt, int H, int w,
-                                                                int Lkp) {
-  const int tw = 2 * w - 1, ntab = tw * tw, n = w * w;
-  const int c = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y;
-  if (c >= ntab) return;
-  const int dy = c / tw - (w - 1), dx = c % tw - (w - 1);
-  const int iy0 = dy > 0 ? dy : 0, iy1 = dy < 0 ? w + dy : w;  // query rows whose partner row iy - dy lies inside the window
-  const int ix0 = dx > 0 ? dx : 0, ix1 = dx < 0 ? w + dx : w;
-  const int per = (Bt + gridDim.z - 1) / gridDim.z;
-  const int b0 = blockIdx.z * per, b1 = b0 + per < Bt ? b0 + per : Bt;
-  float a = 0.f;
-  for (int bt = b0; bt < b1; ++bt) {
-    const bf16_t* base = ds + ((long)bt * H + h) * n * Lkp;
-    for (int iy = iy0; iy < iy1; ++iy) {
-      const bf16_t* row = base + (long)(iy * w) * Lkp + (iy - dy) * w - dx;  // + ix * Lkp + ix
-#pragma unroll 4
-      for (int ix = ix0; ix < ix1; ++ix) a += (float)row[(long)ix * Lkp + ix];
-    }
-  }
-  if (a != 0.f) atomicAdd(dbtab + (long)c * H + h, a);
-}
-
 int swin_flash_dispatch(const void* g, long ldg, int C, void* otok, long ldot, float* lse, int Bt, int H, int n, const float* scale,
                         const float* btab, float* dbtab, float* dbtab_part, int w, int Rp, int Rreal, int shift, int nW, const void* ow,
                         const void* dow, void* dg, int which, hipStream_t s) {
@@ -1851,30 +1763,25 @@ int swin_flash_dispatch(const void* g, long ldg, int C, void* otok, long ldot, f
   f.dout = (const bf16_t*)dow; f.lddo = C;
   bf16_t* dgb = (bf16_t*)dg;
   f.dq = dgb; f.dkk = dgb ? dgb + C : nullptr; f.dv = dgb ? dgb + 2 * C : nullptr; f.lddq = f.lddk = f.lddv = ldg;
-  // d(table): `dbtab_part` is either the per-workgroup partial-table scratch (LDS-atomics form) or, with ds_mode, the dS
-  // scratch [Bt, H, n, roundup32(n)] bf16 of the store-and-reduce form
-  // measured (configs[4] stages at B = 8, tools/swin_attn_bench.py): store-and-reduce 1296 / 791 / 644 / 168 us per block backward
-  // against 1389 / 720 / 413 / 80 us for the LDS-atomics form (0.57 / 0.33 / 0.20 / 0.05 ms without any table gradient): the
-  // one-thread-per-entry reduction of 2-byte dS elements costs what the atomics cost.  Default: atomics; KLAB_SWIN_DTAB_DS=1 selects
-  // the other form.
-  static const bool ds_mode = [] { const char* e = getenv("KLAB_SWIN_DTAB_DS"); return e && atoi(e) != 0; }();
+  // d(table): `dbtab_part` is the per-workgroup partial-table scratch.  Measured against storing dS and reducing it per table entry
+  // (configs[4] stages at B = 8, tools/swin_attn_bench.py): 1389 / 720 / 413 / 80 us per block backward against 1296 / 791 / 644 /
+  // 168 us (0.57 / 0.33 / 0.20 / 0.05 ms without any table gradient): the one-thread-per-entry reduction of 2-byte dS elements
+  // costs what the atomics cost.
   const int ntab = (2 * w - 1) * (2 * w - 1);
   const bool want = which == 1 && dbtab && dbtab_part;
-  if (want && ds_mode) f.ds_ws = (bf16_t*)dbtab_part;
-  else f.dbtab_part = want ? dbtab_part : nullptr;
-  static const bool seq_acc = [] { const char* e = getenv("KLAB_SWIN_DTAB_SEQACC"); return !e || atoi(e) != 0; }();
+  f.dbtab_part = want ? dbtab_part : nullptr;
   const int nkb = (n + FKB - 1) / FKB;
-  if (want && !ds_mode && seq_acc && (nkb == 1 || nkb == 2 || nkb == 3 || nkb == 9)) {
+  if (want && (nkb == 1 || nkb == 2 || nkb == 3 || nkb == 9)) {
     // table gradient accumulated over sequences in registers: `chunk` sequences per workgroup, about 512 workgroups or more
     const int nqb = (n + 63) / 64;
     // chunk: the scatter costs about 1.5 sequences' worth of streaming (1390 vs 570 us per stage-0 block when done per sequence);
     // pick the chunk that minimises rounds-of-resident-workgroups x (chunk + 1.5), two workgroups resident per CU
-    static const int slots = [] { const char* e = getenv("KLAB_SWIN_DTAB_WGS"); return e && atoi(e) > 0 ? atoi(e) : 512; }();
+    constexpr int SLOTS = 512;
     int chunk = 1;
     double best = 1e30;
     for (int c = 1; c <= 16 && c <= Bt; ++c) {
       const long nwg = (long)nqb * H * ((Bt + c - 1) / c);
-      const double cost = (double)((nwg + slots - 1) / slots) * (c + 1.5);
+      const double cost = (double)((nwg + SLOTS - 1) / SLOTS) * (c + 1.5);
       if (cost < best - 1e-9) { best = cost; chunk = c; }
     }
     const int nchunks = (Bt + chunk - 1) / chunk;
@@ -1900,15 +1807,8 @@ int swin_flash_dispatch(const void* g, long ldg, int C, void* otok, long ldot, f
   }
   const int rc = flash_attn_dispatch(f, 32, 2, which, s);
   if (rc || !want) return rc;
-  if (ds_mode) {
-    int gz = Bt / 8;
-    gz = gz < 1 ? 1 : (gz > 64 ? 64 : gz);
-    hipLaunchKernelGGL(swin_dtab_from_ds_kernel, dim3((unsigned)((ntab + 255) / 256), (unsigned)H, (unsigned)gz), dim3(256), 0, s,
-                       (const bf16_t*)dbtab_part, dbtab, Bt, H, w, (n + 31) & ~31);
-  } else {
-    hipLaunchKernelGGL(dbtab_reduce_kernel, dim3((unsigned)(((long)H * ntab + 255) / 256)), dim3(256), 0, s, f.dbtab_part,
-                       (long)Bt * ((n + 63) / 64), H, ntab, dbtab);
-  }
+  hipLaunchKernelGGL(dbtab_reduce_kernel, dim3((unsigned)(((long)H * ntab + 255) / 256)), dim3(256), 0, s, f.dbtab_part,
+                     (long)Bt * ((n + 63) / 64), H, ntab, dbtab);
   KLAB_LAUNCH_CHECK();
   return KLAB_OK;
 }

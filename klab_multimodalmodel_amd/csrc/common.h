@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define KLAB_OK 0
 #define KLAB_ERR_UNSUPPORTED (-2)
@@ -23,6 +24,16 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
   } while (0)
 
 namespace klab {
+
+// On/off switch from the environment: unset or non-zero = on, "0" = off.  Callers cache the result in a function-local static,
+// so each is read once per process.  Exactly nine exist -- KLAB_ZERO_ON_SIDE, KLAB_EARLY_SMALL, KLAB_LMHEAD_AREG,
+// KLAB_T5_ATTN_FUSED, KLAB_T5_ATTN_BWD_FUSED, KLAB_SWIN_FUSED_EMBED, KLAB_SWIN_FUSED_LIN_LN, KLAB_WGRAD_GROUP_TILES,
+// KLAB_GEMM_P8 -- because tests/test_switches_gpu.py and tests/test_attn_bwd_fused_switch_gpu.py run the bench with each one
+// off and assert the loss the default forms give.
+inline bool env_on(const char* name) {
+  const char* v = getenv(name);
+  return !v || atoi(v) != 0;
+}
 
 // raise a kernel's dynamic-LDS limit once per (kernel, size): hipFuncSetAttribute is not a stream operation and must
 // not be issued while the stream is being captured into a hipGraph (misc.hip)

@@ -612,17 +612,14 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
   {  // scratch of the matrix-core window attention: backward of the one-tile windows (train_swin), and forward + backward of
      // windows of more than 64 tokens (window-major copies for the streaming kernels)
     e->sattn_ws = nullptr; e->sattn_ws_bytes = 0;
-    const char* ev = getenv("KLAB_SWIN_BWD_MFMA");  // "0": keep the vector-ALU window-attention kernels (A/B switch)
-    if (!(ev && ev[0] == '0')) {
-      size_t need = 0;
-      for (int st = 0; st < s.n_stages; ++st) {
-        const int R = R0 >> st; const int w = R < s.window ? R : s.window;
-        if (!c.train_swin && w * w <= 64 && R % w == 0) continue;  // frozen tower, one-tile unpadded window: the forward kernels need no scratch
-        const size_t x = klab_swin_attn_bwd_ws_bytes(c.dtype, B, R, w, s.heads[st], s.embed_dim << st);
-        if (x > need) need = x;  // (0: that stage is outside the matrix-core envelope and runs its own kernels)
-      }
-      if (need) { e->sattn_ws = b.take(need); e->sattn_ws_bytes = need; }
+    size_t need = 0;
+    for (int st = 0; st < s.n_stages; ++st) {
+      const int R = R0 >> st; const int w = R < s.window ? R : s.window;
+      if (!c.train_swin && w * w <= 64 && R % w == 0) continue;  // frozen tower, one-tile unpadded window: the forward kernels need no scratch
+      const size_t x = klab_swin_attn_bwd_ws_bytes(c.dtype, B, R, w, s.heads[st], s.embed_dim << st);
+      if (x > need) need = x;  // (0: that stage is outside the matrix-core envelope and runs its own kernels)
     }
+    if (need) { e->sattn_ws = b.take(need); e->sattn_ws_bytes = need; }
   }
   return (b.off + 255) & ~(size_t)255;
 }
@@ -672,8 +669,7 @@ int fwd_gemm(const Ctx& c, klab_gemm_args& g, long woffv) {
 // T5 RMS-norm in front of a Linear: in fp8 mode the kernel also leaves the rows in e4m3 in the stream's staging buffer
 int rms_fwd_for_linear(const Ctx& c, const float* x, const float* w, void* y, float* rstd, int M, int d, float eps) {
   klab_engine* e = c.e;
-  static const bool fuse = [] { const char* v = getenv("KLAB_FP8_NORM_QUANT"); return !v || atoi(v) != 0; }();
-  if (e->fp8 && fuse && c.dt == KLAB_BF16 && d <= 1024 && fp8_weight_ok(d)) {
+  if (e->fp8 && c.dt == KLAB_BF16 && d <= 1024 && fp8_weight_ok(d)) {
     const bool side = c.s == e->side;
     const long cap = side ? e->x8s_bytes : e->x8_bytes, rows = side ? e->xscales_rows : e->xscale_rows;
     if ((long)M * d <= cap && M <= rows) {
@@ -688,9 +684,8 @@ int rms_fwd_for_linear(const Ctx& c, const float* x, const float* w, void* y, fl
 // Swin LayerNorm (+ shortcut) / GELU in front of a Linear: the fp8-mode forms that leave the rows in e4m3 as well
 static bool q8_room(const Ctx& c, long M, long K, bool& side) {
   klab_engine* e = c.e;
-  static const bool fuse = [] { const char* v = getenv("KLAB_FP8_NORM_QUANT"); return !v || atoi(v) != 0; }();
   side = c.s == e->side;
-  if (!e->fp8 || !fuse || c.dt != KLAB_BF16 || !fp8_weight_ok(K)) return false;
+  if (!e->fp8 || c.dt != KLAB_BF16 || !fp8_weight_ok(K)) return false;
   return M * K <= (side ? e->x8s_bytes : e->x8_bytes) && M <= (side ? e->xscales_rows : e->xscale_rows);
 }
 int ln_fwd_for_linear(const Ctx& c, const void* y, const float* g, const float* b, const float* shortcut, float* out, void* outt, float* mean,
@@ -741,15 +736,14 @@ int t5_sublayer_out(const Ctx& c, const void* x, int M, int K, long woffv, int d
   return fwd_gemm(c, g, woffv);
 }
 
-// A/B switch of the fused attention front half (klab_t5_attn_fused_fwd): KLAB_T5_ATTN_FUSED=0 keeps the three launches
+// the fused attention front half (klab_t5_attn_fused_fwd); off: the three launches
 static bool attn_fused_on() {
-  static const bool on = [] { const char* v = getenv("KLAB_T5_ATTN_FUSED"); return !v || atoi(v) != 0; }();
+  static const bool on = klab::env_on("KLAB_T5_ATTN_FUSED");
   return on;
 }
-// A/B switch of the fused attention back half (klab_t5_attn_bwd_fused): KLAB_T5_ATTN_BWD_FUSED=0 keeps the o / co dgrad GEMM +
-// klab_t5_attn_bwd
+// the fused attention back half (klab_t5_attn_bwd_fused); off: the o / co dgrad GEMM + klab_t5_attn_bwd
 static bool attn_bwd_fused_on() {
-  static const bool on = [] { const char* v = getenv("KLAB_T5_ATTN_BWD_FUSED"); return !v || atoi(v) != 0; }();
+  static const bool on = klab::env_on("KLAB_T5_ATTN_BWD_FUSED");
   return on;
 }
 
@@ -872,12 +866,8 @@ struct WgradQueue {
     if (launched) *launched = true;
     const bool large = layers >= 2;  // a list that spans layers goes to the 256 x 256 grouped kernel
     layers = 0;
-    // timing diagnostics only (results are wrong / unoverlapped): KLAB_DIAG_WGRAD=skip drops the layer's weight gradients,
-    // =main runs them on the main stream behind the layer's chain instead of beside it
-    static const int diag = [] { const char* v = getenv("KLAB_DIAG_WGRAD"); return !v ? 0 : (v[0] == 's' ? 1 : (v[0] == 'm' ? 2 : 0)); }();
-    if (diag == 1) { q.clear(); return 0; }
-    if (diag != 2) RC(side_after_main(c));
-    Ctx cs{c.e, diag == 2 ? c.s : c.e->side, c.dt, c.es};
+    RC(side_after_main(c));
+    Ctx cs{c.e, c.e->side, c.dt, c.es};
     std::vector<klab_gemm_args> gs;  // one grouped launch for the layer's weight gradients
     gs.reserve(q.size());
     for (const PendingWgrad& w : q) {
@@ -960,22 +950,22 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
   RC(rms_bwd(e->dxn, s.h[j], W[final_ln], s.rstd_f, nullptr, dh_cur, dy, final_ln, p, tag_of(stack_id, 0, SITE_FINAL), p,
              tag_of(stack_id, (int)L.size() - 1, SITE_FFN_OUT)));
   std::vector<int> pending_buckets;  // layers whose weight gradients are queued but not yet launched
-  // Release plan of the weight gradients (KLAB_WGRAD_GROUP_TILES = T, default 90; 0 = one 128-wide grouped launch per layer, round
-  // 2's form).  One T5-small layer's products are 48-64 tiles of 256 x 256 -- a fifth of the chip, and a large tile takes ~100 us
-  // whatever the grid, which is why PER-LAYER large tiles lost (KLAB_WGRAD_P8: 6.41 vs 6.18 ms).  So the layers of a stack except
+  // Release plan of the weight gradients (groups of >= GROUP_TILES = T tiles; switched off: one 128-wide grouped launch per layer,
+  // round 2's form).  One T5-small layer's products are 48-64 tiles of 256 x 256 -- a fifth of the chip, and a large tile
+  // takes ~100 us whatever the grid, which is why PER-LAYER large tiles lost (6.41 vs 6.18 ms).  So the layers of a stack except
   // its last are released in groups of >= T tiles (T5-small: decoder 3 + 2 layers, encoder 3 + 2; same box, three rounds, T = 0 / 90
   // / 110 (encoder 5 in one group) / 200: 5.990 / 5.855 / 5.880 / 5.982 ms per step), and the LAST layer alone on the
   // 128-wide kernel: its launch is the tail the segment's end waits for, and 70 us of tail hide behind the main chain's own last
   // kernels where a 180-us group does not.  A layer that reaches T on its own (T5-base / large) keeps the per-layer form.
   const int Ln = (int)L.size();
   std::vector<char> flush_at(Ln, 1);
-  static const int group_tiles = [] { const char* v = getenv("KLAB_WGRAD_GROUP_TILES"); return v ? atoi(v) : 90; }();
-  static const bool kv_per_layer = [] { const char* v = getenv("KLAB_KV_WGRAD_PER_LAYER"); return !v || atoi(v) != 0; }();
-  const bool kv_in_queue = dec && dkv_all && kv_per_layer && Gflat == e->G[2] && !e->use_graph && e->kvall_g_off >= 0;
-  if (group_tiles > 0 && Ln >= 3 && Gflat == e->G[2] && !e->use_graph) {
+  constexpr int GROUP_TILES = 90;
+  static const bool group_on = klab::env_on("KLAB_WGRAD_GROUP_TILES");
+  const bool kv_in_queue = dec && dkv_all && Gflat == e->G[2] && !e->use_graph && e->kvall_g_off >= 0;
+  if (group_on && Ln >= 3 && Gflat == e->G[2] && !e->use_graph) {
     auto T2 = [](int n, int k) { return (long)((n + 255) / 256) * ((k + 255) / 256); };
     const long tl = T2(d, ff) + T2(ff, d) + T2(d, inner) + T2(3 * inner, d) + (dec ? T2(d, inner) + T2(inner, d) + (kv_in_queue ? T2(2 * inner, d) : 0) : 0);
-    const int per_group = (int)((group_tiles + tl - 1) / tl), per_layer = dec ? 7 : 4;
+    const int per_group = (int)((GROUP_TILES + tl - 1) / tl), per_layer = dec ? 7 : 4;
     if (per_group >= 2) {
       const int body = Ln - 1;
       int ng = body / per_group;
@@ -1106,7 +1096,7 @@ int swin_forward(const Ctx& c, const float* pixels, float p_in, bool refresh_bia
   const int Kp = e->pe_kp;
   (void)K0;
   // frozen tower: convolution + LayerNorm in one launch straight from the pixels (no column matrix, nothing kept for a backward)
-  static const bool fused_pe = [] { const char* v = getenv("KLAB_SWIN_FUSED_EMBED"); return !v || atoi(v) != 0; }();
+  static const bool fused_pe = klab::env_on("KLAB_SWIN_FUSED_EMBED");
   int perc = KLAB_ERR_UNSUPPORTED;
   if (!e->cfg.train_swin && fused_pe && !e->fp8 && Kp >= 64)
     perc = klab_swin_patch_embed_fused(pixels, woff(c, P[e->si.pew].warena_off), Kp, W[e->si.peb], W[e->si.penw], W[e->si.penb], e->x0, e->x0t, c.dt,
@@ -1142,9 +1132,8 @@ int swin_forward(const Ctx& c, const float* pixels, float p_in, bool refresh_bia
       }
       const float* qkvb = ix.qb >= 0 ? e->farena + bias_off : nullptr;
       bias_off += 3 * C;
-      static const bool fused_qkv = [] { const char* v = getenv("KLAB_SWIN_FUSED_QKV"); return !v || atoi(v) != 0; }();
       int qrc = KLAB_ERR_UNSUPPORTED;
-      if (!e->cfg.train_swin && fused_qkv && q.bias)  // frozen tower, narrow stage, one-tile window: q|k|v never leave the chip
+      if (!e->cfg.train_swin && q.bias)  // frozen tower, narrow stage, one-tile window: q|k|v never leave the chip
         qrc = klab_swin_qkv_attn_fused(xt, woff(c, P[ix.qw].warena_off), qkvb, q.ctx, q.bias, W[ix.ls], c.dt, B, q.R, q.w, q.shift, q.H, C,
                                        c.ws());
       if (qrc != 0 && qrc != KLAB_ERR_UNSUPPORTED) return qrc;
@@ -1158,14 +1147,13 @@ int swin_forward(const Ctx& c, const float* pixels, float p_in, bool refresh_bia
         a.v_bias = qkvb ? qkvb + 2 * C : nullptr;                     // (padded windows: rows of the padded keys)
         RC(klab_swin_attn_fwd(&a, c.ws()));
       }
-      static const bool fused_proj = [] { const char* v = getenv("KLAB_SWIN_FUSED_PROJ"); return !v || atoi(v) != 0; }();
       int prc = KLAB_ERR_UNSUPPORTED;
-      if (!e->cfg.train_swin && fused_proj)  // frozen tower, narrow stage: output projection + LayerNorm + residual in one kernel
+      if (!e->cfg.train_swin)  // frozen tower, narrow stage: output projection + LayerNorm + residual in one kernel
         prc = klab_swin_proj_ln_fused(q.ctx, x, woff(c, P[ix.pw].warena_off), W[ix.pb], W[ix.ln1w], W[ix.ln1b], q.h1, q.h1t, c.dt, M, C, s.ln_eps,
                                       c.ws());
       if (prc != 0 && prc != KLAB_ERR_UNSUPPORTED) return prc;
       // frozen tower, wide stage (C = 256): Linear + bias + LayerNorm + residual in one launch, 64 rows x all columns per workgroup
-      static const bool fused_lin_ln = [] { const char* v = getenv("KLAB_SWIN_FUSED_LIN_LN"); return !v || atoi(v) != 0; }();
+      static const bool fused_lin_ln = klab::env_on("KLAB_SWIN_FUSED_LIN_LN");
       const bool wide_ln = !e->cfg.train_swin && !e->fp8 && fused_lin_ln;
       if (prc != 0 && wide_ln) {
         prc = klab_swin_linear_ln_fused(q.ctx, x, woff(c, P[ix.pw].warena_off), W[ix.pb], W[ix.ln1w], W[ix.ln1b], q.h1, q.h1t, c.dt, M, C, C,
@@ -1181,8 +1169,7 @@ int swin_forward(const Ctx& c, const float* pixels, float p_in, bool refresh_bia
         RC(gelu_fwd_for_linear(c, q.z, q.a, M, F));
       } else {
         // frozen tower, narrow stage: fc1 + GELU + fc2 + LayerNorm + residual in one kernel (the hidden layer stays on chip)
-        static const bool fused_mlp = [] { const char* v = getenv("KLAB_SWIN_FUSED_MLP"); return !v || atoi(v) != 0; }();
-        const int frc = !fused_mlp ? KLAB_ERR_UNSUPPORTED : klab_swin_mlp_fused(q.h1t, q.h1, woff(c, P[ix.f1w].warena_off), W[ix.f1b], woff(c, P[ix.f2w].warena_off), W[ix.f2b],
+        const int frc = klab_swin_mlp_fused(q.h1t, q.h1, woff(c, P[ix.f1w].warena_off), W[ix.f1b], woff(c, P[ix.f2w].warena_off), W[ix.f2b],
                                             W[ix.ln2w], W[ix.ln2b], q.h2, q.h2t, c.dt, M, C, s.ln_eps, c.ws());
         if (frc == 0) { x = q.h2; xt = q.h2t; continue; }
         if (frc != KLAB_ERR_UNSUPPORTED) return frc;
@@ -1507,22 +1494,7 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
     e->seed_set = true;
   }
   if (!e->side) {
-    {  // experiment knob: KLAB_SIDE_PRIO=low|high gives the side stream (weight gradients, language encoder) another priority
-      const char* pv = getenv("KLAB_SIDE_PRIO");
-      int lo = 0, hi = 0;
-      // experiment knob: KLAB_SIDE_CUS=n restricts the side stream to n of the 256 CUs (n / 8 per XCD, CU-mask bits are dealt
-      // round-robin over the XCDs) -- does confining the weight gradients to part of the chip hurt the main chain less?
-      const char* cm = getenv("KLAB_SIDE_CUS");
-      const int ncu = cm ? atoi(cm) : 0;
-      if (ncu >= 8 && ncu < 256) {
-        uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < ncu; ++i) mask[i >> 5] |= 1u << (i & 31);
-        RC((int)hipExtStreamCreateWithCUMask(&e->side, 8, mask));
-      } else if (pv && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && (pv[0] == 'l' || pv[0] == 'h'))
-        RC((int)hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, pv[0] == 'l' ? lo : hi));
-      else
-        RC((int)hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
-    }
+    RC((int)hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
     RC((int)hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
     RC((int)hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
     RC((int)hipEventCreateWithFlags(&e->ev_zero, hipEventDisableTiming));
@@ -1621,8 +1593,8 @@ int forward_part_a(klab_engine* e, hipStream_t stream, float p, bool refresh_fro
     Ctx cs{e, e->side, e->cfg.dtype, e->es};
     // Small kernels that depend on nothing but the inputs and the weights run here, ahead of the language encoder and off the
     // main chain (ev_join covers them): the position biases of the encoder and decoder stacks and the decoder's input embedding
-    // (5 launches of 4-6 us).  KLAB_EARLY_SMALL=0: where they were.
-    static const bool early = [] { const char* v = getenv("KLAB_EARLY_SMALL"); return !v || atoi(v) != 0; }();
+    // (5 launches of 4-6 us).  Off: where they were.
+    static const bool early = klab::env_on("KLAB_EARLY_SMALL");
     if (early && !e->use_graph) {
       const int H = cfg.main.n_heads;
       RC(klab_relbias_fwd(e->W[2][e->mi.enc[0].relb], e->enc.bucket, e->enc.bias, H, e->enc.Lseq, e->enc.Lseq, cs.ws()));
@@ -2141,9 +2113,8 @@ static int backward_segment(klab_engine* e, int segment, const float* dloss_dev,
     const float alpha = cfg.main.scale_decoder_outputs ? 1.f / sqrtf((float)d) : 1.f;
     Ctx cs{e, e->side, c.dt, c.es};
     // Clearing 242 MB of gradient slices and the bias accumulators took 36 + 12 us of the main chain (four fills in front of the
-    // kernels that need none of them).  They now run on the side stream, beside the LM-head input gradient; KLAB_ZERO_ON_SIDE=0:
-    // the old order.
-    static const bool zero_side = [] { const char* v = getenv("KLAB_ZERO_ON_SIDE"); return !v || atoi(v) != 0; }();
+    // kernels that need none of them).  They now run on the side stream, beside the LM-head input gradient; off: the old order.
+    static const bool zero_side = klab::env_on("KLAB_ZERO_ON_SIDE");
     const bool zside = zero_side && !e->use_graph;  // (host-side flags below: not for a captured sequence)
     if (zside) {
       RC(side_after_main(c));  // behind every earlier reader of the gradient buffers on the caller's stream (optimizer, running sums)
@@ -2169,9 +2140,6 @@ static int backward_segment(klab_engine* e, int segment, const float* dloss_dev,
     {  // d shared [V,d] = dlogits^T @ dec_out  (first of the tied weight's three contributors)
       klab_gemm_args g = G0(cs, V, d, Md, e->logits, V, 0, e->dec.out_t, d, 0, Gm + e->P[2][e->mi.shared].grad_off, d, KLAB_F32);
       g.alpha = alpha; g.alpha_dev = dloss_dev; g.accumulate = 1; g.atomic_ok = 1;
-      // KLAB_LMHEAD_WGRAD_P8=1 (experiment): 256 x 256 tiles (252 of them, half the operand bytes of the 1004 tiles of 128 x 128)
-      static const bool wg_p8 = [] { const char* v = getenv("KLAB_LMHEAD_WGRAD_P8"); return v && atoi(v) != 0; }();
-      if (wg_p8) g.name_tag = 2;
       RC(klab_gemm(&g, cs.ws()));
     }
     float* dh0 = nullptr;
@@ -2256,8 +2224,7 @@ int swin_backward(const Ctx& c, const float* dh0, float p_in) {
   long bias_off = bias_off_total;
   (void)bias_off;
   int swin_bucket = 0, blk_no = 0;
-  static const bool side_env = [] { const char* v = getenv("KLAB_SWIN_SIDE_WGRAD"); return !v || atoi(v) != 0; }();
-  const bool side_on = side_env && e->sdyA[0] != nullptr;
+  const bool side_on = e->sdyA[0] != nullptr;
   const Ctx cs{e, e->side, c.dt, c.es};
   for (int st = last; st >= 0; --st) {
     SwinStageBufs& sb = e->sw[st];

@@ -425,7 +425,7 @@ __device__ __forceinline__ void gemm_glds_body(const GemmP& p, const int bid = b
   // for them before its MFMAs: three exposed LDS round trips per tile of C).  The fragments of k-tile t are waited for BEFORE the
   // branch, so that a register copy hipcc may place at the branch cannot pick up data that has not landed.
   wait_lgkmcnt<0>();
-  if (nt - t == 4 && !(p.ablate & 128)) {
+  if (nt - t == 4) {
     wait_vmcnt<2 * LPS>();
     __builtin_amdgcn_s_barrier();
     mma_and(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, a0, b0, a1, b1, true, false, 0);
@@ -480,7 +480,6 @@ __device__ __forceinline__ void gemm_glds_body(const GemmP& p, const int bid = b
       }
   } else {
     __syncthreads();  // all LDS-DMA retired (vmcnt(0) above) and all fragment reads done: LDS is free for the epilogue
-    if (p.ablate & 16) { if (acc[0][0][0] == 12345.f) reinterpret_cast<float*>(p.C)[0] = 1.f; return; }
     staged_epilogue<T, BM, BN, MI, NI>(p, acc, alpha, smem, bm0, bn0, wm, wn, tid, lane);
   }
 }
@@ -678,7 +677,7 @@ __global__ __launch_bounds__(256) void gemm_glds_grouped_tn_kernel(GroupP g) {
   p.C = e.C; p.ldc = e.ldc; p.c_f32 = 1; p.accumulate = 1;
   p.alpha = e.alpha; p.alpha_dev = nullptr; p.bias = nullptr; p.act = 0;
   p.aux = nullptr; p.ldaux = 0; p.aux_mode = 0; p.aux_scale = 1.f; p.residual = nullptr; p.ldr = 0; p.r_f32 = 1;
-  p.drop_p = 0.f; p.seed = nullptr; p.tag = 0; p.splits = e.splits; p.epi = 0; p.ablate = 0;
+  p.drop_p = 0.f; p.seed = nullptr; p.tag = 0; p.splits = e.splits; p.epi = 0;
   // (measured: members whose K is not split adding their tile with staged, coalesced read-modify-writes instead of 16 K float
   // atomics per tile -- 0.082 vs 0.079 ms per launch, no change in the step: the atomics are not what bounds this kernel)
   gemm_glds_body<128, BN, false, false, true>(p, (int)blockIdx.x - e.start);
@@ -882,8 +881,7 @@ static int dispatch_tile(GemmP& p, bool atomic_ok, hipStream_t s, int p8_force =
     // very long K over few tiles (LM-head dgrad: K = vocabulary): one workgroup per CU streams its operands from HBM
     // with too little in flight; split K so that ~4 workgroups share a CU.  128x128 tiles when N allows: the streamed
     // operand (263 MB of dlogits) is re-read once per column tile, i.e. 4x instead of 8x for N = 512.
-    static const int lk = [] { const char* e = getenv("KLAB_GEMM_LONGK_TILE"); return e ? atoi(e) : 128; }();
-    const bool wide = lk == 128 && p.N >= 128;
+    const bool wide = p.N >= 128;
     const long t = wide ? tiles(128, 128) : tiles(128, 64);
     long sp = (1024 + t - 1) / t;
     if (sp > nt / 64) sp = nt / 64;
@@ -893,21 +891,14 @@ static int dispatch_tile(GemmP& p, bool atomic_ok, hipStream_t s, int p8_force =
       return wide ? dispatch_layout<T, 128, 128>(p, true, s) : dispatch_layout<T, 128, 64>(p, true, s);
     }
   }
-  {  // tuning aid: KLAB_GEMM_TILE = 1 (128x128) | 2 (128x64) | 3 (64x64) forces the tile of every unsplit product
-    static const int force = [] { const char* e = getenv("KLAB_GEMM_TILE"); return e ? atoi(e) : 0; }();
-    if (force == 1) return dispatch_layout<T, 128, 128>(p, false, s);
-    if (force == 2) return dispatch_layout<T, 128, 64>(p, false, s);
-    if (force == 3) return dispatch_layout<T, 64, 64>(p, false, s);
-  }
   if constexpr (sizeof(T) == 2) {
     // 256 x 128 tiles on eight waves (4 x 2 of 64 x 64; 85 FLOP per operand byte instead of 64; one workgroup per CU).  Measured
-    // per shape (tools/gemm_bench.py, KLAB_GEMM_W8=2 forces it wherever it fits): it wins where 128 x 128 tiles need a second,
+    // per shape (tools/gemm_bench.py): it wins where 128 x 128 tiles need a second,
     // poorly filled round of workgroups and the big tiles fit in ONE round (T5-large wo forward 75.7 -> 63.0 us, wi / qkv dgrad
     // 64 -> 56 / 52 -> 47 us), ties or loses everywhere else (several rounds of one-per-CU workgroups expose every epilogue)
-    static const int w8 = [] { const char* e = getenv("KLAB_GEMM_W8"); return e ? atoi(e) : 1; }();
     const bool w8_fits = p.a_kmajor && (p.K % 32) == 0 && p.K >= 128 && p.M >= 256 && p.N >= 128 && (p.b_kmajor || p.N >= 8);
     // (inside the configs[1] step, K = 512, the same rule measured 0.7 % SLOWER -- 6.40 vs 6.35 ms -- hence K >= 1024; configs[4] +0.6 %)
-    if (w8_fits && (w8 == 2 || (w8 == 1 && p.K >= 1024 && tiles(128, 128) > 256 && tiles(256, 128) <= 256))) {
+    if (w8_fits && p.K >= 1024 && tiles(128, 128) > 256 && tiles(256, 128) <= 256) {
       const int nt = p.K / 32;
       size_t lds = (size_t)(nt < KLAB_GLDS_STAGES ? nt : KLAB_GLDS_STAGES) * (256 + 128) * 64;
       const size_t epi = (size_t)epilogue_lds_bytes<256, 128>(p.c_f32);
@@ -923,10 +914,10 @@ static int dispatch_tile(GemmP& p, bool atomic_ok, hipStream_t s, int p8_force =
   }
   // a grid of about one workgroup per CU or more.  224, not 240: the T5-small encoder's M = 3712 gives 29 x 8 = 232 tiles of
   // 128 x 64, which measured 0.4 % faster per step than the 464 tiles of 64 x 64 the higher threshold chose (same box, 3 rounds:
-  // 6.135 / 6.139 / 6.167 vs 6.173 / 6.159 / 6.179 ms).  KLAB_GEMM_TILE_MIN: tuning aid.
-  static const int tmin = [] { const char* e = getenv("KLAB_GEMM_TILE_MIN"); return e ? atoi(e) : 224; }();
-  if (tiles(128, 128) >= tmin) return dispatch_layout<T, 128, 128>(p, false, s);
-  if (tiles(128, 64) >= tmin) return dispatch_layout<T, 128, 64>(p, false, s);
+  // 6.135 / 6.139 / 6.167 vs 6.173 / 6.159 / 6.179 ms).
+  constexpr int TILE_MIN = 224;
+  if (tiles(128, 128) >= TILE_MIN) return dispatch_layout<T, 128, 128>(p, false, s);
+  if (tiles(128, 64) >= TILE_MIN) return dispatch_layout<T, 128, 64>(p, false, s);
   if (atomic_ok && nt >= 16) {
     const bool big = p.M >= 128 && p.N >= 64;
     const long t = big ? tiles(128, 64) : tiles(64, 64);
@@ -1339,8 +1330,7 @@ extern "C" int klab_gemm(const klab_gemm_args* a, void* stream);
 extern "C" int klab_gemm_grouped(const klab_gemm_args* list, int n, void* stream) {
   using namespace klab;
   if (!list || n < 0) return KLAB_ERR_BADARG;
-  static const bool grouped_on = [] { const char* e = getenv("KLAB_GEMM_GROUPED"); return !e || atoi(e) != 0; }();
-  {  // (experiment, KLAB_WGRAD_P8=1) the whole list on 256 x 256 tiles without split-K: mm8p.hip
+  {  // lists the engine marks with tl_grouped_large_tiles: the whole list on 256 x 256 tiles without split-K (mm8p.hip)
     const int rc = mm8p_grouped_try(list, n, (hipStream_t)stream);
     if (rc != KLAB_ERR_UNSUPPORTED) return rc;
   }
@@ -1348,14 +1338,13 @@ extern "C" int klab_gemm_grouped(const klab_gemm_args* list, int n, void* stream
   g.n = 0;
   int blocks = 0;
   auto fits = [&](const klab_gemm_args* a) {
-    return grouped_on && a->dtype == KLAB_BF16 && !a->a_kmajor && !a->b_kmajor && a->c_dtype == KLAB_F32 && a->accumulate && a->atomic_ok &&
+    return a->dtype == KLAB_BF16 && !a->a_kmajor && !a->b_kmajor && a->c_dtype == KLAB_F32 && a->accumulate && a->atomic_ok &&
            !a->bias && !a->act && !a->aux && !a->residual && a->drop_p == 0.f && !a->alpha_dev && a->name_tag == 0 && a->M >= 128 &&
            a->N >= 64 && (a->K % 32) == 0 && a->K >= 512 && !(a->M & 7) && !(a->N & 7) && !(a->lda & 7) && !(a->ldb & 7) &&
            !((uintptr_t)a->A & 15) && !((uintptr_t)a->B & 15) && !((uintptr_t)a->C & 15);
   };
   // 128x128 tiles when every member is at least 128 wide (less operand traffic per flop), else 128x64
-  static const int wide_on = [] { const char* e = getenv("KLAB_GEMM_GROUP_WIDE"); return e ? atoi(e) : 1; }();
-  bool wide = wide_on != 0;
+  bool wide = true;
   for (int i = 0; i < n; ++i)
     if (fits(&list[i]) && list[i].N < 128) wide = false;
   const int BNr = wide ? 128 : 64;
@@ -1377,8 +1366,8 @@ extern "C" int klab_gemm_grouped(const klab_gemm_args* list, int n, void* stream
     if (fits(&list[i])) work += (long)((list[i].M + 127) / 128) * ((list[i].N + BNr - 1) / BNr) * (list[i].K / 32);
   // round 2 sweep (bench.py, two runs each): target 1024 -> 6.71-6.74 ms/step, 768 -> 6.70-6.72, 384 -> 6.62-6.63, 128 -> 6.64-6.69:
   // fewer, longer workgroups make the grouped kernel itself slower (78 vs 69 us) but leave more of the chip to the main chain
-  static const int tgt = [] { const char* e = getenv("KLAB_GEMM_GROUP_TARGET"); return e ? atoi(e) : 384; }();
-  long per_wg = work / (wide ? tgt / 2 : tgt);
+  constexpr int GROUP_TARGET = 384;
+  long per_wg = work / (wide ? GROUP_TARGET / 2 : GROUP_TARGET);
   if (per_wg < 16) per_wg = 16;
   for (int i = 0; i < n; ++i) {
     const klab_gemm_args* a = &list[i];
@@ -1427,19 +1416,13 @@ static void fill_gemmp(const klab_gemm_args* a, GemmP& p) {
     // aligned 16-byte vector and nothing is accumulated into C
     if (!a->accumulate && a->dtype == KLAB_BF16) {
       if (f == EF_AUXNZ && a->c_dtype == KLAB_BF16 && !(a->N & 7) && !(a->ldc & 7) && !(a->ldaux & 7) && !((uintptr_t)a->aux & 15)) f = EF_AUXNZ_CO;
-      static const bool dgelu_co = [] { const char* e = getenv("KLAB_GEMM_DGELU_CO"); return !e || atoi(e) != 0; }();
-      if (dgelu_co && f == EF_DGELU && a->c_dtype == KLAB_BF16 && !(a->N & 7) && !(a->ldc & 7) && !(a->ldaux & 7) && !((uintptr_t)a->aux & 15)) f = EF_DGELU_CO;
+      if (f == EF_DGELU && a->c_dtype == KLAB_BF16 && !(a->N & 7) && !(a->ldc & 7) && !(a->ldaux & 7) && !((uintptr_t)a->aux & 15)) f = EF_DGELU_CO;
       if ((f == EF_RES || f == (EF_DROP | EF_RES)) && a->c_dtype == KLAB_F32 && a->r_dtype == KLAB_F32 && !(a->N & 3) && !(a->ldc & 3) &&
           !(a->ldr & 3) && !((uintptr_t)a->residual & 15))
         f = (f & ~EF_RES) | EF_RES_CO;
     }
     if ((f & EF_DROP) && (long)a->M * a->N >= (1L << 32)) f = EF_GENERIC;  // dropout indices beyond 32 bits: the general body hashes 64-bit indices
     p.epi = f;  // combinations without a dedicated variant fall into the generic body (switch default)
-  }
-  {
-    static int ablate = -1;
-    if (ablate < 0) { const char* e = getenv("KLAB_GEMM_ABLATE"); ablate = e ? atoi(e) : 0; }
-    p.ablate = ablate;
   }
 }
 }  // namespace klab
@@ -1593,9 +1576,8 @@ extern "C" int klab_gemm_fp8(const klab_gemm_args* a, const float* a_row_scale, 
   }
   auto tiles = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn); };
   // LDS-DMA ring form (whole 64-byte k-tiles, rows the DMA can address): the production path; the register-staged kernels below
-  // take what is left (K % 64 != 0, tiny operands) and remain reachable with KLAB_FP8_GLDS=0
-  static const bool glds_on = [] { const char* e = getenv("KLAB_FP8_GLDS"); return !e || atoi(e) != 0; }();
-  if (glds_on && (p.K % 64) == 0 && p.K >= 64 && p.M >= 16 && p.N >= 16) {
+  // take what is left (K % 64 != 0, tiny operands)
+  if ((p.K % 64) == 0 && p.K >= 64 && p.M >= 16 && p.N >= 16) {
     p.splits = 1;
     const int nt = p.K / 64;
 #define FP8_GLDS(BM_, BN_)                                                                                              \

@@ -40,8 +40,7 @@ struct GemmP {
   const void* residual; long ldr; int r_f32;
   float drop_p; const uint32_t* seed; uint32_t tag;
   int splits;
-  int epi;     // feature set of the epilogue (EF_* bits), chosen on the host
-  int ablate;  // diagnostics only (KLAB_GEMM_ABLATE): 1 = no global loads, 2 = no MFMA, 4 = no LDS fragment reads
+  int epi;  // feature set of the epilogue (EF_* bits), chosen on the host
 };
 
 // Workgroup -> output tile.  Blocks are dealt round-robin over the 8 XCDs (b and b+8 share an L2), so the grid
@@ -60,14 +59,14 @@ __device__ __forceinline__ void tile_of_block(const GemmP& p, int BM, int BN, in
   const int kbytes = (p.K / (p.splits > 0 ? p.splits : 1)) * 2;
   if ((long)p.M <= (long)p.N) {  // A (M x K) is the smaller operand: m fastest
     int G = (2 << 20) / (BM * kbytes);
-    G = (G < 8 || G > tiles_m || (p.ablate & 32)) ? tiles_m : G;  // groups narrower than 8 tiles would re-read the streamed operand too often
+    G = (G < 8 || G > tiles_m) ? tiles_m : G;  // groups narrower than 8 tiles would re-read the streamed operand too often
     const int per_group = G * tiles_n, full = tiles_m / G;
     const int g = lin / per_group;
     if (g < full) { const int rem = lin - g * per_group; bm0 = (int)(g * G + rem % G) * BM; bn0 = (int)(rem / G) * BN; }
     else { const int rem = lin - full * per_group, gm = tiles_m - full * G; bm0 = (int)(full * G + rem % gm) * BM; bn0 = (int)(rem / gm) * BN; }
   } else {
     int G = (2 << 20) / (BN * kbytes);
-    G = (G < 8 || G > tiles_n || (p.ablate & 32)) ? tiles_n : G;
+    G = (G < 8 || G > tiles_n) ? tiles_n : G;
     const int per_group = G * tiles_m, full = tiles_n / G;
     const int g = lin / per_group;
     if (g < full) { const int rem = lin - g * per_group; bn0 = (int)(g * G + rem % G) * BN; bm0 = (int)(rem / G) * BM; }
@@ -171,7 +170,7 @@ __device__ __forceinline__ void copy_out_tile(const GemmP& p, const char* smem, 
   // mask operand requested from memory -- BEFORE the first store.  The general loop below does read, (load,) store per chunk; on
   // this ISA a store counts in vmcnt like a load, so each chunk's operand wait also drained the stores issued before it: 8-16
   // memory round trips in a row at the end of every tile.
-  if (bm0 + BM <= p.M && bn0 + BN <= p.N && vec_ok && (!p.accumulate || (f32out && CO == 0)) && !(p.ablate & 64)) {
+  if (bm0 + BM <= p.M && bn0 + BN <= p.N && vec_ok && (!p.accumulate || (f32out && CO == 0))) {
     auto fast = [&](auto esz_c) {
       constexpr int ESZ = decltype(esz_c)::value, EPC = 16 / ESZ, CPR = BN / EPC, PER = BM * CPR / NT;
       static_assert(BM * CPR % NT == 0, "whole chunks per thread");
@@ -257,11 +256,7 @@ __device__ __forceinline__ void copy_out_tile(const GemmP& p, const char* smem, 
           continue;
         }
       }
-      if (p.ablate & 64) {  // experiment: write-through (sc1) stores -- nothing left dirty in L2 for the end-of-kernel release
-        asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(val) : "memory");
-      } else {
-        *reinterpret_cast<f32x4*>(dst) = val;
-      }
+      *reinterpret_cast<f32x4*>(dst) = val;
     } else {
       const int epc = 1 << sh;
       const int nv = (p.N - n) < epc ? (p.N - n) : epc;
@@ -302,7 +297,6 @@ __device__ __forceinline__ void staged_epilogue(const GemmP& p, f32x4 (&acc)[MI]
   }
 #undef KLAB_EPI
   __syncthreads();
-  if (p.ablate & 8) return;
   if constexpr (sizeof(T) == 2) {
     if (p.epi == EF_AUXNZ_CO) { copy_out_tile<T, BM, BN, EF_AUXNZ_CO, NT>(p, smem, bm0, bn0, tid); return; }
     if (p.epi == EF_DGELU_CO) { copy_out_tile<T, BM, BN, EF_DGELU_CO, NT>(p, smem, bm0, bn0, tid); return; }

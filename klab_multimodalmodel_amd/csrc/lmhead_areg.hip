@@ -30,6 +30,7 @@ constexpr int BM = 128, BN = 128, KT = 8, BK = 64, K = KT * BK, R = 7, SLOT = BN
 constexpr int STG_PITCH = 272;  // the finished 128 x 128 bf16 tile, rows of 256 B + 16 (bank spread), written by all waves, read by waves 4-7
 constexpr int LDS_BYTES = R * SLOT + BM * STG_PITCH;
 constexpr int NTHREADS = 512;
+constexpr int MIN_N = 64 * BN;  // narrower outputs stay with the tiled kernel
 constexpr int INFL = 4 * (R - 3);  // DMA instructions (four per k-tile and issuing wave) that may stay in flight behind the k-tile waited for
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -45,7 +46,7 @@ __device__ __forceinline__ bf16x8 bfrag(const char* slot, int f, int ks, int lan
   return *reinterpret_cast<const bf16x8*>(slot + r * 128 + (((4 * ks + g) ^ (r & 7)) * 16));
 }
 
-__global__ __launch_bounds__(NTHREADS) void klab_lmhead_areg_gemm(GemmP p, int rotate) {
+__global__ __launch_bounds__(NTHREADS) void klab_lmhead_areg_gemm(GemmP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -61,11 +62,12 @@ __global__ __launch_bounds__(NTHREADS) void klab_lmhead_areg_gemm(GemmP p, int r
   // tile boundary also waited for that tile's stores to be acknowledged (41 us of a 199 us launch, measured by skipping them).
   // The cursor (tile, k-tile, slot) advances by one k-tile per issue: no division in the loop.
   // The 32 row blocks of an XCD walk the same eighth of the vocabulary in lockstep (every B line is fetched once per XCD and serves
-  // 32 workgroups); `rotate` starts each at a different tile instead (see the launch site).
+  // 32 workgroups).  Starting each at a rotated tile instead measured the same speed, but 1.03 GB per launch left L2 instead of
+  // ~0.35 GB (the 4 MB working set no longer survives next to the logits write stream).
   const bool dma_wave = wave < 4;
   const int srow = (wave & 3) * 32 + (lane >> 3), schunk = (lane & 7) ^ (lane >> 3);
-  const int ntl = t1 - t0, ts = t0 + (rotate ? rb % (ntl > 0 ? ntl : 1) : 0);
-  int is_tile = ts, is_kt = 0, is_slot = 0, issued = 0;
+  const int ntl = t1 - t0;
+  int is_tile = t0, is_kt = 0, is_slot = 0, issued = 0;
   const bf16_t* is_src;  // piece 0 of the current tile; pieces 1-3 are 8, 16, 24 rows further (N % 128 == 0: no row needs clamping)
   const long piece_stride = 8 * p.ldb;
   auto set_rows = [&]() { is_src = Bp + (long)(is_tile * BN + srow) * p.ldb + schunk * 8; };
@@ -79,7 +81,7 @@ __global__ __launch_bounds__(NTHREADS) void klab_lmhead_areg_gemm(GemmP p, int r
                                        (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
     ++issued;
     is_slot = is_slot + 1 == R ? 0 : is_slot + 1;
-    if (++is_kt == KT) { is_kt = 0; is_tile = is_tile + 1 == t1 ? t0 : is_tile + 1; set_rows(); }
+    if (++is_kt == KT) { is_kt = 0; ++is_tile; set_rows(); }
   };
 
   const int wm = wave >> 1, wn = wave & 1;
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(NTHREADS) void klab_lmhead_areg_gemm(GemmP p, int r
   char* stg = smem + R * SLOT;
   bf16_t* Cp = reinterpret_cast<bf16_t*>(p.C);
 
-  int prev_tile = ts;
+  int prev_tile = t0;
   auto store_tile = [&](int tile) {  // waves 4-7: 2048 chunks of 16 B, a wave-instruction covers 4 rows x 256 B
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(NTHREADS) void klab_lmhead_areg_gemm(GemmP p, int r
 #pragma unroll
   for (int jn = 0; jn < 4; ++jn) f0[0][jn] = bfrag(smem, wn * 4 + jn, 0, lane);
   int j = 0, cur_slot = 0;  // slot of k-tile j
-  for (int tt = 0, tile = ts; tt < ntl; ++tt, tile = tile + 1 == t1 ? t0 : tile + 1) {
+  for (int tt = 0, tile = t0; tt < ntl; ++tt, ++tile) {
     f32x4 acc[2][4];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -181,20 +183,15 @@ __global__ __launch_bounds__(NTHREADS) void klab_lmhead_areg_gemm(GemmP p, int r
 // KLAB_ERR_UNSUPPORTED: not this kernel's product (the caller continues with klab_lmhead_gemm's tiled form)
 int lmhead_areg_try(const GemmP& p, hipStream_t s) {
   using namespace la;
-  static const bool on = [] { const char* e = getenv("KLAB_LMHEAD_AREG"); return !e || atoi(e) != 0; }();
+  static const bool on = env_on("KLAB_LMHEAD_AREG");
   if (!on) return KLAB_ERR_UNSUPPORTED;
   if (p.K != K || !p.a_kmajor || !p.b_kmajor || p.c_f32 || p.accumulate || p.bias || p.act || p.aux || p.residual || p.drop_p != 0.f)
     return KLAB_ERR_UNSUPPORTED;
-  static const int min_n = [] { const char* e = getenv("KLAB_LMHEAD_MIN_N"); return e ? atoi(e) : 64 * BN; }();  // (tuning aid)
-  if (p.M < 1024 || p.N < min_n || (p.N % BN) || (p.ldc & 7) || (p.lda & 7) || (p.ldb & 7)) return KLAB_ERR_UNSUPPORTED;
+  if (p.M < 1024 || p.N < MIN_N || (p.N % BN) || (p.ldc & 7) || (p.lda & 7) || (p.ldb & 7)) return KLAB_ERR_UNSUPPORTED;
   const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(klab_lmhead_areg_gemm), (size_t)LDS_BYTES);
   if (rc) return rc;
   const unsigned grid = (unsigned)(((p.M + BM - 1) / BM) * NCHUNK);
-  // KLAB_LMHEAD_ROT=1: the row blocks of an XCD start at rotated tiles of their eighth of the vocabulary (32 regions in flight at once
-  // instead of one shared stream).  Measured the same speed, but 1.03 GB per launch leave L2 instead of ~0.35 GB (the 4 MB working set
-  // no longer survives next to the logits write stream), so the default is the lockstep walk.
-  static const int rotate = [] { const char* e = getenv("KLAB_LMHEAD_ROT"); return e ? atoi(e) : 0; }();
-  probed_launch(klab_lmhead_areg_gemm, dim3(grid), dim3(NTHREADS), (size_t)LDS_BYTES, s, p, rotate);
+  probed_launch(klab_lmhead_areg_gemm, dim3(grid), dim3(NTHREADS), (size_t)LDS_BYTES, s, p);
   KLAB_LAUNCH_CHECK();
   return KLAB_OK;
 }

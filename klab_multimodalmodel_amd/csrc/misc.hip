@@ -78,9 +78,9 @@ __global__ __launch_bounds__(256) void cast_pack_kernel(const CastDesc* __restri
 // bf16/f32 copy the next forward's GEMMs read, written straight into the engine's weight arena (the separate cast pass
 // over the masters disappears).  m / v live in flat buffers laid out like the flat gradient buffer.
 struct AdamDesc { float* p; long goff; long aoff; long n4_prefix; };  // aoff < 0: no arena copy
-struct AdamHyper { float lr_over_bc1, beta1, beta2, eps, weight_decay, inv_sqrt_bc2; int desc_in_lds; };
+struct AdamHyper { float lr_over_bc1, beta1, beta2, eps, weight_decay, inv_sqrt_bc2; };
 
-template <typename T, int U = 4, bool NT = false>
+template <typename T, int U = 4>
 __global__ __launch_bounds__(256) void adam_step_kernel(const AdamDesc* __restrict__ dglob, int nd, long begin4, long total4, const float* __restrict__ grads,
                                                         float* __restrict__ m, float* __restrict__ v, T* __restrict__ arena, AdamHyper h) {
   // The descriptor table (one entry per tensor: ~130 for T5-small) is searched once per thread and iteration -- eight DEPENDENT loads,
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const AdamDesc* __restri
   // of every batch of streaming loads and kept the kernel at 4.5 TB/s; a copy in LDS makes it ~100 cycles per step.
   constexpr int MAXD = 1024;  // (T5-large: ~560 tensors; 32 KiB)
   __shared__ AdamDesc dsh[MAXD];
-  const bool in_lds = nd <= MAXD && h.desc_in_lds;
+  const bool in_lds = nd <= MAXD;
   if (in_lds) {
     for (int i = threadIdx.x; i < nd; i += blockDim.x) dsh[i] = dglob[i];
     __syncthreads();
@@ -111,17 +111,10 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const AdamDesc* __restri
         while (lo + 1 < nd && d[lo + 1].n4_prefix <= g) ++lo;
         const long local = (g - d[lo].n4_prefix) * 4;
         pp[u] = d[lo].p + local; go[u] = d[lo].goff + local; ao[u] = d[lo].aoff < 0 ? -1 : d[lo].aoff + local;
-        if constexpr (NT) {
-          pv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pp[u]));
-          gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(grads + go[u]));
-          mv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + go[u]));
-          vv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + go[u]));
-        } else {
-          pv[u] = *reinterpret_cast<const f32x4*>(pp[u]);
-          gv[u] = *reinterpret_cast<const f32x4*>(grads + go[u]);
-          mv[u] = *reinterpret_cast<const f32x4*>(m + go[u]);
-          vv[u] = *reinterpret_cast<const f32x4*>(v + go[u]);
-        }
+        pv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pp[u]));
+        gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(grads + go[u]));
+        mv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + go[u]));
+        vv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + go[u]));
       }
     }
 #pragma unroll
@@ -136,15 +129,9 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const AdamDesc* __restri
           const float denom = sqrtf(vo[i]) * h.inv_sqrt_bc2 + h.eps;
           po[i] = pv[u][i] - h.lr_over_bc1 * (mo[i] / denom);
         }
-        if constexpr (NT) {
-          __builtin_nontemporal_store(po, reinterpret_cast<f32x4*>(pp[u]));
-          __builtin_nontemporal_store(mo, reinterpret_cast<f32x4*>(m + go[u]));
-          __builtin_nontemporal_store(vo, reinterpret_cast<f32x4*>(v + go[u]));
-        } else {
-          *reinterpret_cast<f32x4*>(pp[u]) = po;
-          *reinterpret_cast<f32x4*>(m + go[u]) = mo;
-          *reinterpret_cast<f32x4*>(v + go[u]) = vo;
-        }
+        __builtin_nontemporal_store(po, reinterpret_cast<f32x4*>(pp[u]));
+        __builtin_nontemporal_store(mo, reinterpret_cast<f32x4*>(m + go[u]));
+        __builtin_nontemporal_store(vo, reinterpret_cast<f32x4*>(v + go[u]));
         if (ao[u] >= 0) {
           if constexpr (sizeof(T) == 2) *reinterpret_cast<bf16x4*>(arena + ao[u]) = bf16x4{(bf16_t)po[0], (bf16_t)po[1], (bf16_t)po[2], (bf16_t)po[3]};
           else *reinterpret_cast<f32x4*>(arena + ao[u]) = po;
@@ -547,21 +534,20 @@ extern "C" int klab_adam_step_range(const void* desc_dev, int ndesc, long begin4
   if (!desc_dev || ndesc <= 0 || !grads || !m || !v || !arena || bias_corr1 <= 0.f || bias_corr2 <= 0.f || begin4 < 0 || end4 < begin4)
     return KLAB_ERR_BADARG;
   if (end4 == begin4) return KLAB_OK;
-  static const int desc_lds = [] { const char* e = getenv("KLAB_ADAM_DESC_LDS"); return !e || atoi(e) != 0 ? 1 : 0; }();
-  AdamHyper h{lr / bias_corr1, beta1, beta2, eps, weight_decay, 1.f / sqrtf(bias_corr2), desc_lds};
+  AdamHyper h{lr / bias_corr1, beta1, beta2, eps, weight_decay, 1.f / sqrtf(bias_corr2)};
   hipStream_t s = (hipStream_t)stream;
-  static const int cap = [] { const char* e = getenv("KLAB_ADAM_GRID"); return e ? atoi(e) : 1024; }();
-  // non-temporal loads / stores: every byte is touched once per step (415 -> 397 us); an 8-deep unroll measured 1.5 ms (spills)
-  static const bool nt = [] { const char* e = getenv("KLAB_ADAM_NT"); return !e || atoi(e) != 0; }();
+  constexpr int ADAM_GRID = 1024;
+  // non-temporal loads / stores (adam_step_kernel): every byte is touched once per step (415 -> 397 us); an 8-deep unroll measured
+  // 1.5 ms (spills)
   constexpr int U = 4;
   long gl = ((end4 - begin4 + U - 1) / U + 255) / 256;
-  const unsigned grid = (unsigned)(gl < 1 ? 1 : (gl > cap ? cap : gl));
-#define ADAM_LAUNCH(TT, NN)                                                                                                       \
-  hipLaunchKernelGGL((adam_step_kernel<TT, U, NN>), dim3(grid), dim3(256), 0, s, (const AdamDesc*)desc_dev, ndesc, begin4, end4, grads, m, v, \
-                     (TT*)arena, h)
-  if (dtype == KLAB_BF16) { if (nt) ADAM_LAUNCH(bf16_t, true); else ADAM_LAUNCH(bf16_t, false); }
-  else { if (nt) ADAM_LAUNCH(float, true); else ADAM_LAUNCH(float, false); }
-#undef ADAM_LAUNCH
+  const unsigned grid = (unsigned)(gl < 1 ? 1 : (gl > ADAM_GRID ? ADAM_GRID : gl));
+  if (dtype == KLAB_BF16)
+    hipLaunchKernelGGL((adam_step_kernel<bf16_t, U>), dim3(grid), dim3(256), 0, s, (const AdamDesc*)desc_dev, ndesc, begin4, end4, grads, m, v,
+                       (bf16_t*)arena, h);
+  else
+    hipLaunchKernelGGL((adam_step_kernel<float, U>), dim3(grid), dim3(256), 0, s, (const AdamDesc*)desc_dev, ndesc, begin4, end4, grads, m, v,
+                       (float*)arena, h);
   KLAB_LAUNCH_CHECK();
   return KLAB_OK;
 }
@@ -629,10 +615,9 @@ extern "C" int klab_ce_fwd(void* logits, long ld, int dtype, const long long* la
     KLAB_LAUNCH_CHECK();
   }
   write_grad &= 1;
-  static const bool onepass = [] { const char* e = getenv("KLAB_CE_ONEPASS"); return !e || atoi(e) != 0; }();
-  if (dtype == KLAB_BF16 && onepass && V <= 256 * 8 * 16 && V > 256 * 8 * 8)
+  if (dtype == KLAB_BF16 && V <= 256 * 8 * 16 && V > 256 * 8 * 8)
     hipLaunchKernelGGL((ce_fwd_onepass_kernel<bf16_t, 16>), dim3(rows), dim3(256), 0, s, (bf16_t*)logits, ld, labels, V, inv_n, loss_row, write_grad);
-  else if (dtype == KLAB_BF16 && onepass && V <= 256 * 8 * 8)
+  else if (dtype == KLAB_BF16 && V <= 256 * 8 * 8)
     hipLaunchKernelGGL((ce_fwd_onepass_kernel<bf16_t, 8>), dim3(rows), dim3(256), 0, s, (bf16_t*)logits, ld, labels, V, inv_n, loss_row, write_grad);
   else if (dtype == KLAB_BF16)
     hipLaunchKernelGGL(ce_fwd_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, (bf16_t*)logits, ld, labels, V, inv_n, loss_row, write_grad);

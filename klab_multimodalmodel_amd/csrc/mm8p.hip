@@ -452,7 +452,7 @@ __global__ __launch_bounds__(512) void mm8p_kernel(GemmP p) { mm8p_body<AK, BKM,
 // workgroup: no split-K, no atomics, half the operand traffic of the 128 x 128 split-K form (gemm.hip's grouped kernel), and a
 // layer's gradients occupy ~50 CUs instead of all 256 -- they run on a side stream beside the activation-gradient chain.
 struct Group8Entry { const void* A; long lda; const void* B; long ldb; float* C; long ldc; int M, N, K, start; float alpha; };
-constexpr int GROUP_MAX = 32;  // (several layers' products in one grid: KLAB_WGRAD_GROUP_TILES)
+constexpr int GROUP_MAX = 32;  // (several layers' products in one grid: engine.cpp's grouped weight gradients)
 struct Group8P { Group8Entry e[GROUP_MAX]; int n; };
 __global__ __launch_bounds__(512) void mm8p_grouped_tn_kernel(Group8P g) {
   int i = 0;
@@ -469,7 +469,7 @@ __global__ __launch_bounds__(512) void mm8p_grouped_tn_kernel(Group8P g) {
   p.aux = nullptr; p.ldaux = 0; p.aux_mode = 0; p.aux_scale = 1.f;
   p.residual = nullptr; p.ldr = 0; p.r_f32 = 1;
   p.drop_p = 0.f; p.seed = nullptr; p.tag = 0;
-  p.splits = 1; p.epi = 0; p.ablate = 0;
+  p.splits = 1; p.epi = 0;
   mm8p_body<false, false, false>(p, (int)blockIdx.x - e.start);
 }
 
@@ -479,8 +479,7 @@ __global__ __launch_bounds__(512) void mm8p_grouped_tn_kernel(Group8P g) {
 // 128 x 128 split-K grouped kernel for the whole list)
 int mm8p_grouped_try(const klab_gemm_args* list, int n, hipStream_t s) {
   using namespace p8;
-  static const int mode = [] { const char* e = getenv("KLAB_WGRAD_P8"); return e ? atoi(e) : 0; }();  // 1: every grouped list (experiment)
-  if ((mode == 0 && !tl_grouped_large_tiles) || n <= 0 || n > GROUP_MAX) return KLAB_ERR_UNSUPPORTED;
+  if (!tl_grouped_large_tiles || n <= 0 || n > GROUP_MAX) return KLAB_ERR_UNSUPPORTED;
   Group8P g;
   g.n = 0;
   int blocks = 0;
@@ -508,8 +507,8 @@ int mm8p_grouped_try(const klab_gemm_args* list, int n, hipStream_t s) {
 // Host side: is this product worth the large tiles, and the launch.  Returns KLAB_ERR_UNSUPPORTED when it is not taken.
 int mm8p_try(const GemmP& pin, bool atomic_ok, int force, hipStream_t s) {
   using namespace p8;
-  static const int mode = [] { const char* e = getenv("KLAB_GEMM_P8"); return e ? atoi(e) : 1; }();  // 0: off, 1: heuristic, 2: whenever legal
-  if (mode == 0 && force <= 0) return KLAB_ERR_UNSUPPORTED;
+  static const bool on = env_on("KLAB_GEMM_P8");  // off: only name_tag forcing reaches this kernel
+  if (!on && force <= 0) return KLAB_ERR_UNSUPPORTED;
   GemmP p = pin;
   if (p.K % BK || p.K < 2 * BK) return KLAB_ERR_UNSUPPORTED;
   if (!p.a_kmajor && (p.M % 8)) return KLAB_ERR_UNSUPPORTED;
@@ -523,7 +522,7 @@ int mm8p_try(const GemmP& pin, bool atomic_ok, int force, hipStream_t s) {
     const int nt = p.K / BK;
     while (tiles * splits * 2 <= ncu && nt / (splits * 2) >= 8) splits *= 2;
   }
-  if (mode == 1 && force <= 0) {
+  if (force <= 0) {
     // Measured envelope (tools/gemm_bench.py --sq, KLAB_BENCH_AB=1): per 64 k the main loop takes 1.5 us on a 4096 x 4096 output
     // (1.44 PFLOP/s marginal) against 1.7 -> 4.0 us for the four-wave ring as K grows from 1024 to 8192, but a launch carries a
     // larger fixed cost (one workgroup per CU: nothing hides the ring fill and the two-slab epilogue).  It pays from K = 2048 per

@@ -148,9 +148,8 @@ int mmf8_try(const GemmP& pin, const float* sa, const float* sb, long sb_stride,
   // is correct and SLOWER than gemm_glds_fp8_kernel (qkv 40.8 vs 33.2 us, wi 50.4 vs 41.2, 4096^3 104.8 vs 94.2) although its
   // matrix instruction runs at twice the rate -- every tiled kernel of this library, bf16 or fp8, 128- or 256-wide, sits at
   // 10-11.5 TB/s of L2 -> LDS operand traffic (1 GB per 4096^3 launch in 94-110 us), so a 128 x 128 tile is bound by its operand
-  // bytes, not by the MFMA rate.  Hence opt-in: KLAB_FP8_SCALED=1, or klab_gemm_args.name_tag = 2 per call (tests).
-  static const bool on = [] { const char* e = getenv("KLAB_FP8_SCALED"); return e && atoi(e) != 0; }();
-  if (force < 0 || (!on && force <= 0)) return KLAB_ERR_UNSUPPORTED;
+  // bytes, not by the MFMA rate.  Hence opt-in, per call: klab_gemm_args.name_tag = 2 (tests).
+  if (force <= 0) return KLAB_ERR_UNSUPPORTED;
   GemmP p = pin;
   if ((p.K % BK) || p.K < BK || p.M < 16 || p.N < 16) return KLAB_ERR_UNSUPPORTED;
   p.splits = 1;

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const float* __restric
 
 // Fused row + weight-gradient variant for d <= 256*SLOTS: the row's x / dy_eff stay in registers between the two passes,
 // each lane keeps the dw partial of its own columns over the block's rows, the 4 waves fold through LDS and a block
-// issues ONE f32 atomic per column (<= KLAB_RMS_BLOCKS-way contention; the un-reduced per-wave atomics were 10x slower).
+// issues ONE f32 atomic per column (<= RMS_BLOCKS-way contention; the un-reduced per-wave atomics were 10x slower).
 // IDX32: rows * d < 2^32, so an element's dropout index fits 32 bits and the one-round hash of drop_mult (high word zero) is
 // evaluated without its two branches (drop_mult32_nb gives the identical multiplier): sixteen copies of them per row otherwise cut
 // the unrolled body into ~56 basic blocks
@@ -597,9 +597,9 @@ extern "C" int klab_rmsnorm_fwd_q8(const float* x, const float* w, void* y_bf16,
 }
 
 static int rms_part_rows(int rows) {
-  static const int nblk = [] { const char* v = getenv("KLAB_RMS_BLOCKS"); int n = v ? atoi(v) : 512; return n < 1 ? 1 : n; }();
+  constexpr int RMS_BLOCKS = 512;
   const int g16 = (rows + 15) / 16;
-  return g16 < nblk ? g16 : nblk;
+  return g16 < RMS_BLOCKS ? g16 : RMS_BLOCKS;
 }
 static int rms_fused_launch(const float* dy, const float* x, const float* w, const float* rstd, const float* dres, float* dx, void* dxt,
                             int dxt_dtype, float* dw, int partial, int rows, int d, int grp, int grp_stride, int off, float p_y,
@@ -741,8 +741,7 @@ static int layernorm_bwd_impl(const float* dout, const void* y, int y_dtype, con
   if (!dout || !y || !gamma || !mean || !rstd || rows < 0 || C <= 0 || (C & 3)) return KLAB_ERR_BADARG;
   if (dprev_bias && !dy) return KLAB_ERR_BADARG;
   if (rows == 0) return KLAB_OK;
-  static const bool fused_on = [] { const char* e = getenv("KLAB_LN_BWD_FUSED"); return !e || atoi(e) != 0; }();
-  if (dy && (dgamma || dbeta || dprev_bias) && C <= 1024 && fused_on) {
+  if (dy && (dgamma || dbeta || dprev_bias) && C <= 1024) {
     const int gf = rms_part_rows(rows);
 #define LNB(TI, SL)                                                                                                                   \
     hipLaunchKernelGGL((layernorm_bwd_fused_kernel<TI, SL>), dim3(gf), dim3(1024), 0, s, dout, (const TI*)y, gamma, mean, rstd, (TI*)dy, \

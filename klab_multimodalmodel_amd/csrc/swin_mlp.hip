@@ -273,8 +273,5 @@ extern "C" int klab_swin_proj_ln_fused(const void* x, const float* shortcut, con
   MlpP p{(const bf16_t*)x, shortcut, (const bf16_t*)w, b, nullptr, nullptr, gamma, beta, out, (bf16_t*)outt, M, eps};
   if (C == 64) return launch_mlp<64, 2, true>(p, (hipStream_t)stream);
   if (C == 128) return launch_mlp<128, 2, true>(p, (hipStream_t)stream);
-  // C = 256 (stage 2 of the caption tower): opt-in experiment (KLAB_SWIN_PROJ256=1); see DESIGN for the measurement
-  static const bool p256 = [] { const char* e = getenv("KLAB_SWIN_PROJ256"); return e && atoi(e) != 0; }();
-  if (C == 256 && p256) return launch_mlp<256, 2, true>(p, (hipStream_t)stream);
   return KLAB_ERR_UNSUPPORTED;
 }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """klab_gemm_fp8 on the forward Linear shapes of BASELINE configs[4] (T5-large widths, M = 32 x 153 encoder tokens): us and TFLOP/s
-per launch, next to klab_gemm (bf16) on the same shapes.  KLAB_FP8_SCALED=0 selects the non-scaled fp8 kernels (A/B)."""
+per launch, next to klab_gemm (bf16) on the same shapes.  The fp8 products run on the default (non-scaled) kernels; the block-scaled
+kernel is selected per call with ops.gemm_fp8(..., name_tag=2)."""
 import os
 import sys
 
