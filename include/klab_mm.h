@@ -546,6 +546,48 @@ int klab_engine_sample_begin(klab_engine* e, int num_return_sequences, int max_l
 int klab_engine_sample_step(klab_engine* e, int t, void* ws, void* stream);
 const int* klab_engine_sample_stop_word(klab_engine* e, void* ws, int pos);
 int klab_engine_sample_result(klab_engine* e, void* ws, long long* seq, int length, void* stream);
+
+/* ---- logits processors (HF's RepetitionPenalty, NoRepeatNGram, NoBadWords, MinLength, MinNewTokensLength, in that order;
+ * csrc/logits_proc.hip) --------------------------------------------------------------------------------------------------
+ * klab_logits_process_rows: one processed fp32 row per row r < rows from logits row (r / row_div) (element stride ld),
+ * V <= 32768 (KLAB_ERR_UNSUPPORTED above).  Scores = fp32 logits, or their log_softmax when log_softmax != 0 (beam search).
+ * History of row r: seq[r*ld_seq + p] for 1 <= p < cur_len, position 0 read as start_id (seq may hold anything there);
+ * cur_len <= 1024.  Then, in HF's order:
+ *   repetition_penalty != 1: every token of the history (once, however often it occurs) s -> s < 0 ? s * p : s / p;
+ *   no_repeat_ngram_size n > 0, cur_len >= n: every window w <= cur_len - n whose n-1 tokens equal the last n-1 bans token w+n-1;
+ *   bad words (n_bad entries; entry i = bad_tok[bad_off[i] .. bad_off[i+1]), device, bad_off[n_bad] <= 1024): a 1-token entry is
+ *     always banned; a longer entry of length L <= cur_len bans its last token when the history ends with its first L-1;
+ *   cur_len < min_length or cur_len - 1 < min_new_tokens: eos_id banned.
+ * Banned = -inf.  Outputs: out [rows, ld_out] f32 (NULL allowed only with pick).  pick != 0: also the arg-max of the processed
+ * row (the lowest id among equal maxima, 0 when every score is -inf) with klab_sample_rows' bookkeeping: done [rows], eos_id,
+ * pad_id, tokens [rows], seq[r*ld_seq + cur_len] (and seq[r*ld_seq] = start_id when cur_len == 1), stop_word.             */
+typedef struct {
+  int dtype;
+  const void* logits; long ld; int row_div;
+  int rows, V, log_softmax;
+  long long* seq; long ld_seq; int cur_len, start_id;
+  float repetition_penalty; int no_repeat_ngram_size, min_length, min_new_tokens, eos_id;
+  int n_bad; const int* bad_off; const int* bad_tok;
+  float* out; long ld_out;
+  int pick; int* done; int pad_id; long long* tokens; int* stop_word;
+} klab_logits_proc_args;
+int klab_logits_process_rows(const klab_logits_proc_args* a, void* stream);
+/* the beam top-2k of klab_beam_topk over scores that are already log-probabilities (f32, e.g. klab_logits_process_rows with
+ * log_softmax): per sample b, the 2k best of  scores row b*k+j + run_score[b*k+j], same order, ties and buffers.           */
+int klab_beam_topk_scores(const float* scores, long ld, int row_div, const float* run_score, int B, int k, int V, float* row_score,
+                          int* row_idx, float* out_score, int* out_idx, void* stream);
+/* Processor settings of an engine binding (host memory; bad_off / bad_tok are copied): NULL = none, the default.  When set, the
+ * sample and beam workspaces grow by an f32 [rows, vocab] buffer and the bad-words table, and every sample / beam begin and step
+ * runs klab_logits_process_rows before the sampler or the top-2k.  pick != 0 (sampling entry points only): greedy decoding --
+ * the processed arg-max replaces the draw (temperature, top_k, top_p and seed are then ignored).  A begun search keeps the
+ * settings it began with.  KLAB_ERR_BADARG for penalty <= 0, negative sizes, empty entries or ids >= vocab;
+ * KLAB_ERR_UNSUPPORTED for more than 1024 bad-word tokens in all.                                                         */
+typedef struct {
+  float repetition_penalty; int no_repeat_ngram_size, min_length, min_new_tokens;
+  int n_bad; const int* bad_off; const int* bad_tok;
+  int pick;
+} klab_logits_proc_cfg;
+int klab_engine_set_logits_processors(klab_engine* e, const klab_logits_proc_cfg* cfg);
 /* segment 0: LM head + decoder + tied embedding; 1: encoder; 2: Swin (no-op unless train_swin).
  * dloss_dev: device scalar d(objective)/d(loss) (NULL = 1).                                       */
 int klab_engine_backward(klab_engine* e, int segment, const float* dloss_dev, void* stream);

@@ -68,6 +68,19 @@ class SampleArgs(C.Structure):  # klab_sample_args
                 ("tokens", vp), ("seq", vp), ("ld_seq", i64), ("pos", i32), ("stop_word", vp)]
 
 
+class LogitsProcArgs(C.Structure):  # klab_logits_proc_args
+    _fields_ = [("dtype", i32), ("logits", vp), ("ld", i64), ("row_div", i32), ("rows", i32), ("V", i32), ("log_softmax", i32),
+                ("seq", vp), ("ld_seq", i64), ("cur_len", i32), ("start_id", i32),
+                ("repetition_penalty", f32), ("no_repeat_ngram_size", i32), ("min_length", i32), ("min_new_tokens", i32), ("eos_id", i32),
+                ("n_bad", i32), ("bad_off", vp), ("bad_tok", vp), ("out", vp), ("ld_out", i64),
+                ("pick", i32), ("done", vp), ("pad_id", i32), ("tokens", vp), ("stop_word", vp)]
+
+
+class LogitsProcCfg(C.Structure):  # klab_logits_proc_cfg
+    _fields_ = [("repetition_penalty", f32), ("no_repeat_ngram_size", i32), ("min_length", i32), ("min_new_tokens", i32),
+                ("n_bad", i32), ("bad_off", C.POINTER(i32)), ("bad_tok", C.POINTER(i32)), ("pick", i32)]
+
+
 # every exported entry point of include/klab_mm.h: name -> argtypes (restype is always int)
 SIGNATURES = {
     "klab_version": [],
@@ -99,6 +112,8 @@ SIGNATURES = {
     "klab_beam_init": [C.POINTER(BeamUpdateArgs), i32, i32, vp],
     "klab_beam_copy_rows": [i32, vp, i64, i32, vp, i64, i32, i32, vp],
     "klab_sample_rows": [C.POINTER(SampleArgs), vp],
+    "klab_logits_process_rows": [C.POINTER(LogitsProcArgs), vp],
+    "klab_beam_topk_scores": [vp, i64, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "klab_dbias_reduce": [vp, i32, vp, i32, i32, i32, i32, vp],
     "klab_swin_mlp_fused": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "klab_gemm_grouped": [vp, i32, vp],

@@ -5,6 +5,7 @@
 //                      Two launches: one 256-thread workgroup per row streams the row once (online max / sum-exp and a
 //                      per-thread sorted candidate list, merged across the workgroup in LDS), then one wave per sample merges
 //                      the k sorted row lists.  Ties are broken by the LOWER flat index, in both stages.
+//   klab_beam_topk_scores : the same over rows that already hold processed log-probabilities (csrc/logits_proc.hip).
 //   klab_beam_update : one wave per sample; HF's `_get_running_beams_for_next_iteration`, `_update_finished_beams`,
 //                      `_check_early_stop_heuristic` and the per-sample part of `_beam_search_has_unfinished_sequences`
 //                      over fixed-shape state (klab_beam_update_args, include/klab_mm.h).
@@ -46,8 +47,9 @@ __device__ __forceinline__ void list_insert(float (&lv)[KMAX], int (&li)[KMAX], 
   }
 }
 
-// one workgroup per row r = b*k + beam: the K2 best (log_softmax(row) + run_score[r], beam*V + token) of the row, sorted
-template <typename T, int KMAX, int TOPK_THREADS = topk_threads<KMAX>()>
+// one workgroup per row r = b*k + beam: the K2 best (log_softmax(row) + run_score[r], beam*V + token) of the row, sorted.
+// NORMED: the row already holds log-probabilities (f32, processed; may hold -inf): row + run_score[r], no log_softmax.
+template <typename T, int KMAX, bool NORMED = false, int TOPK_THREADS = topk_threads<KMAX>()>
 __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_rows_kernel(const T* __restrict__ logits, long ld, int row_div,
                                                                      const float* __restrict__ run_score, int k, int V, int K2,
                                                                      float* __restrict__ row_score, int* __restrict__ row_idx) {
@@ -63,8 +65,10 @@ __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_rows_kernel(const T* _
   for (int c = 0; c < KMAX; ++c) { lv[c] = -INFINITY; li[c] = INT_MAX; }
   float m = -INFINITY, s = 0.f;
   auto take = [&](float xv, int j) {
-    if (xv > m) { s = s * __expf(m - xv) + 1.f; m = xv; }
-    else s += __expf(xv - m);
+    if constexpr (!NORMED) {
+      if (xv > m) { s = s * __expf(m - xv) + 1.f; m = xv; }
+      else s += __expf(xv - m);
+    }
     list_insert<KMAX>(lv, li, xv, j);
   };
   constexpr int VEC = 16 / sizeof(T);
@@ -117,7 +121,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_rows_kernel(const T* _
     if (h < KMAX && s_i[tid * KMAX + h] == bi) ++h;  // indices are unique within a row: exactly one thread advances
     if (tid == 0) {
       const long o = (long)r * K2 + n;
-      row_score[o] = ((bv - M) - logS) + rs;  // log_softmax (x - max - log sum exp), then + running score
+      row_score[o] = (NORMED ? bv : ((bv - M) - logS)) + rs;  // log_softmax (x - max - log sum exp), then + running score
       row_idx[o] = bi == INT_MAX ? INT_MAX : beam * V + bi;
     }
   }
@@ -263,20 +267,20 @@ __global__ void copy_rows_kernel(const T* __restrict__ src, long src_ld, int src
   for (int c = threadIdx.x; c < cols; c += blockDim.x) d[c] = s[c];
 }
 
-template <typename T, int KMAX>
+template <typename T, int KMAX, bool NORMED>
 static void launch_rows(const void* logits, long ld, int row_div, const float* rs, int B, int k, int V, float* rsc, int* ri, hipStream_t s) {
-  hipLaunchKernelGGL((beam_topk_rows_kernel<T, KMAX>), dim3(B * k), dim3(topk_threads<KMAX>()), 0, s, (const T*)logits, ld, row_div, rs, k, V, 2 * k,
+  hipLaunchKernelGGL((beam_topk_rows_kernel<T, KMAX, NORMED>), dim3(B * k), dim3(topk_threads<KMAX>()), 0, s, (const T*)logits, ld, row_div, rs, k, V, 2 * k,
                      rsc, ri);
 }
 
-template <typename T>
+template <typename T, bool NORMED = false>
 static int topk_dispatch(const void* logits, long ld, int row_div, const float* rs, int B, int k, int V, float* rsc, int* ri, hipStream_t s) {
   const int K2 = 2 * k;
-  if (K2 <= 2) launch_rows<T, 2>(logits, ld, row_div, rs, B, k, V, rsc, ri, s);
-  else if (K2 <= 4) launch_rows<T, 4>(logits, ld, row_div, rs, B, k, V, rsc, ri, s);
-  else if (K2 <= 8) launch_rows<T, 8>(logits, ld, row_div, rs, B, k, V, rsc, ri, s);
-  else if (K2 <= 16) launch_rows<T, 16>(logits, ld, row_div, rs, B, k, V, rsc, ri, s);
-  else launch_rows<T, 32>(logits, ld, row_div, rs, B, k, V, rsc, ri, s);
+  if (K2 <= 2) launch_rows<T, 2, NORMED>(logits, ld, row_div, rs, B, k, V, rsc, ri, s);
+  else if (K2 <= 4) launch_rows<T, 4, NORMED>(logits, ld, row_div, rs, B, k, V, rsc, ri, s);
+  else if (K2 <= 8) launch_rows<T, 8, NORMED>(logits, ld, row_div, rs, B, k, V, rsc, ri, s);
+  else if (K2 <= 16) launch_rows<T, 16, NORMED>(logits, ld, row_div, rs, B, k, V, rsc, ri, s);
+  else launch_rows<T, 32, NORMED>(logits, ld, row_div, rs, B, k, V, rsc, ri, s);
   KLAB_LAUNCH_CHECK();
   return KLAB_OK;
 }
@@ -294,6 +298,20 @@ extern "C" int klab_beam_topk(int dtype, const void* logits, long ld, int row_di
   if (dtype == KLAB_BF16) rc = topk_dispatch<bf16_t>(logits, ld, row_div, run_score, B, k, V, row_score, row_idx, s);
   else if (dtype == KLAB_F32) rc = topk_dispatch<float>(logits, ld, row_div, run_score, B, k, V, row_score, row_idx, s);
   else return KLAB_ERR_BADARG;
+  if (rc) return rc;
+  hipLaunchKernelGGL(beam_topk_merge_kernel, dim3(B), dim3(64), 0, s, row_score, row_idx, k, 2 * k, out_score, out_idx);
+  KLAB_LAUNCH_CHECK();
+  return KLAB_OK;
+}
+
+extern "C" int klab_beam_topk_scores(const float* scores, long ld, int row_div, const float* run_score, int B, int k, int V,
+                                     float* row_score, int* row_idx, float* out_score, int* out_idx, void* stream) {
+  using namespace klab;
+  if (!scores || !run_score || !row_score || !row_idx || !out_score || !out_idx || B <= 0 || k < 1 || k > 16 || row_div < 1 ||
+      V < 2 * k || ld < V)
+    return KLAB_ERR_BADARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = topk_dispatch<float, true>(scores, ld, row_div, run_score, B, k, V, row_score, row_idx, s);
   if (rc) return rc;
   hipLaunchKernelGGL(beam_topk_merge_kernel, dim3(B), dim3(64), 0, s, row_score, row_idx, k, 2 * k, out_score, out_idx);
   KLAB_LAUNCH_CHECK();

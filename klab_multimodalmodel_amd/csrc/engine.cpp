@@ -81,6 +81,13 @@ struct Bump {
   }
 };
 
+// logits-processor settings (klab_engine_set_logits_processors); table = bad_off [n_bad + 1] then bad_tok, as they go to the device
+struct ProcSet {
+  bool on = false;
+  klab_logits_proc_cfg cfg{};
+  std::vector<int> table;
+};
+
 }  // namespace
 
 struct klab_engine {
@@ -136,6 +143,8 @@ struct klab_engine {
   // sampling (klab_engine_sample_*): parameters of the run begun last on this binding, the last position sampled
   int sp_n = 0, sp_len = 0, sp_cur = 0, sp_topk = 0, sp_eos = 1, sp_pad = 0; float sp_temp = 1.f, sp_topp = 1.f;
   unsigned long long sp_seed = 0;
+  // logits processors: the settings set last, and the copies the beam search / sampling run begun last keeps
+  ProcSet lp, bm_lp_set, sp_lp;
   // lang scratch (no grad => reused across layers)
   void* kv_all = nullptr; void* dkv_all = nullptr;
   void* logits = nullptr; float *loss_row = nullptr, *inv_n = nullptr, *loss = nullptr;
@@ -1881,6 +1890,62 @@ extern "C" int klab_engine_decode_step(klab_engine* e, int t, const long long* p
   return decode_rows(e, c, t, prev_tokens, r);
 }
 
+// ---- logits processors (HF's RepetitionPenalty, NoRepeatNGram, NoBadWords, MinLength, MinNewTokensLength) ------------------
+namespace {
+// the processors' part of a sample / beam workspace: the processed f32 rows [M, V] and the bad-words table (nothing when off)
+void take_proc(Bump& b, const ProcSet& lp, long M, long V, float*& proc, int*& table) {
+  proc = nullptr; table = nullptr;
+  if (!lp.on) return;
+  proc = (float*)b.take(M * V * 4);
+  if (!lp.table.empty()) table = (int*)b.take(lp.table.size() * 4);
+}
+// the bad-words table into the workspace (at begin; the run's own copy of the settings holds the host data)
+int upload_proc(const ProcSet& lp, int* table, hipStream_t s) {
+  if (!lp.on || lp.table.empty()) return 0;
+  return (int)hipMemcpyAsync(table, lp.table.data(), lp.table.size() * 4, hipMemcpyHostToDevice, s);
+}
+klab_logits_proc_args proc_args(const ProcSet& lp, const int* table, int dtype, const void* logits, long ld, int row_div, int rows, int V,
+                                long long* seq, long ld_seq, int cur_len, int start_id, int eos_id) {
+  klab_logits_proc_args a;
+  memset(&a, 0, sizeof(a));
+  a.dtype = dtype; a.logits = logits; a.ld = ld; a.row_div = row_div; a.rows = rows; a.V = V;
+  a.seq = seq; a.ld_seq = ld_seq; a.cur_len = cur_len; a.start_id = start_id;
+  a.repetition_penalty = lp.cfg.repetition_penalty; a.no_repeat_ngram_size = lp.cfg.no_repeat_ngram_size;
+  a.min_length = lp.cfg.min_length; a.min_new_tokens = lp.cfg.min_new_tokens; a.eos_id = eos_id;
+  a.n_bad = lp.cfg.n_bad;
+  if (table) { a.bad_off = table; a.bad_tok = table + lp.cfg.n_bad + 1; }
+  return a;
+}
+}  // namespace
+
+extern "C" int klab_engine_set_logits_processors(klab_engine* e, const klab_logits_proc_cfg* cfg) {
+  if (!e) return KLAB_ERR_BADARG;
+  if (!cfg) {
+    e->lp = ProcSet();
+    return 0;
+  }
+  const int n = cfg->n_bad;
+  if (!(cfg->repetition_penalty > 0.f) || cfg->no_repeat_ngram_size < 0 || cfg->min_length < 0 || cfg->min_new_tokens < 0 || n < 0 ||
+      (n > 0 && (!cfg->bad_off || !cfg->bad_tok || cfg->bad_off[0] != 0)))
+    return KLAB_ERR_BADARG;
+  ProcSet lp;
+  lp.on = true;
+  lp.cfg = *cfg;
+  lp.cfg.bad_off = nullptr; lp.cfg.bad_tok = nullptr;
+  if (n > 0) {
+    for (int i = 0; i < n; ++i)
+      if (cfg->bad_off[i + 1] <= cfg->bad_off[i]) return KLAB_ERR_BADARG;  // empty entry
+    const int nt = cfg->bad_off[n];
+    if (nt > 1024) return KLAB_ERR_UNSUPPORTED;
+    for (int i = 0; i < nt; ++i)
+      if (cfg->bad_tok[i] < 0 || cfg->bad_tok[i] >= e->cfg.main.vocab) return KLAB_ERR_BADARG;
+    lp.table.assign(cfg->bad_off, cfg->bad_off + n + 1);
+    lp.table.insert(lp.table.end(), cfg->bad_tok, cfg->bad_tok + nt);
+  }
+  e->lp = std::move(lp);
+  return 0;
+}
+
 // ---- beam search (HF `_beam_search`): a workspace of its own, owned by the caller ------------------------------------------
 namespace {
 struct BeamWs {
@@ -1888,8 +1953,9 @@ struct BeamWs {
   int* slot[2]; float *row_score, *cand_score; int *row_idx, *cand_idx;
   long long* prev; int* parent; long long* run_seq[2]; float* run_score; long long* fin_seq[2];
   float* fin_score; int *fin_flag, *fin_len, *unsat, *stop;
+  float* proc = nullptr; int* table = nullptr;  // logits processors only
 };
-size_t plan_beam(const klab_engine* e, int k, int Lm, void* base, BeamWs& w) {
+size_t plan_beam(const klab_engine* e, int k, int Lm, const ProcSet& lp, void* base, BeamWs& w) {
   Bump b(base);
   const klab_t5_cfg& cfg = e->cfg.main;
   const size_t es = e->es;
@@ -1912,6 +1978,7 @@ size_t plan_beam(const klab_engine* e, int k, int Lm, void* base, BeamWs& w) {
   w.prev = (long long*)b.take(M * 8); w.parent = (int*)b.take(M * 4); w.run_score = (float*)b.take(M * 4);
   w.fin_score = (float*)b.take(M * 4); w.fin_flag = (int*)b.take(M * 4); w.fin_len = (int*)b.take(M * 4);
   w.unsat = (int*)b.take((long)e->B * 4); w.stop = (int*)b.take((long)Lm * 4);
+  take_proc(b, lp, M, V, w.proc, w.table);
   return b.off;
 }
 // the update arguments of cur_len c: reads the buffers of parity c+1, writes those of parity c
@@ -1928,27 +1995,43 @@ klab_beam_update_args beam_args(const klab_engine* e, const BeamWs& w, int c) {
   a.prev_tokens = w.prev; a.parent = w.parent; a.stop_word = w.stop;
   return a;
 }
-bool beam_shape_ok(const klab_engine* e, int k, int Lm) {
-  return e && e->bound && k >= 1 && k <= 16 && Lm >= 2 && Lm - 1 <= e->Lt && e->cfg.main.vocab >= 2 * k;
+bool beam_shape_ok(const klab_engine* e, int k, int Lm, const ProcSet& lp) {
+  return e && e->bound && k >= 1 && k <= 16 && Lm >= 2 && Lm - 1 <= e->Lt && e->cfg.main.vocab >= 2 * k &&
+         (!lp.on || (!lp.cfg.pick && e->cfg.main.vocab <= 32768));
+}
+// the 2k candidates of every sample from logits rows r / row_div (through the processors when the search has them)
+int beam_topk_pos(klab_engine* e, const Ctx& c, const BeamWs& w, const void* logits, long ld, int row_div, int cur_len) {
+  const int k = e->bm_k, B = e->B, V = e->cfg.main.vocab;
+  if (!e->bm_lp_set.on)
+    return klab_beam_topk(c.dt, logits, ld, row_div, w.run_score, B, k, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws());
+  // HF's `_beam_search` hands log_softmax(logits) to the processors; each beam's history is its running sequence (parity c + 1)
+  klab_logits_proc_args a = proc_args(e->bm_lp_set, w.table, c.dt, logits, ld, row_div, B * k, V, w.run_seq[(cur_len + 1) & 1], e->bm_len,
+                                      cur_len, e->cfg.main.start_id, e->bm_eos);
+  a.log_softmax = 1;
+  a.out = w.proc; a.ld_out = V;
+  RC(klab_logits_process_rows(&a, c.ws()));
+  return klab_beam_topk_scores(w.proc, V, 1, w.run_score, B, k, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws());
 }
 }  // namespace
 
 extern "C" size_t klab_engine_beam_workspace_bytes(klab_engine* e, int num_beams, int max_length) {
-  if (!beam_shape_ok(e, num_beams, max_length)) return 0;
+  if (!beam_shape_ok(e, num_beams, max_length, e->lp)) return 0;
   BeamWs w;
-  return plan_beam(e, num_beams, max_length, nullptr, w);
+  return plan_beam(e, num_beams, max_length, e->lp, nullptr, w);
 }
 
 // Precondition: klab_engine_forward in evaluation mode on this binding (the prefill; its logits row b*Lt is position 0 of sample b)
 extern "C" int klab_engine_beam_begin(klab_engine* e, int num_beams, int max_length, float length_penalty, int early_stopping_mode,
                                       int eos_id, int fill_id, void* ws, void* stream) {
-  if (!beam_shape_ok(e, num_beams, max_length) || !ws || early_stopping_mode < 0 || early_stopping_mode > 2) return KLAB_ERR_BADARG;
+  if (!beam_shape_ok(e, num_beams, max_length, e->lp) || !ws || early_stopping_mode < 0 || early_stopping_mode > 2) return KLAB_ERR_BADARG;
   Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
   const klab_t5_cfg& cfg = e->cfg.main;
   const int k = num_beams, Lm = max_length, B = e->B, V = cfg.vocab, inner = cfg.n_heads * cfg.d_kv;
   e->bm_k = k; e->bm_len = Lm; e->bm_mode = early_stopping_mode; e->bm_eos = eos_id; e->bm_lp = length_penalty; e->bm_cur = 0;
+  e->bm_lp_set = e->lp;
   BeamWs w;
-  plan_beam(e, k, Lm, ws, w);
+  plan_beam(e, k, Lm, e->bm_lp_set, ws, w);
+  RC(upload_proc(e->bm_lp_set, w.table, c.s));
   klab_beam_update_args a = beam_args(e, w, 1);
   RC(klab_beam_init(&a, cfg.start_id, fill_id, c.ws()));
   // position 0 (the start token) of every beam: the prefill's self q|k|v row of its sample, copied into the beam's own slot
@@ -1956,7 +2039,7 @@ extern "C" int klab_engine_beam_begin(klab_engine* e, int num_beams, int max_len
     RC(klab_beam_copy_rows((int)e->es, e->dec.L[i].qkv, (long)e->Lt * 3 * inner, k, eoff(c, w.rows.cache, (long)i * w.rows.cache_layer),
                            (long)Lm * 3 * inner, B * k, 3 * inner, c.ws()));
   // HF's first step (cur_len 1) on the prefill's position-0 logits, shared by the k beams of a sample
-  RC(klab_beam_topk(c.dt, e->logits, (long)e->Lt * V, k, w.run_score, B, k, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws()));
+  RC(beam_topk_pos(e, c, w, e->logits, (long)e->Lt * V, k, 1));
   RC(klab_beam_update(&a, 1, c.ws()));
   e->bm_cur = 1;
   return 0;
@@ -1964,16 +2047,17 @@ extern "C" int klab_engine_beam_begin(klab_engine* e, int num_beams, int max_len
 
 // the decoder over position t for every beam (inputs: the tokens the last update chose), then top-2k and the update at cur_len t+1
 extern "C" int klab_engine_beam_step(klab_engine* e, int t, void* ws, void* stream) {
-  if (!e || !e->bound || !ws || e->bm_k < 1 || t < 1 || t != e->bm_cur || t > e->bm_len - 2 || !beam_shape_ok(e, e->bm_k, e->bm_len))
+  if (!e || !e->bound || !ws || e->bm_k < 1 || t < 1 || t != e->bm_cur || t > e->bm_len - 2 ||
+      !beam_shape_ok(e, e->bm_k, e->bm_len, e->bm_lp_set))
     return KLAB_ERR_BADARG;
   Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
-  const int k = e->bm_k, B = e->B, V = e->cfg.main.vocab;
+  const int k = e->bm_k, V = e->cfg.main.vocab;
   BeamWs w;
-  plan_beam(e, k, e->bm_len, ws, w);
+  plan_beam(e, k, e->bm_len, e->bm_lp_set, ws, w);
   DecodeRows r = w.rows;
   r.kv_slot = w.slot[t & 1];
   RC(decode_rows(e, c, t, w.prev, r));
-  RC(klab_beam_topk(c.dt, r.logits, V, 1, w.run_score, B, k, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws()));
+  RC(beam_topk_pos(e, c, w, r.logits, V, 1, t + 1));
   klab_beam_update_args a = beam_args(e, w, t + 1);
   RC(klab_beam_update(&a, t + 1, c.ws()));
   e->bm_cur = t + 1;
@@ -1983,7 +2067,7 @@ extern "C" int klab_engine_beam_step(klab_engine* e, int t, void* ws, void* stre
 extern "C" const int* klab_engine_beam_stop_word(klab_engine* e, void* ws, int cur_len) {
   if (!e || !ws || e->bm_k < 1 || cur_len < 1 || cur_len >= e->bm_len) return nullptr;
   BeamWs w;
-  plan_beam(e, e->bm_k, e->bm_len, ws, w);
+  plan_beam(e, e->bm_k, e->bm_len, e->bm_lp_set, ws, w);
   return w.stop + cur_len;
 }
 
@@ -1992,7 +2076,7 @@ extern "C" int klab_engine_beam_result(klab_engine* e, void* ws, int num_return_
   const int n = num_return_sequences;
   if (!e || !ws || e->bm_cur < 1 || n < 1 || n > e->bm_k || !seq || !scores || !len) return KLAB_ERR_BADARG;
   BeamWs w;
-  plan_beam(e, e->bm_k, e->bm_len, ws, w);
+  plan_beam(e, e->bm_k, e->bm_len, e->bm_lp_set, ws, w);
   const size_t Lm = e->bm_len, k = e->bm_k, B = e->B;
   hipStream_t s = (hipStream_t)stream;
   hipError_t rc = hipMemcpy2DAsync(seq, n * Lm * 8, w.fin_seq[e->bm_cur & 1], k * Lm * 8, n * Lm * 8, B, hipMemcpyDeviceToDevice, s);
@@ -2006,8 +2090,9 @@ namespace {
 struct SampleWs {
   DecodeRows rows;
   long long *seq, *prev; int *done, *stop;
+  float* proc = nullptr; int* table = nullptr;  // logits processors only
 };
-size_t plan_sample(const klab_engine* e, int n, int Lm, void* base, SampleWs& w) {
+size_t plan_sample(const klab_engine* e, int n, int Lm, const ProcSet& lp, void* base, SampleWs& w) {
   Bump b(base);
   const klab_t5_cfg& cfg = e->cfg.main;
   const size_t es = e->es;
@@ -2022,16 +2107,32 @@ size_t plan_sample(const klab_engine* e, int n, int Lm, void* base, SampleWs& w)
   r.kv_group = n;  // (kv_slot NULL: row r's self-attention keys are its own slot r)
   w.seq = (long long*)b.take(M * Lm * 8); w.prev = (long long*)b.take(M * 8);
   w.done = (int*)b.take(M * 4); w.stop = (int*)b.take((long)Lm * 4);
+  if (!lp.cfg.pick) take_proc(b, lp, M, V, w.proc, w.table);  // (greedy's pick writes no processed rows)
+  else if (!lp.table.empty()) w.table = (int*)b.take(lp.table.size() * 4);
   return b.off;
 }
 bool sample_shape_ok(const klab_engine* e, int n, int Lm) {
   return e && e->bound && n >= 1 && Lm >= 2 && Lm - 1 <= e->Lt && e->cfg.main.vocab <= 32768;
 }
-// one klab_sample_rows for position pos over the B*n rows (logits row r / row_div)
+// one klab_sample_rows for position pos over the B*n rows (logits row r / row_div), behind the processors when the run has them
+// (HF's `_sample`: processors, then the warpers); greedy's pick replaces the draw
 int sample_pos(klab_engine* e, const Ctx& c, const SampleWs& w, const void* logits, long ld, int row_div, int pos) {
+  int dt = c.dt;
+  if (e->sp_lp.on) {
+    const int V = e->cfg.main.vocab;
+    klab_logits_proc_args p = proc_args(e->sp_lp, w.table, c.dt, logits, ld, row_div, e->B * e->sp_n, V, w.seq, e->sp_len, pos,
+                                        e->cfg.main.start_id, e->sp_eos);
+    if (e->sp_lp.cfg.pick) {
+      p.pick = 1; p.done = w.done; p.pad_id = e->sp_pad; p.tokens = w.prev; p.stop_word = w.stop + pos;
+      return klab_logits_process_rows(&p, c.ws());
+    }
+    p.out = w.proc; p.ld_out = V;
+    RC(klab_logits_process_rows(&p, c.ws()));
+    dt = KLAB_F32; logits = w.proc; ld = V; row_div = 1;
+  }
   klab_sample_args a;
   memset(&a, 0, sizeof(a));
-  a.dtype = c.dt; a.logits = logits; a.ld = ld; a.row_div = row_div;
+  a.dtype = dt; a.logits = logits; a.ld = ld; a.row_div = row_div;
   a.rows = e->B * e->sp_n; a.V = e->cfg.main.vocab;
   a.temperature = e->sp_temp; a.top_k = e->sp_topk; a.top_p = e->sp_topp;
   a.seed = e->sp_seed; a.step = pos;
@@ -2044,7 +2145,7 @@ int sample_pos(klab_engine* e, const Ctx& c, const SampleWs& w, const void* logi
 extern "C" size_t klab_engine_sample_workspace_bytes(klab_engine* e, int num_return_sequences, int max_length) {
   if (!sample_shape_ok(e, num_return_sequences, max_length)) return 0;
   SampleWs w;
-  return plan_sample(e, num_return_sequences, max_length, nullptr, w);
+  return plan_sample(e, num_return_sequences, max_length, e->lp, nullptr, w);
 }
 
 // Precondition: klab_engine_forward in evaluation mode on this binding (the prefill; its logits row b*Lt is position 0 of sample b)
@@ -2057,8 +2158,10 @@ extern "C" int klab_engine_sample_begin(klab_engine* e, int num_return_sequences
   const int n = num_return_sequences, Lm = max_length, B = e->B, V = cfg.vocab, inner = cfg.n_heads * cfg.d_kv;
   e->sp_n = n; e->sp_len = Lm; e->sp_temp = temperature; e->sp_topk = top_k; e->sp_topp = top_p; e->sp_seed = seed;
   e->sp_eos = eos_id; e->sp_pad = pad_id; e->sp_cur = 0;
+  e->sp_lp = e->lp;
   SampleWs w;
-  plan_sample(e, n, Lm, ws, w);
+  plan_sample(e, n, Lm, e->sp_lp, ws, w);
+  RC(upload_proc(e->sp_lp, w.table, c.s));
   RC((int)hipMemsetAsync(w.done, 0, (size_t)B * n * 4, c.s));
   RC((int)hipMemsetAsync(w.stop, 0, (size_t)Lm * 4, c.s));
   // position 0 (the start token) of every row: the prefill's self q|k|v row of its image, copied into the row's own slot
@@ -2077,7 +2180,7 @@ extern "C" int klab_engine_sample_step(klab_engine* e, int t, void* ws, void* st
     return KLAB_ERR_BADARG;
   Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
   SampleWs w;
-  plan_sample(e, e->sp_n, e->sp_len, ws, w);
+  plan_sample(e, e->sp_n, e->sp_len, e->sp_lp, ws, w);
   RC(decode_rows(e, c, t, w.prev, w.rows));
   RC(sample_pos(e, c, w, w.rows.logits, e->cfg.main.vocab, 1, t + 1));
   e->sp_cur = t + 1;
@@ -2087,14 +2190,14 @@ extern "C" int klab_engine_sample_step(klab_engine* e, int t, void* ws, void* st
 extern "C" const int* klab_engine_sample_stop_word(klab_engine* e, void* ws, int pos) {
   if (!e || !ws || e->sp_n < 1 || pos < 1 || pos >= e->sp_len) return nullptr;
   SampleWs w;
-  plan_sample(e, e->sp_n, e->sp_len, ws, w);
+  plan_sample(e, e->sp_n, e->sp_len, e->sp_lp, ws, w);
   return w.stop + pos;
 }
 
 extern "C" int klab_engine_sample_result(klab_engine* e, void* ws, long long* seq, int length, void* stream) {
   if (!e || !ws || e->sp_cur < 1 || !seq || length < 1 || length > e->sp_cur + 1) return KLAB_ERR_BADARG;
   SampleWs w;
-  plan_sample(e, e->sp_n, e->sp_len, ws, w);
+  plan_sample(e, e->sp_n, e->sp_len, e->sp_lp, ws, w);
   const size_t Lm = e->sp_len, rows = (size_t)e->B * e->sp_n;
   return (int)hipMemcpy2DAsync(seq, (size_t)length * 8, w.seq, Lm * 8, (size_t)length * 8, rows, hipMemcpyDeviceToDevice, (hipStream_t)stream);
 }

@@ -128,6 +128,7 @@ ENGINE_SIGS = {
     "klab_engine_sample_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_sample_stop_word": ([C.c_void_p, C.c_void_p, C.c_int], C.c_void_p),
     "klab_engine_sample_result": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
+    "klab_engine_set_logits_processors": ([C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_backward": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_set_graph": ([C.c_void_p, C.c_int], C.c_int),
     "klab_engine_get_rng": ([C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p], C.c_int),
@@ -431,6 +432,25 @@ class Engine:
         L.check(self._lib.klab_engine_sample_result(self._h, ws.data_ptr(), seq.data_ptr(), int(length), L.stream_ptr()),
                 "klab_engine_sample_result")
         return seq
+
+    # ---- logits processors (HF's repetition penalty, n-gram ban, bad words, min length) for the sample / beam entry points ------
+    def set_logits_processors(self, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=(), min_length=0, min_new_tokens=0,
+                              pick=False, clear=False):
+        """the processor settings of the next sample_begin / beam_begin (clear=True: none, the default state); pick=True: greedy
+        decoding through the sampling entry points, the processed arg-max replacing the draw"""
+        if clear:
+            L.check(self._lib.klab_engine_set_logits_processors(self._h, None), "klab_engine_set_logits_processors")
+            return
+        words = [list(map(int, w)) for w in bad_words_ids]
+        off = [0]
+        for w in words:
+            off.append(off[-1] + len(w))
+        toks = [t for w in words for t in w]
+        off_a = (C.c_int * len(off))(*off)
+        tok_a = (C.c_int * max(1, len(toks)))(*toks)
+        cfg = L.LogitsProcCfg(float(repetition_penalty), int(no_repeat_ngram_size), int(min_length), int(min_new_tokens), len(words),
+                              C.cast(off_a, C.POINTER(C.c_int)), C.cast(tok_a, C.POINTER(C.c_int)), int(bool(pick)))
+        L.check(self._lib.klab_engine_set_logits_processors(self._h, C.byref(cfg)), "klab_engine_set_logits_processors")
 
     def backward(self, segment, dloss=None):
         L.check(self._lib.klab_engine_backward(self._h, segment, dloss.data_ptr() if dloss is not None else None, L.stream_ptr()),

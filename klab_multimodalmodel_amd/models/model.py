@@ -16,6 +16,7 @@ from torch import nn
 
 from .. import hf_io
 from ..engine import Engine, SwinConfig, T5Config
+from ..logits_proc import logits_processor_settings
 
 TIED_T5 = ("encoder.embed_tokens.weight", "decoder.embed_tokens.weight", "lm_head.weight")  # HF/t5:902-906
 
@@ -367,14 +368,23 @@ class MyModel(nn.Module):
 
     @torch.no_grad()
     def generate(self, pixels, src, max_length=20, kv_cache=True, num_beams=1, length_penalty=1.0, early_stopping=False,
-                 num_return_sequences=1, return_scores=False, do_sample=False, temperature=1.0, top_k=50, top_p=1.0):
+                 num_return_sequences=1, return_scores=False, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
+                 repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_length=0, min_new_tokens=None):
         """greedy decoding with HF's default generation settings (ref/models/model.py:28: max_length 20, no sampling).
         Prefill = one evaluation-mode forward (Swin, both encoders, the cross K/V of all layers, decoder position 0); every
         further token runs the decoder over ONE new position against the per-layer K/V cache (`klab_engine_decode_step`,
         SURVEY §8 row f-3; HF/t5:308-332).  kv_cache=False keeps the round-1 form -- decoder + LM head over the whole prefix per
         token -- as the cross-check of the cache.
         num_beams > 1: HF's beam search (`_beam_search`, `generate(num_beams=...)`) on the device -- see _generate_beam.
-        do_sample=True: HF's `_sample` with temperature -> top-k -> top-p on the device -- see _generate_sample."""
+        do_sample=True: HF's `_sample` with temperature -> top-k -> top-p on the device -- see _generate_sample.
+        repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens: HF's logits processors with HF's
+        names, defaults and checks (logits_proc.logits_processor_settings), in front of all three loops as in HF: on the fp32
+        logits for greedy and sampling (before the warpers), on log_softmax(logits) for beam search; the history is the decoder
+        sequence with its start token.  One `klab_logits_process_rows` per step (csrc/logits_proc.hip); greedy decoding with
+        processors runs through the sampling entry points, the processed arg-max replacing the draw.  With none of them active
+        every path runs as without them."""
+        procs = logits_processor_settings(repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens,
+                                          eos_token_id=self.main_cfg.eos_token_id, vocab_size=self.main_cfg.vocab_size)
         if do_sample:
             if num_beams > 1:
                 raise NotImplementedError("beam sampling (do_sample=True with num_beams > 1) is not supported")
@@ -391,16 +401,22 @@ class MyModel(nn.Module):
                 raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
             if num_return_sequences < 1:
                 raise ValueError(f"`num_return_sequences` has to be a positive integer, but is {num_return_sequences}")
-            return self._generate_sample(pixels, src, max_length, num_return_sequences, float(temperature), int(top_k), float(top_p))
+            return self._generate_sample(pixels, src, max_length, num_return_sequences, float(temperature), int(top_k), float(top_p),
+                                         procs)
         if num_return_sequences > num_beams:
             raise ValueError(f"`num_return_sequences` ({num_return_sequences}) has to be smaller or equal to `num_beams` ({num_beams}).")
         if num_beams > 1:
             if not kv_cache:
                 raise ValueError("beam search runs on the K/V cache only: kv_cache=False needs num_beams=1")
             return self._generate_beam(pixels, src, max_length, num_beams, length_penalty, early_stopping, num_return_sequences,
-                                       return_scores)
+                                       return_scores, procs)
         if return_scores:
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence scores)")
+        if procs is not None:
+            if not kv_cache:
+                raise ValueError("logits processors run on the K/V cache only: repetition_penalty, no_repeat_ngram_size, bad_words_ids, "
+                                 "min_length and min_new_tokens need kv_cache=True")
+            return self._generate_sample(pixels, src, max_length, 1, 1.0, 0, 1.0, procs, pick=True)
         B = src.shape[0]
         cfg = self.main_cfg
         steps = max_length - 1
@@ -430,11 +446,13 @@ class MyModel(nn.Module):
         start = torch.full((B, 1), cfg.decoder_start_token_id, dtype=torch.int64, device=src.device)
         return torch.cat([start, tgt], dim=1)
 
-    def _generate_beam(self, pixels, src, max_length, num_beams, length_penalty, early_stopping, num_return_sequences, return_scores):
+    def _generate_beam(self, pixels, src, max_length, num_beams, length_penalty, early_stopping, num_return_sequences, return_scores,
+                       procs=None):
         """One prefill at B rows (Swin, both encoders and the cross K/V run once per sample, not per beam), then the beam state
         lives on the device: every step is the decoder over B*num_beams rows, top-2k and HF's bookkeeping
         (`klab_engine_beam_step`); the host reads one stop word per step.  Returns [B*num_return_sequences, L] int64 (start
-        token, pads after EOS, cropped to the longest returned hypothesis), and its scores when return_scores."""
+        token, pads after EOS, cropped to the longest returned hypothesis), and its scores when return_scores.  procs: the logits
+        processors' settings (logits_proc.logits_processor_settings), set on the engine for this call only."""
         if early_stopping not in (False, True, "never"):
             raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
         if max_length < 2:
@@ -447,9 +465,12 @@ class MyModel(nn.Module):
         fill = cfg.pad_token_id or cfg.eos_token_id
         was_training = self.transformer.training
         self.transformer.eval()
+        eng = None
         try:
             eng = self._engine_for(pixels, src, tgt)
             eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
+            if procs is not None:
+                eng.set_logits_processors(**procs)
             nbytes = eng.beam_workspace_bytes(k, max_length)
             if nbytes == 0:
                 raise ValueError(f"beam search: unsupported num_beams={k} / max_length={max_length} for this model")
@@ -464,28 +485,35 @@ class MyModel(nn.Module):
                 cur += 1
             seq, scores, lens = eng.beam_result(ws, num_return_sequences, max_length)
         finally:
+            if procs is not None and eng is not None:
+                eng.set_logits_processors(clear=True)
             self.transformer.train(was_training)
         seq = seq[:, :1 + int(lens.max())]
         return (seq, scores) if return_scores else seq
 
-    def _generate_sample(self, pixels, src, max_length, num_return_sequences, temperature, top_k, top_p):
+    def _generate_sample(self, pixels, src, max_length, num_return_sequences, temperature, top_k, top_p, procs=None, pick=False):
         """One prefill at B rows, then B*n rows (row b*n + j: sample j of image b, HF's `_expand_inputs_for_generation`) on the
         device: every step is the decoder over B*n rows and one sampling kernel that applies HF's warpers, draws, and does
         greedy's bookkeeping (`klab_engine_sample_step`); the host reads one stop word per step.  The draws come from a counter
         hash of one 64-bit seed taken from torch's default CPU generator per call (torch.manual_seed reproduces a call).
-        Returns [B*n, L] int64: start token, pad after EOS, cropped when every row is done."""
+        Returns [B*n, L] int64: start token, pad after EOS, cropped when every row is done.  procs: the logits processors'
+        settings, applied before the warpers and set on the engine for this call only; pick=True (with procs, n = 1): greedy
+        decoding, the processed arg-max instead of a draw (no seed is taken)."""
         if max_length < 2:
             raise ValueError("max_length must count the start token and at least one generated token")
         B = src.shape[0]
         cfg = self.main_cfg
         n = int(num_return_sequences)
-        seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (), dtype=torch.int64)) & 0xFFFFFFFFFFFFFFFF
+        seed = 0 if pick else int(torch.randint(-2 ** 63, 2 ** 63 - 1, (), dtype=torch.int64)) & 0xFFFFFFFFFFFFFFFF
         tgt = torch.full((B, max_length - 1), cfg.pad_token_id, dtype=torch.int64, device=src.device)
         was_training = self.transformer.training
         self.transformer.eval()
+        eng = None
         try:
             eng = self._engine_for(pixels, src, tgt)
             eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
+            if procs is not None:
+                eng.set_logits_processors(**procs, pick=pick)
             nbytes = eng.sample_workspace_bytes(n, max_length)
             if nbytes == 0:
                 raise ValueError(f"sampling: unsupported num_return_sequences={n} / max_length={max_length} for this model")
@@ -497,6 +525,8 @@ class MyModel(nn.Module):
                 cur += 1
             seq = eng.sample_result(ws, B * n, cur + 1)
         finally:
+            if procs is not None and eng is not None:
+                eng.set_logits_processors(clear=True)
             self.transformer.train(was_training)
         return seq
 
