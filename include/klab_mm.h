@@ -487,23 +487,6 @@ int klab_beam_init(const klab_beam_update_args* a, int start_id, int fill_id, vo
 /* dst row r = src row r / src_div (elem_bytes 2, 4 or 8; element strides) */
 int klab_beam_copy_rows(int elem_bytes, const void* src, long src_ld, int src_div, void* dst, long dst_ld, int rows, int cols,
                         void* stream);
-/* Beam-search generation on an engine binding.  The workspace (klab_engine_beam_workspace_bytes) is caller-owned and separate from
- * the binding's: decoder scratch for B*k rows, the per-layer self-attention cache [B*k*max_length, 3*inner], the beam logits
- * [B*k, V], the key-slot tables and the beam state.
- * beam_begin: after a klab_engine_forward in evaluation mode at B rows with Lt >= max_length - 1; copies position 0's self K/V
- *   into every beam's cache slot, initialises the state and runs HF's first step (cur_len 1) on the prefill's logits.
- *   fill_id: HF's output fill value (pad_token_id, or eos when that is 0).
- * beam_step(t): the decoder over position t (1 <= t <= max_length - 2) for all B*k beams, then top-2k and the update at
- *   cur_len t + 1.  Three launches beyond klab_engine_decode_step's chain.
- * beam_stop_word: device address of the stop word of cur_len (read after the step; see klab_beam_update).
- * beam_result: the first n of each sample's finished pool (sorted by score): seq [B*n, max_length] int64, scores [B*n] f32,
- *   len [B*n] int32 (generated tokens, the start token excluded).                                                          */
-size_t klab_engine_beam_workspace_bytes(klab_engine* e, int num_beams, int max_length);
-int klab_engine_beam_begin(klab_engine* e, int num_beams, int max_length, float length_penalty, int early_stopping_mode, int eos_id,
-                           int fill_id, void* ws, void* stream);
-int klab_engine_beam_step(klab_engine* e, int t, void* ws, void* stream);
-const int* klab_engine_beam_stop_word(klab_engine* e, void* ws, int cur_len);
-int klab_engine_beam_result(klab_engine* e, void* ws, int num_return_sequences, long long* seq, float* scores, int* len, void* stream);
 
 /* ---- sampling (HF `_sample` with temperature -> top-k -> top-p; csrc/sample.hip) ------------------------------------------
  * klab_sample_rows: one drawn token per row r < rows from logits row (r / row_div) (element stride ld), V <= 32768
@@ -530,22 +513,6 @@ typedef struct {
   int* stop_word;
 } klab_sample_args;
 int klab_sample_rows(const klab_sample_args* a, void* stream);
-/* Sampling generation on an engine binding, the beam pattern at B*n rows (row b*n + j = sample j of image b, HF's
- * `_expand_inputs_for_generation`).  The workspace (klab_engine_sample_workspace_bytes) is caller-owned and separate from the
- * binding's: decoder scratch and logits for B*n rows, the per-layer self-attention cache [B*n*max_length, 3*inner] (row r reads
- * its own slot), the sequences [B*n, max_length] int64, the next decoder inputs, the done flags and the stop words.
- * sample_begin: after a klab_engine_forward in evaluation mode at B rows with Lt >= max_length - 1; copies position 0's self K/V
- *   into every row's slot and samples position 1 from the prefill's position-0 logits (the n rows of an image share them).
- * sample_step(t): the decoder over position t (1 <= t <= max_length - 2) for all B*n rows (cross-attention K/V shared by the n
- *   rows of an image), then one klab_sample_rows for position t + 1.
- * sample_stop_word: device address of the stop word of position pos (1 while some row is unfinished after sampling pos).
- * sample_result: the first `length` columns of the sequences into seq [B*n, length] int64.                                 */
-size_t klab_engine_sample_workspace_bytes(klab_engine* e, int num_return_sequences, int max_length);
-int klab_engine_sample_begin(klab_engine* e, int num_return_sequences, int max_length, float temperature, int top_k, float top_p,
-                             unsigned long long seed, int eos_id, int pad_id, void* ws, void* stream);
-int klab_engine_sample_step(klab_engine* e, int t, void* ws, void* stream);
-const int* klab_engine_sample_stop_word(klab_engine* e, void* ws, int pos);
-int klab_engine_sample_result(klab_engine* e, void* ws, long long* seq, int length, void* stream);
 
 /* ---- logits processors (HF's RepetitionPenalty, NoRepeatNGram, NoBadWords, MinLength, MinNewTokensLength, in that order;
  * csrc/logits_proc.hip) --------------------------------------------------------------------------------------------------
@@ -576,18 +543,54 @@ int klab_logits_process_rows(const klab_logits_proc_args* a, void* stream);
  * log_softmax): per sample b, the 2k best of  scores row b*k+j + run_score[b*k+j], same order, ties and buffers.           */
 int klab_beam_topk_scores(const float* scores, long ld, int row_div, const float* run_score, int B, int k, int V, float* row_score,
                           int* row_idx, float* out_score, int* out_idx, void* stream);
-/* Processor settings of an engine binding (host memory; bad_off / bad_tok are copied): NULL = none, the default.  When set, the
- * sample and beam workspaces grow by an f32 [rows, vocab] buffer and the bad-words table, and every sample / beam begin and step
- * runs klab_logits_process_rows before the sampler or the top-2k.  pick != 0 (sampling entry points only): greedy decoding --
- * the processed arg-max replaces the draw (temperature, top_k, top_p and seed are then ignored).  A begun search keeps the
- * settings it began with.  KLAB_ERR_BADARG for penalty <= 0, negative sizes, empty entries or ids >= vocab;
- * KLAB_ERR_UNSUPPORTED for more than 1024 bad-word tokens in all.                                                         */
+/* Logits-processor settings of a decoding session (host memory; bad_off / bad_tok are copied at klab_engine_gen_begin).
+ * KLAB_ERR_BADARG for penalty <= 0, negative sizes, empty entries or ids >= vocab; KLAB_ERR_UNSUPPORTED for more than 1024
+ * bad-word tokens in all.                                                                                                 */
 typedef struct {
   float repetition_penalty; int no_repeat_ngram_size, min_length, min_new_tokens;
   int n_bad; const int* bad_off; const int* bad_tok;
-  int pick;
 } klab_logits_proc_cfg;
-int klab_engine_set_logits_processors(klab_engine* e, const klab_logits_proc_cfg* cfg);
+
+/* ---- decoding sessions on an engine binding: HF's `_beam_search`, `_sample`, and greedy decoding behind the processors ----
+ * One prefill at B rows, then M = B*n rows on the device (row b*n + j: beam / sample j of image b, HF's
+ * `_expand_inputs_for_generation`; the n rows of an image share its cross-attention K/V).  The workspace
+ * (klab_engine_gen_workspace_bytes; 0 = unsupported settings) is caller-owned and separate from the binding's: decoder scratch
+ * and logits for M rows, the per-layer self-attention cache [M*max_length, 3*inner], the mode's state, the next decoder inputs
+ * and the stop words; with processors also an f32 [M, vocab] buffer (not for pick) and the bad-words table.
+ * mode KLAB_GEN_BEAM: n = num_beams <= 16, vocab >= 2n; pad_id = HF's output fill value (pad_token_id, or eos when that is 0);
+ *   early_stopping 0 False, 1 True, 2 "never"; length_penalty.  Each position: klab_beam_topk (with processors:
+ *   klab_logits_process_rows on log_softmax(logits), then klab_beam_topk_scores) and klab_beam_update.  Beam r's self-attention
+ *   keys are in the slots of its key-slot table.
+ * mode KLAB_GEN_SAMPLE: n = num_return_sequences; temperature > 0, top_k >= 0, 0 <= top_p <= 1, seed.  Each position: the
+ *   processors when set (f32 rows), then klab_sample_rows.
+ * mode KLAB_GEN_PICK: greedy decoding, one klab_logits_process_rows with pick per position (procs NULL: neutral settings).
+ * The processors (procs, NULL = none) need vocab <= 32768, as do sampling and pick.  A begun session keeps the settings it
+ * began with; beginning another ends it.
+ * gen_begin: after a klab_engine_forward in evaluation mode at B rows with Lt >= max_length - 1; copies position 0's self
+ *   K/V into every row's cache slot, initialises the mode's state and chooses position 1 (HF's first step, cur_len 1) from the
+ *   prefill's position-0 logits.
+ * gen_step(t): the decoder over position t (1 <= t <= max_length - 2, in order) for all M rows, then position t + 1.
+ * gen_stop_word: device address of the stop word of position pos, written by the step that chose it.  Beam search goes on iff
+ *   bits 1 and 4 are set and, with early_stopping True, bit 2 (see klab_beam_update); sampling and pick go on while it is
+ *   non-zero (some row unfinished).
+ * gen_result: beam search: the first n <= num_beams of each sample's finished pool (sorted by score), length = max_length:
+ *   seq [B*n, max_length] int64, scores [B*n] f32, len [B*n] int32 (generated tokens, the start token excluded).  Sampling
+ *   and pick: n = the session's n, the first length <= (last position chosen) + 1 columns of the sequences into seq
+ *   [B*n, length] int64 (start token, pad_id after EOS); scores and len unused (NULL).                                    */
+#define KLAB_GEN_PICK 0
+#define KLAB_GEN_SAMPLE 1
+#define KLAB_GEN_BEAM 2
+typedef struct {
+  int mode, n, max_length, eos_id, pad_id;
+  float temperature; int top_k; float top_p; unsigned long long seed; /* sampling only */
+  float length_penalty; int early_stopping;                           /* beam search only */
+  const klab_logits_proc_cfg* procs;
+} klab_gen_cfg;
+size_t klab_engine_gen_workspace_bytes(klab_engine* e, const klab_gen_cfg* cfg);
+int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, void* ws, void* stream);
+int klab_engine_gen_step(klab_engine* e, int t, void* ws, void* stream);
+const int* klab_engine_gen_stop_word(klab_engine* e, void* ws, int pos);
+int klab_engine_gen_result(klab_engine* e, void* ws, int n, int length, long long* seq, float* scores, int* len, void* stream);
 /* segment 0: LM head + decoder + tied embedding; 1: encoder; 2: Swin (no-op unless train_swin).
  * dloss_dev: device scalar d(objective)/d(loss) (NULL = 1).                                       */
 int klab_engine_backward(klab_engine* e, int segment, const float* dloss_dev, void* stream);

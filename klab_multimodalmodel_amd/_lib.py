@@ -78,7 +78,16 @@ class LogitsProcArgs(C.Structure):  # klab_logits_proc_args
 
 class LogitsProcCfg(C.Structure):  # klab_logits_proc_cfg
     _fields_ = [("repetition_penalty", f32), ("no_repeat_ngram_size", i32), ("min_length", i32), ("min_new_tokens", i32),
-                ("n_bad", i32), ("bad_off", C.POINTER(i32)), ("bad_tok", C.POINTER(i32)), ("pick", i32)]
+                ("n_bad", i32), ("bad_off", C.POINTER(i32)), ("bad_tok", C.POINTER(i32))]
+
+
+GEN_PICK, GEN_SAMPLE, GEN_BEAM = 0, 1, 2
+
+
+class GenCfg(C.Structure):  # klab_gen_cfg
+    _fields_ = [("mode", i32), ("n", i32), ("max_length", i32), ("eos_id", i32), ("pad_id", i32),
+                ("temperature", f32), ("top_k", i32), ("top_p", f32), ("seed", C.c_uint64),
+                ("length_penalty", f32), ("early_stopping", i32), ("procs", C.POINTER(LogitsProcCfg))]
 
 
 # every exported entry point of include/klab_mm.h: name -> argtypes (restype is always int)

@@ -81,11 +81,17 @@ struct Bump {
   }
 };
 
-// logits-processor settings (klab_engine_set_logits_processors); table = bad_off [n_bad + 1] then bad_tok, as they go to the device
+// logits-processor settings of a decoding session (neutral when off); table = bad_off [n_bad + 1] then bad_tok, as they go to the device
 struct ProcSet {
   bool on = false;
-  klab_logits_proc_cfg cfg{};
+  klab_logits_proc_cfg cfg{1.f};
   std::vector<int> table;
+};
+// a decoding session: its settings (cfg.procs cleared; the processors live in lp) and the last position it chose (0: none begun)
+struct GenRun {
+  klab_gen_cfg cfg{};
+  ProcSet lp;
+  int cur = 0;
 };
 
 }  // namespace
@@ -138,13 +144,8 @@ struct klab_engine {
   // greedy decoding with a K/V cache (klab_engine_decode_step): one position per sample, contiguous [B, .] rows
   float* dc_h[2] = {nullptr, nullptr}; float* dc_rstd = nullptr;
   void *dc_xn = nullptr, *dc_q = nullptr, *dc_ctx = nullptr, *dc_hmid = nullptr, *dc_out = nullptr, *dc_logits = nullptr;
-  // beam search (klab_engine_beam_*): parameters of the search begun last on this binding, cur_len of its last update
-  int bm_k = 0, bm_len = 0, bm_mode = 0, bm_eos = 1, bm_cur = 0; float bm_lp = 1.f;
-  // sampling (klab_engine_sample_*): parameters of the run begun last on this binding, the last position sampled
-  int sp_n = 0, sp_len = 0, sp_cur = 0, sp_topk = 0, sp_eos = 1, sp_pad = 0; float sp_temp = 1.f, sp_topp = 1.f;
-  unsigned long long sp_seed = 0;
-  // logits processors: the settings set last, and the copies the beam search / sampling run begun last keeps
-  ProcSet lp, bm_lp_set, sp_lp;
+  // the decoding session (klab_engine_gen_*) begun last on this binding
+  GenRun gen;
   // lang scratch (no grad => reused across layers)
   void* kv_all = nullptr; void* dkv_all = nullptr;
   void* logits = nullptr; float *loss_row = nullptr, *inv_n = nullptr, *loss = nullptr;
@@ -1890,45 +1891,18 @@ extern "C" int klab_engine_decode_step(klab_engine* e, int t, const long long* p
   return decode_rows(e, c, t, prev_tokens, r);
 }
 
-// ---- logits processors (HF's RepetitionPenalty, NoRepeatNGram, NoBadWords, MinLength, MinNewTokensLength) ------------------
+// ---- decoding sessions (HF `_beam_search`, `_sample`, greedy behind the logits processors): one prefill at B rows, then B*n rows
+// on the device in a workspace of their own, owned by the caller ----------------------------------------------------------------
 namespace {
-// the processors' part of a sample / beam workspace: the processed f32 rows [M, V] and the bad-words table (nothing when off)
-void take_proc(Bump& b, const ProcSet& lp, long M, long V, float*& proc, int*& table) {
-  proc = nullptr; table = nullptr;
-  if (!lp.on) return;
-  proc = (float*)b.take(M * V * 4);
-  if (!lp.table.empty()) table = (int*)b.take(lp.table.size() * 4);
-}
-// the bad-words table into the workspace (at begin; the run's own copy of the settings holds the host data)
-int upload_proc(const ProcSet& lp, int* table, hipStream_t s) {
-  if (!lp.on || lp.table.empty()) return 0;
-  return (int)hipMemcpyAsync(table, lp.table.data(), lp.table.size() * 4, hipMemcpyHostToDevice, s);
-}
-klab_logits_proc_args proc_args(const ProcSet& lp, const int* table, int dtype, const void* logits, long ld, int row_div, int rows, int V,
-                                long long* seq, long ld_seq, int cur_len, int start_id, int eos_id) {
-  klab_logits_proc_args a;
-  memset(&a, 0, sizeof(a));
-  a.dtype = dtype; a.logits = logits; a.ld = ld; a.row_div = row_div; a.rows = rows; a.V = V;
-  a.seq = seq; a.ld_seq = ld_seq; a.cur_len = cur_len; a.start_id = start_id;
-  a.repetition_penalty = lp.cfg.repetition_penalty; a.no_repeat_ngram_size = lp.cfg.no_repeat_ngram_size;
-  a.min_length = lp.cfg.min_length; a.min_new_tokens = lp.cfg.min_new_tokens; a.eos_id = eos_id;
-  a.n_bad = lp.cfg.n_bad;
-  if (table) { a.bad_off = table; a.bad_tok = table + lp.cfg.n_bad + 1; }
-  return a;
-}
-}  // namespace
-
-extern "C" int klab_engine_set_logits_processors(klab_engine* e, const klab_logits_proc_cfg* cfg) {
-  if (!e) return KLAB_ERR_BADARG;
-  if (!cfg) {
-    e->lp = ProcSet();
-    return 0;
-  }
+// the logits processors of a session (HF's RepetitionPenalty, NoRepeatNGram, NoBadWords, MinLength, MinNewTokensLength) from cfg
+// (NULL: none), checked against this binding
+int make_procs(const klab_engine* e, const klab_logits_proc_cfg* cfg, ProcSet& lp) {
+  lp = ProcSet();
+  if (!cfg) return 0;
   const int n = cfg->n_bad;
   if (!(cfg->repetition_penalty > 0.f) || cfg->no_repeat_ngram_size < 0 || cfg->min_length < 0 || cfg->min_new_tokens < 0 || n < 0 ||
       (n > 0 && (!cfg->bad_off || !cfg->bad_tok || cfg->bad_off[0] != 0)))
     return KLAB_ERR_BADARG;
-  ProcSet lp;
   lp.on = true;
   lp.cfg = *cfg;
   lp.cfg.bad_off = nullptr; lp.cfg.bad_tok = nullptr;
@@ -1942,160 +1916,39 @@ extern "C" int klab_engine_set_logits_processors(klab_engine* e, const klab_logi
     lp.table.assign(cfg->bad_off, cfg->bad_off + n + 1);
     lp.table.insert(lp.table.end(), cfg->bad_tok, cfg->bad_tok + nt);
   }
-  e->lp = std::move(lp);
   return 0;
 }
-
-// ---- beam search (HF `_beam_search`): a workspace of its own, owned by the caller ------------------------------------------
-namespace {
-struct BeamWs {
-  DecodeRows rows;
-  int* slot[2]; float *row_score, *cand_score; int *row_idx, *cand_idx;
-  long long* prev; int* parent; long long* run_seq[2]; float* run_score; long long* fin_seq[2];
-  float* fin_score; int *fin_flag, *fin_len, *unsat, *stop;
-  float* proc = nullptr; int* table = nullptr;  // logits processors only
-};
-size_t plan_beam(const klab_engine* e, int k, int Lm, const ProcSet& lp, void* base, BeamWs& w) {
-  Bump b(base);
-  const klab_t5_cfg& cfg = e->cfg.main;
-  const size_t es = e->es;
-  const long M = (long)e->B * k, d = cfg.d_model, inner = (long)cfg.n_heads * cfg.d_kv, ff = cfg.d_ff, V = cfg.vocab;
-  DecodeRows& r = w.rows;
-  r.M = (int)M;
-  r.h[0] = (float*)b.take(M * d * 4); r.h[1] = (float*)b.take(M * d * 4); r.rstd = (float*)b.take(M * 4);
-  r.xn = b.take(M * d * es); r.q = b.take(M * inner * es); r.ctx = b.take(M * inner * es); r.hmid = b.take(M * ff * es);
-  r.out = b.take(M * d * es); r.logits = b.take(M * V * es);
-  r.cache_layer = M * Lm * 3 * inner; r.cache_rows = Lm;
-  r.cache = b.take((size_t)cfg.n_dec_layers * r.cache_layer * es);
-  r.kv_group = k; r.slot_ld = Lm;
-  for (int p = 0; p < 2; ++p) {
-    w.slot[p] = (int*)b.take(M * Lm * 4);
-    w.run_seq[p] = (long long*)b.take(M * Lm * 8);
-    w.fin_seq[p] = (long long*)b.take(M * Lm * 8);
+bool gen_shape_ok(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp) {
+  if (!e->bound || g.n < 1 || g.max_length < 2 || g.max_length - 1 > e->Lt) return false;
+  const int V = e->cfg.main.vocab;
+  switch (g.mode) {
+    case KLAB_GEN_BEAM:
+      return g.n <= 16 && V >= 2 * g.n && (!lp.on || V <= 32768) && g.early_stopping >= 0 && g.early_stopping <= 2;
+    case KLAB_GEN_SAMPLE:
+      return V <= 32768 && g.temperature > 0.f && g.top_k >= 0 && g.top_p >= 0.f && g.top_p <= 1.f;
+    case KLAB_GEN_PICK: return V <= 32768;
+    default: return false;
   }
-  w.row_score = (float*)b.take(M * 2 * k * 4); w.row_idx = (int*)b.take(M * 2 * k * 4);
-  w.cand_score = (float*)b.take((long)e->B * 2 * k * 4); w.cand_idx = (int*)b.take((long)e->B * 2 * k * 4);
-  w.prev = (long long*)b.take(M * 8); w.parent = (int*)b.take(M * 4); w.run_score = (float*)b.take(M * 4);
-  w.fin_score = (float*)b.take(M * 4); w.fin_flag = (int*)b.take(M * 4); w.fin_len = (int*)b.take(M * 4);
-  w.unsat = (int*)b.take((long)e->B * 4); w.stop = (int*)b.take((long)Lm * 4);
-  take_proc(b, lp, M, V, w.proc, w.table);
-  return b.off;
-}
-// the update arguments of cur_len c: reads the buffers of parity c+1, writes those of parity c
-klab_beam_update_args beam_args(const klab_engine* e, const BeamWs& w, int c) {
-  klab_beam_update_args a;
-  memset(&a, 0, sizeof(a));
-  a.B = e->B; a.k = e->bm_k; a.V = e->cfg.main.vocab; a.max_length = e->bm_len; a.eos_id = e->bm_eos; a.early_stopping = e->bm_mode;
-  a.length_penalty = e->bm_lp;
-  a.cand_score = w.cand_score; a.cand_idx = w.cand_idx;
-  a.run_seq_in = w.run_seq[(c + 1) & 1]; a.run_seq_out = w.run_seq[c & 1]; a.run_score = w.run_score;
-  a.fin_seq_in = w.fin_seq[(c + 1) & 1]; a.fin_seq_out = w.fin_seq[c & 1];
-  a.fin_score = w.fin_score; a.fin_flag = w.fin_flag; a.fin_len = w.fin_len; a.unsat = w.unsat;
-  a.slot_in = w.slot[(c + 1) & 1]; a.slot_out = w.slot[c & 1];
-  a.prev_tokens = w.prev; a.parent = w.parent; a.stop_word = w.stop;
-  return a;
-}
-bool beam_shape_ok(const klab_engine* e, int k, int Lm, const ProcSet& lp) {
-  return e && e->bound && k >= 1 && k <= 16 && Lm >= 2 && Lm - 1 <= e->Lt && e->cfg.main.vocab >= 2 * k &&
-         (!lp.on || (!lp.cfg.pick && e->cfg.main.vocab <= 32768));
-}
-// the 2k candidates of every sample from logits rows r / row_div (through the processors when the search has them)
-int beam_topk_pos(klab_engine* e, const Ctx& c, const BeamWs& w, const void* logits, long ld, int row_div, int cur_len) {
-  const int k = e->bm_k, B = e->B, V = e->cfg.main.vocab;
-  if (!e->bm_lp_set.on)
-    return klab_beam_topk(c.dt, logits, ld, row_div, w.run_score, B, k, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws());
-  // HF's `_beam_search` hands log_softmax(logits) to the processors; each beam's history is its running sequence (parity c + 1)
-  klab_logits_proc_args a = proc_args(e->bm_lp_set, w.table, c.dt, logits, ld, row_div, B * k, V, w.run_seq[(cur_len + 1) & 1], e->bm_len,
-                                      cur_len, e->cfg.main.start_id, e->bm_eos);
-  a.log_softmax = 1;
-  a.out = w.proc; a.ld_out = V;
-  RC(klab_logits_process_rows(&a, c.ws()));
-  return klab_beam_topk_scores(w.proc, V, 1, w.run_score, B, k, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws());
-}
-}  // namespace
-
-extern "C" size_t klab_engine_beam_workspace_bytes(klab_engine* e, int num_beams, int max_length) {
-  if (!beam_shape_ok(e, num_beams, max_length, e->lp)) return 0;
-  BeamWs w;
-  return plan_beam(e, num_beams, max_length, e->lp, nullptr, w);
 }
 
-// Precondition: klab_engine_forward in evaluation mode on this binding (the prefill; its logits row b*Lt is position 0 of sample b)
-extern "C" int klab_engine_beam_begin(klab_engine* e, int num_beams, int max_length, float length_penalty, int early_stopping_mode,
-                                      int eos_id, int fill_id, void* ws, void* stream) {
-  if (!beam_shape_ok(e, num_beams, max_length, e->lp) || !ws || early_stopping_mode < 0 || early_stopping_mode > 2) return KLAB_ERR_BADARG;
-  Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
-  const klab_t5_cfg& cfg = e->cfg.main;
-  const int k = num_beams, Lm = max_length, B = e->B, V = cfg.vocab, inner = cfg.n_heads * cfg.d_kv;
-  e->bm_k = k; e->bm_len = Lm; e->bm_mode = early_stopping_mode; e->bm_eos = eos_id; e->bm_lp = length_penalty; e->bm_cur = 0;
-  e->bm_lp_set = e->lp;
-  BeamWs w;
-  plan_beam(e, k, Lm, e->bm_lp_set, ws, w);
-  RC(upload_proc(e->bm_lp_set, w.table, c.s));
-  klab_beam_update_args a = beam_args(e, w, 1);
-  RC(klab_beam_init(&a, cfg.start_id, fill_id, c.ws()));
-  // position 0 (the start token) of every beam: the prefill's self q|k|v row of its sample, copied into the beam's own slot
-  for (int i = 0; i < cfg.n_dec_layers; ++i)
-    RC(klab_beam_copy_rows((int)e->es, e->dec.L[i].qkv, (long)e->Lt * 3 * inner, k, eoff(c, w.rows.cache, (long)i * w.rows.cache_layer),
-                           (long)Lm * 3 * inner, B * k, 3 * inner, c.ws()));
-  // HF's first step (cur_len 1) on the prefill's position-0 logits, shared by the k beams of a sample
-  RC(beam_topk_pos(e, c, w, e->logits, (long)e->Lt * V, k, 1));
-  RC(klab_beam_update(&a, 1, c.ws()));
-  e->bm_cur = 1;
-  return 0;
-}
-
-// the decoder over position t for every beam (inputs: the tokens the last update chose), then top-2k and the update at cur_len t+1
-extern "C" int klab_engine_beam_step(klab_engine* e, int t, void* ws, void* stream) {
-  if (!e || !e->bound || !ws || e->bm_k < 1 || t < 1 || t != e->bm_cur || t > e->bm_len - 2 ||
-      !beam_shape_ok(e, e->bm_k, e->bm_len, e->bm_lp_set))
-    return KLAB_ERR_BADARG;
-  Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
-  const int k = e->bm_k, V = e->cfg.main.vocab;
-  BeamWs w;
-  plan_beam(e, k, e->bm_len, e->bm_lp_set, ws, w);
-  DecodeRows r = w.rows;
-  r.kv_slot = w.slot[t & 1];
-  RC(decode_rows(e, c, t, w.prev, r));
-  RC(beam_topk_pos(e, c, w, r.logits, V, 1, t + 1));
-  klab_beam_update_args a = beam_args(e, w, t + 1);
-  RC(klab_beam_update(&a, t + 1, c.ws()));
-  e->bm_cur = t + 1;
-  return 0;
-}
-
-extern "C" const int* klab_engine_beam_stop_word(klab_engine* e, void* ws, int cur_len) {
-  if (!e || !ws || e->bm_k < 1 || cur_len < 1 || cur_len >= e->bm_len) return nullptr;
-  BeamWs w;
-  plan_beam(e, e->bm_k, e->bm_len, e->bm_lp_set, ws, w);
-  return w.stop + cur_len;
-}
-
-extern "C" int klab_engine_beam_result(klab_engine* e, void* ws, int num_return_sequences, long long* seq, float* scores, int* len,
-                                       void* stream) {
-  const int n = num_return_sequences;
-  if (!e || !ws || e->bm_cur < 1 || n < 1 || n > e->bm_k || !seq || !scores || !len) return KLAB_ERR_BADARG;
-  BeamWs w;
-  plan_beam(e, e->bm_k, e->bm_len, e->bm_lp_set, ws, w);
-  const size_t Lm = e->bm_len, k = e->bm_k, B = e->B;
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t rc = hipMemcpy2DAsync(seq, n * Lm * 8, w.fin_seq[e->bm_cur & 1], k * Lm * 8, n * Lm * 8, B, hipMemcpyDeviceToDevice, s);
-  if (rc == hipSuccess) rc = hipMemcpy2DAsync(scores, n * 4, w.fin_score, k * 4, n * 4, B, hipMemcpyDeviceToDevice, s);
-  if (rc == hipSuccess) rc = hipMemcpy2DAsync(len, n * 4, w.fin_len, k * 4, n * 4, B, hipMemcpyDeviceToDevice, s);
-  return (int)rc;
-}
-
-// ---- sampling (HF `_sample`): a workspace of its own, owned by the caller ------------------------------------------------------
-namespace {
-struct SampleWs {
+struct GenWs {
   DecodeRows rows;
-  long long *seq, *prev; int *done, *stop;
+  long long* prev; int* stop;
   float* proc = nullptr; int* table = nullptr;  // logits processors only
+  // beam search
+  int* slot[2]; float *row_score, *cand_score; int *row_idx, *cand_idx;
+  int* parent; long long* run_seq[2]; float* run_score; long long* fin_seq[2];
+  float* fin_score; int *fin_flag, *fin_len, *unsat;
+  // sampling and pick
+  long long* seq; int* done;
 };
-size_t plan_sample(const klab_engine* e, int n, int Lm, const ProcSet& lp, void* base, SampleWs& w) {
+// decoder scratch, logits and self-attention cache for M = B*n rows, the mode's state, the next decoder inputs, the stop words, then
+// the processors' f32 rows [M, V] (not for pick, which writes none) and the bad-words table
+size_t plan_gen(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp, void* base, GenWs& w) {
   Bump b(base);
   const klab_t5_cfg& cfg = e->cfg.main;
   const size_t es = e->es;
+  const int n = g.n, Lm = g.max_length;
   const long M = (long)e->B * n, d = cfg.d_model, inner = (long)cfg.n_heads * cfg.d_kv, ff = cfg.d_ff, V = cfg.vocab;
   DecodeRows& r = w.rows;
   r.M = (int)M;
@@ -2104,26 +1957,81 @@ size_t plan_sample(const klab_engine* e, int n, int Lm, const ProcSet& lp, void*
   r.out = b.take(M * d * es); r.logits = b.take(M * V * es);
   r.cache_layer = M * Lm * 3 * inner; r.cache_rows = Lm;
   r.cache = b.take((size_t)cfg.n_dec_layers * r.cache_layer * es);
-  r.kv_group = n;  // (kv_slot NULL: row r's self-attention keys are its own slot r)
-  w.seq = (long long*)b.take(M * Lm * 8); w.prev = (long long*)b.take(M * 8);
-  w.done = (int*)b.take(M * 4); w.stop = (int*)b.take((long)Lm * 4);
-  if (!lp.cfg.pick) take_proc(b, lp, M, V, w.proc, w.table);  // (greedy's pick writes no processed rows)
-  else if (!lp.table.empty()) w.table = (int*)b.take(lp.table.size() * 4);
+  r.kv_group = n;
+  if (g.mode == KLAB_GEN_BEAM) {
+    r.slot_ld = Lm;  // (the step sets kv_slot; sampling leaves it NULL: row r's self-attention keys are its own slot r)
+    for (int p = 0; p < 2; ++p) {
+      w.slot[p] = (int*)b.take(M * Lm * 4);
+      w.run_seq[p] = (long long*)b.take(M * Lm * 8);
+      w.fin_seq[p] = (long long*)b.take(M * Lm * 8);
+    }
+    w.row_score = (float*)b.take(M * 2 * n * 4); w.row_idx = (int*)b.take(M * 2 * n * 4);
+    w.cand_score = (float*)b.take((long)e->B * 2 * n * 4); w.cand_idx = (int*)b.take((long)e->B * 2 * n * 4);
+    w.parent = (int*)b.take(M * 4); w.run_score = (float*)b.take(M * 4);
+    w.fin_score = (float*)b.take(M * 4); w.fin_flag = (int*)b.take(M * 4); w.fin_len = (int*)b.take(M * 4);
+    w.unsat = (int*)b.take((long)e->B * 4);
+  } else {
+    w.seq = (long long*)b.take(M * Lm * 8); w.done = (int*)b.take(M * 4);
+  }
+  w.prev = (long long*)b.take(M * 8); w.stop = (int*)b.take((long)Lm * 4);
+  if (lp.on && g.mode != KLAB_GEN_PICK) w.proc = (float*)b.take(M * V * 4);
+  if (!lp.table.empty()) w.table = (int*)b.take(lp.table.size() * 4);
   return b.off;
 }
-bool sample_shape_ok(const klab_engine* e, int n, int Lm) {
-  return e && e->bound && n >= 1 && Lm >= 2 && Lm - 1 <= e->Lt && e->cfg.main.vocab <= 32768;
+klab_logits_proc_args proc_args(const ProcSet& lp, const int* table, int dtype, const void* logits, long ld, int row_div, int rows, int V,
+                                long long* seq, long ld_seq, int cur_len, int start_id, int eos_id) {
+  klab_logits_proc_args a;
+  memset(&a, 0, sizeof(a));
+  a.dtype = dtype; a.logits = logits; a.ld = ld; a.row_div = row_div; a.rows = rows; a.V = V;
+  a.seq = seq; a.ld_seq = ld_seq; a.cur_len = cur_len; a.start_id = start_id;
+  a.repetition_penalty = lp.cfg.repetition_penalty; a.no_repeat_ngram_size = lp.cfg.no_repeat_ngram_size;
+  a.min_length = lp.cfg.min_length; a.min_new_tokens = lp.cfg.min_new_tokens; a.eos_id = eos_id;
+  a.n_bad = lp.cfg.n_bad;
+  if (table) { a.bad_off = table; a.bad_tok = table + lp.cfg.n_bad + 1; }
+  return a;
 }
-// one klab_sample_rows for position pos over the B*n rows (logits row r / row_div), behind the processors when the run has them
-// (HF's `_sample`: processors, then the warpers); greedy's pick replaces the draw
-int sample_pos(klab_engine* e, const Ctx& c, const SampleWs& w, const void* logits, long ld, int row_div, int pos) {
+// the beam update arguments of cur_len c: reads the buffers of parity c+1, writes those of parity c
+klab_beam_update_args beam_args(const klab_engine* e, const GenWs& w, int c) {
+  const klab_gen_cfg& g = e->gen.cfg;
+  klab_beam_update_args a;
+  memset(&a, 0, sizeof(a));
+  a.B = e->B; a.k = g.n; a.V = e->cfg.main.vocab; a.max_length = g.max_length; a.eos_id = g.eos_id; a.early_stopping = g.early_stopping;
+  a.length_penalty = g.length_penalty;
+  a.cand_score = w.cand_score; a.cand_idx = w.cand_idx;
+  a.run_seq_in = w.run_seq[(c + 1) & 1]; a.run_seq_out = w.run_seq[c & 1]; a.run_score = w.run_score;
+  a.fin_seq_in = w.fin_seq[(c + 1) & 1]; a.fin_seq_out = w.fin_seq[c & 1];
+  a.fin_score = w.fin_score; a.fin_flag = w.fin_flag; a.fin_len = w.fin_len; a.unsat = w.unsat;
+  a.slot_in = w.slot[(c + 1) & 1]; a.slot_out = w.slot[c & 1];
+  a.prev_tokens = w.prev; a.parent = w.parent; a.stop_word = w.stop;
+  return a;
+}
+// position pos (beam search: cur_len) of every row from logits rows r / row_div, behind the processors when the session has them:
+// beam search's top-2k of each sample and HF's update (HF hands the processors log_softmax(logits); each beam's history is its
+// running sequence, parity pos + 1), or one klab_sample_rows (HF's `_sample`: processors, then the warpers), or greedy's pick of
+// the processed arg-max
+int gen_pos(klab_engine* e, const Ctx& c, const GenWs& w, const void* logits, long ld, int row_div, int pos) {
+  const GenRun& g = e->gen;
+  const int B = e->B, n = g.cfg.n, V = e->cfg.main.vocab, start = e->cfg.main.start_id;
+  if (g.cfg.mode == KLAB_GEN_BEAM) {
+    if (!g.lp.on) {
+      RC(klab_beam_topk(c.dt, logits, ld, row_div, w.run_score, B, n, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws()));
+    } else {
+      klab_logits_proc_args p = proc_args(g.lp, w.table, c.dt, logits, ld, row_div, B * n, V, w.run_seq[(pos + 1) & 1], g.cfg.max_length,
+                                          pos, start, g.cfg.eos_id);
+      p.log_softmax = 1;
+      p.out = w.proc; p.ld_out = V;
+      RC(klab_logits_process_rows(&p, c.ws()));
+      RC(klab_beam_topk_scores(w.proc, V, 1, w.run_score, B, n, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws()));
+    }
+    klab_beam_update_args a = beam_args(e, w, pos);
+    return klab_beam_update(&a, pos, c.ws());
+  }
   int dt = c.dt;
-  if (e->sp_lp.on) {
-    const int V = e->cfg.main.vocab;
-    klab_logits_proc_args p = proc_args(e->sp_lp, w.table, c.dt, logits, ld, row_div, e->B * e->sp_n, V, w.seq, e->sp_len, pos,
-                                        e->cfg.main.start_id, e->sp_eos);
-    if (e->sp_lp.cfg.pick) {
-      p.pick = 1; p.done = w.done; p.pad_id = e->sp_pad; p.tokens = w.prev; p.stop_word = w.stop + pos;
+  if (g.lp.on || g.cfg.mode == KLAB_GEN_PICK) {
+    klab_logits_proc_args p = proc_args(g.lp, w.table, c.dt, logits, ld, row_div, B * n, V, w.seq, g.cfg.max_length, pos, start,
+                                        g.cfg.eos_id);
+    if (g.cfg.mode == KLAB_GEN_PICK) {
+      p.pick = 1; p.done = w.done; p.pad_id = g.cfg.pad_id; p.tokens = w.prev; p.stop_word = w.stop + pos;
       return klab_logits_process_rows(&p, c.ws());
     }
     p.out = w.proc; p.ld_out = V;
@@ -2133,73 +2041,94 @@ int sample_pos(klab_engine* e, const Ctx& c, const SampleWs& w, const void* logi
   klab_sample_args a;
   memset(&a, 0, sizeof(a));
   a.dtype = dt; a.logits = logits; a.ld = ld; a.row_div = row_div;
-  a.rows = e->B * e->sp_n; a.V = e->cfg.main.vocab;
-  a.temperature = e->sp_temp; a.top_k = e->sp_topk; a.top_p = e->sp_topp;
-  a.seed = e->sp_seed; a.step = pos;
-  a.done = w.done; a.eos_id = e->sp_eos; a.pad_id = e->sp_pad; a.start_id = e->cfg.main.start_id;
-  a.tokens = w.prev; a.seq = w.seq; a.ld_seq = e->sp_len; a.pos = pos; a.stop_word = w.stop + pos;
+  a.rows = B * n; a.V = V;
+  a.temperature = g.cfg.temperature; a.top_k = g.cfg.top_k; a.top_p = g.cfg.top_p;
+  a.seed = g.cfg.seed; a.step = pos;
+  a.done = w.done; a.eos_id = g.cfg.eos_id; a.pad_id = g.cfg.pad_id; a.start_id = start;
+  a.tokens = w.prev; a.seq = w.seq; a.ld_seq = g.cfg.max_length; a.pos = pos; a.stop_word = w.stop + pos;
   return klab_sample_rows(&a, c.ws());
 }
 }  // namespace
 
-extern "C" size_t klab_engine_sample_workspace_bytes(klab_engine* e, int num_return_sequences, int max_length) {
-  if (!sample_shape_ok(e, num_return_sequences, max_length)) return 0;
-  SampleWs w;
-  return plan_sample(e, num_return_sequences, max_length, e->lp, nullptr, w);
+extern "C" size_t klab_engine_gen_workspace_bytes(klab_engine* e, const klab_gen_cfg* cfg) {
+  ProcSet lp;
+  if (!e || !cfg || make_procs(e, cfg->procs, lp) || !gen_shape_ok(e, *cfg, lp)) return 0;
+  GenWs w;
+  return plan_gen(e, *cfg, lp, nullptr, w);
 }
 
 // Precondition: klab_engine_forward in evaluation mode on this binding (the prefill; its logits row b*Lt is position 0 of sample b)
-extern "C" int klab_engine_sample_begin(klab_engine* e, int num_return_sequences, int max_length, float temperature, int top_k,
-                                        float top_p, unsigned long long seed, int eos_id, int pad_id, void* ws, void* stream) {
-  if (!sample_shape_ok(e, num_return_sequences, max_length) || !ws || !(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f && top_p <= 1.f))
-    return KLAB_ERR_BADARG;
+extern "C" int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, void* ws, void* stream) {
+  if (!e || !cfg || !ws) return KLAB_ERR_BADARG;
+  ProcSet lp;
+  RC(make_procs(e, cfg->procs, lp));
+  if (!gen_shape_ok(e, *cfg, lp)) return KLAB_ERR_BADARG;
+  GenRun& g = e->gen;
+  g.cfg = *cfg; g.cfg.procs = nullptr;
+  g.lp = std::move(lp);
+  g.cur = 0;
   Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
-  const klab_t5_cfg& cfg = e->cfg.main;
-  const int n = num_return_sequences, Lm = max_length, B = e->B, V = cfg.vocab, inner = cfg.n_heads * cfg.d_kv;
-  e->sp_n = n; e->sp_len = Lm; e->sp_temp = temperature; e->sp_topk = top_k; e->sp_topp = top_p; e->sp_seed = seed;
-  e->sp_eos = eos_id; e->sp_pad = pad_id; e->sp_cur = 0;
-  e->sp_lp = e->lp;
-  SampleWs w;
-  plan_sample(e, n, Lm, e->sp_lp, ws, w);
-  RC(upload_proc(e->sp_lp, w.table, c.s));
-  RC((int)hipMemsetAsync(w.done, 0, (size_t)B * n * 4, c.s));
-  RC((int)hipMemsetAsync(w.stop, 0, (size_t)Lm * 4, c.s));
+  const klab_t5_cfg& mc = e->cfg.main;
+  const int n = g.cfg.n, Lm = g.cfg.max_length, B = e->B, inner = mc.n_heads * mc.d_kv;
+  GenWs w;
+  plan_gen(e, g.cfg, g.lp, ws, w);
+  if (!g.lp.table.empty()) RC((int)hipMemcpyAsync(w.table, g.lp.table.data(), g.lp.table.size() * 4, hipMemcpyHostToDevice, c.s));
+  if (g.cfg.mode == KLAB_GEN_BEAM) {
+    klab_beam_update_args a = beam_args(e, w, 1);
+    RC(klab_beam_init(&a, mc.start_id, g.cfg.pad_id, c.ws()));
+  } else {
+    RC((int)hipMemsetAsync(w.done, 0, (size_t)B * n * 4, c.s));
+    RC((int)hipMemsetAsync(w.stop, 0, (size_t)Lm * 4, c.s));
+  }
   // position 0 (the start token) of every row: the prefill's self q|k|v row of its image, copied into the row's own slot
-  for (int i = 0; i < cfg.n_dec_layers; ++i)
+  for (int i = 0; i < mc.n_dec_layers; ++i)
     RC(klab_beam_copy_rows((int)e->es, e->dec.L[i].qkv, (long)e->Lt * 3 * inner, n, eoff(c, w.rows.cache, (long)i * w.rows.cache_layer),
                            (long)Lm * 3 * inner, B * n, 3 * inner, c.ws()));
-  // position 1 from the prefill's position-0 logits, shared by the n rows of an image
-  RC(sample_pos(e, c, w, e->logits, (long)e->Lt * V, n, 1));
-  e->sp_cur = 1;
+  // position 1 (HF's first step) from the prefill's position-0 logits, shared by the n rows of an image
+  RC(gen_pos(e, c, w, e->logits, (long)e->Lt * mc.vocab, n, 1));
+  g.cur = 1;
   return 0;
 }
 
-// the decoder over position t for every row (inputs: the tokens sampled at t), then the draw of position t + 1
-extern "C" int klab_engine_sample_step(klab_engine* e, int t, void* ws, void* stream) {
-  if (!e || !e->bound || !ws || e->sp_n < 1 || t < 1 || t != e->sp_cur || t > e->sp_len - 2 || !sample_shape_ok(e, e->sp_n, e->sp_len))
-    return KLAB_ERR_BADARG;
+// the decoder over position t for every row (inputs: the tokens chosen at t), then position t + 1
+extern "C" int klab_engine_gen_step(klab_engine* e, int t, void* ws, void* stream) {
+  if (!e || !ws) return KLAB_ERR_BADARG;
+  GenRun& g = e->gen;
+  if (g.cur < 1 || t != g.cur || t > g.cfg.max_length - 2 || !gen_shape_ok(e, g.cfg, g.lp)) return KLAB_ERR_BADARG;
   Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
-  SampleWs w;
-  plan_sample(e, e->sp_n, e->sp_len, e->sp_lp, ws, w);
-  RC(decode_rows(e, c, t, w.prev, w.rows));
-  RC(sample_pos(e, c, w, w.rows.logits, e->cfg.main.vocab, 1, t + 1));
-  e->sp_cur = t + 1;
+  GenWs w;
+  plan_gen(e, g.cfg, g.lp, ws, w);
+  DecodeRows r = w.rows;
+  if (g.cfg.mode == KLAB_GEN_BEAM) r.kv_slot = w.slot[t & 1];
+  RC(decode_rows(e, c, t, w.prev, r));
+  RC(gen_pos(e, c, w, r.logits, e->cfg.main.vocab, 1, t + 1));
+  g.cur = t + 1;
   return 0;
 }
 
-extern "C" const int* klab_engine_sample_stop_word(klab_engine* e, void* ws, int pos) {
-  if (!e || !ws || e->sp_n < 1 || pos < 1 || pos >= e->sp_len) return nullptr;
-  SampleWs w;
-  plan_sample(e, e->sp_n, e->sp_len, e->sp_lp, ws, w);
+extern "C" const int* klab_engine_gen_stop_word(klab_engine* e, void* ws, int pos) {
+  if (!e || !ws || e->gen.cur < 1 || pos < 1 || pos >= e->gen.cfg.max_length) return nullptr;
+  GenWs w;
+  plan_gen(e, e->gen.cfg, e->gen.lp, ws, w);
   return w.stop + pos;
 }
 
-extern "C" int klab_engine_sample_result(klab_engine* e, void* ws, long long* seq, int length, void* stream) {
-  if (!e || !ws || e->sp_cur < 1 || !seq || length < 1 || length > e->sp_cur + 1) return KLAB_ERR_BADARG;
-  SampleWs w;
-  plan_sample(e, e->sp_n, e->sp_len, e->sp_lp, ws, w);
-  const size_t Lm = e->sp_len, rows = (size_t)e->B * e->sp_n;
-  return (int)hipMemcpy2DAsync(seq, (size_t)length * 8, w.seq, Lm * 8, (size_t)length * 8, rows, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+extern "C" int klab_engine_gen_result(klab_engine* e, void* ws, int n, int length, long long* seq, float* scores, int* len, void* stream) {
+  if (!e || !ws || e->gen.cur < 1 || !seq) return KLAB_ERR_BADARG;
+  const klab_gen_cfg& g = e->gen.cfg;
+  GenWs w;
+  plan_gen(e, g, e->gen.lp, ws, w);
+  const size_t Lm = g.max_length, k = g.n, B = e->B;
+  hipStream_t s = (hipStream_t)stream;
+  if (g.mode != KLAB_GEN_BEAM) {
+    if (n != g.n || length < 1 || length > e->gen.cur + 1) return KLAB_ERR_BADARG;
+    return (int)hipMemcpy2DAsync(seq, (size_t)length * 8, w.seq, Lm * 8, (size_t)length * 8, B * k, hipMemcpyDeviceToDevice, s);
+  }
+  if (n < 1 || n > g.n || length != g.max_length || !scores || !len) return KLAB_ERR_BADARG;
+  hipError_t rc = hipMemcpy2DAsync(seq, n * Lm * 8, w.fin_seq[e->gen.cur & 1], k * Lm * 8, n * Lm * 8, B, hipMemcpyDeviceToDevice, s);
+  if (rc == hipSuccess) rc = hipMemcpy2DAsync(scores, n * 4, w.fin_score, k * 4, n * 4, B, hipMemcpyDeviceToDevice, s);
+  if (rc == hipSuccess) rc = hipMemcpy2DAsync(len, n * 4, w.fin_len, k * 4, n * 4, B, hipMemcpyDeviceToDevice, s);
+  return (int)rc;
 }
 
 // segment 0: LM head + decoder + shared embedding; 1: encoder; 2: Swin

@@ -117,18 +117,11 @@ ENGINE_SIGS = {
                           C.POINTER(C.c_void_p), C.c_void_p], C.c_int),
     "klab_engine_forward": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p], C.c_int),
     "klab_engine_decode_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
-    "klab_engine_beam_workspace_bytes": ([C.c_void_p, C.c_int, C.c_int], C.c_size_t),
-    "klab_engine_beam_begin": ([C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
-    "klab_engine_beam_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
-    "klab_engine_beam_stop_word": ([C.c_void_p, C.c_void_p, C.c_int], C.c_void_p),
-    "klab_engine_beam_result": ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-    "klab_engine_sample_workspace_bytes": ([C.c_void_p, C.c_int, C.c_int], C.c_size_t),
-    "klab_engine_sample_begin": ([C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
-                                  C.c_void_p], C.c_int),
-    "klab_engine_sample_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
-    "klab_engine_sample_stop_word": ([C.c_void_p, C.c_void_p, C.c_int], C.c_void_p),
-    "klab_engine_sample_result": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
-    "klab_engine_set_logits_processors": ([C.c_void_p, C.c_void_p], C.c_int),
+    "klab_engine_gen_workspace_bytes": ([C.c_void_p, C.POINTER(L.GenCfg)], C.c_size_t),
+    "klab_engine_gen_begin": ([C.c_void_p, C.POINTER(L.GenCfg), C.c_void_p, C.c_void_p], C.c_int),
+    "klab_engine_gen_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+    "klab_engine_gen_stop_word": ([C.c_void_p, C.c_void_p, C.c_int], C.c_void_p),
+    "klab_engine_gen_result": ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_backward": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_set_graph": ([C.c_void_p, C.c_int], C.c_int),
     "klab_engine_get_rng": ([C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p], C.c_int),
@@ -277,6 +270,7 @@ class Engine:
             self.buckets.append(out)
         self._keep = None
         self.shape = None
+        self._gen = None  # the klab_gen_cfg of the decoding session begun last
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -370,87 +364,70 @@ class Engine:
         """decoder over position t (>= 1) only, self-attention K/V from the binding's cache; logits -> buffer("logits_step")"""
         L.check(self._lib.klab_engine_decode_step(self._h, int(t), prev_tokens.data_ptr(), L.stream_ptr()), "klab_engine_decode_step")
 
-    # ---- beam search (HF `_beam_search`); the workspace is the caller's, the binding's is untouched -------------------
+    # ---- decoding sessions (HF `_beam_search`, `_sample`, greedy behind the processors); the workspace is the caller's, the
+    # binding's is untouched -------------------------------------------------------------------------------------------------
+    GEN_MODES = {"pick": L.GEN_PICK, "sample": L.GEN_SAMPLE, "beam": L.GEN_BEAM}
     EARLY_STOPPING = {False: 0, True: 1, "never": 2}
 
-    def beam_workspace_bytes(self, num_beams, max_length):
-        return int(self._lib.klab_engine_beam_workspace_bytes(self._h, int(num_beams), int(max_length)))
+    @classmethod
+    def gen_cfg(cls, mode, n, max_length, eos_id, pad_id, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=1.0,
+                early_stopping=False, procs=None):
+        """the klab_gen_cfg of a session; procs: the logits processors' settings (logits_proc.logits_processor_settings), None =
+        none.  The cfg keeps the C arrays it points to alive."""
+        cfg = L.GenCfg(cls.GEN_MODES[mode], int(n), int(max_length), int(eos_id), int(pad_id), float(temperature), int(top_k),
+                       float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, float(length_penalty), cls.EARLY_STOPPING[early_stopping])
+        if procs is not None:
+            words = [list(map(int, w)) for w in procs["bad_words_ids"]]
+            off = [0]
+            for w in words:
+                off.append(off[-1] + len(w))
+            toks = [t for w in words for t in w]
+            off_a = (C.c_int * len(off))(*off)
+            tok_a = (C.c_int * max(1, len(toks)))(*toks)
+            cfg.procs = C.pointer(L.LogitsProcCfg(float(procs["repetition_penalty"]), int(procs["no_repeat_ngram_size"]),
+                                                  int(procs["min_length"]), int(procs["min_new_tokens"]), len(words),
+                                                  C.cast(off_a, C.POINTER(C.c_int)), C.cast(tok_a, C.POINTER(C.c_int))))
+        return cfg
 
-    def beam_begin(self, num_beams, max_length, length_penalty, early_stopping, eos_id, fill_id, ws):
-        """after an evaluation-mode forward (the prefill): state init + HF's first step on the prefill's position-0 logits"""
-        mode = self.EARLY_STOPPING[early_stopping]
-        L.check(self._lib.klab_engine_beam_begin(self._h, int(num_beams), int(max_length), float(length_penalty), mode, int(eos_id), int(fill_id),
-                                                 ws.data_ptr(), L.stream_ptr()), "klab_engine_beam_begin")
+    def gen_workspace_bytes(self, cfg):
+        """bytes of the session's workspace; 0 = settings this binding does not support"""
+        return int(self._lib.klab_engine_gen_workspace_bytes(self._h, C.byref(cfg)))
 
-    def beam_step(self, t, ws):
-        """decoder over position t for all beams, then top-2k and the update at cur_len t + 1"""
-        L.check(self._lib.klab_engine_beam_step(self._h, int(t), ws.data_ptr(), L.stream_ptr()), "klab_engine_beam_step")
+    def gen_begin(self, cfg, ws):
+        """after an evaluation-mode forward (the prefill): the session's state, and position 1 from the prefill's position-0 logits"""
+        L.check(self._lib.klab_engine_gen_begin(self._h, C.byref(cfg), ws.data_ptr(), L.stream_ptr()), "klab_engine_gen_begin")
+        self._gen = cfg
 
-    def beam_stop_word(self, ws, cur_len):
-        """int32 view of the stop word the update at cur_len ORs into (bits: 1 improvable, 2 open pool entry, 4 live candidate)"""
-        p = self._lib.klab_engine_beam_stop_word(self._h, ws.data_ptr(), int(cur_len))
+    def gen_step(self, t, ws):
+        """decoder over position t for all rows, then position t + 1"""
+        L.check(self._lib.klab_engine_gen_step(self._h, int(t), ws.data_ptr(), L.stream_ptr()), "klab_engine_gen_step")
+
+    def gen_going(self, ws, pos):
+        """the one host sync per step: whether the session goes on after position pos (beam search: bits 1 (improvable) and 4 (live
+        candidate), and 2 (open pool entry) with early_stopping True; sampling and pick: some row unfinished)"""
+        p = self._lib.klab_engine_gen_stop_word(self._h, ws.data_ptr(), int(pos))
         if not p:
-            raise ValueError("klab: bad argument to klab_engine_beam_stop_word")
+            raise ValueError("klab: bad argument to klab_engine_gen_stop_word")
         off = p - ws.data_ptr()
-        return ws[off:off + 4].view(torch.int32)
+        w = int(ws[off:off + 4].view(torch.int32).item())
+        if self._gen.mode != L.GEN_BEAM:
+            return w != 0
+        return bool((w & 1) and (w & 4) and (self._gen.early_stopping != 1 or (w & 2)))
 
-    def beam_result(self, ws, num_return_sequences, max_length):
-        """(sequences [B*n, max_length] int64, scores [B*n] f32, generated lengths [B*n] int32) of the finished pools"""
-        B, n = self.shape[0], int(num_return_sequences)
-        seq = torch.empty(B * n, int(max_length), dtype=torch.int64, device=ws.device)
+    def gen_result(self, ws, n, length):
+        """beam search: (sequences [B*n, length = max_length] int64, scores [B*n] f32, generated lengths [B*n] int32) of the first n
+        entries of the finished pools; sampling and pick: (the first `length` columns of the sequences [B*n, length] int64, None, None)"""
+        B, n, length = self.shape[0], int(n), int(length)
+        seq = torch.empty(B * n, length, dtype=torch.int64, device=ws.device)
+        if self._gen.mode != L.GEN_BEAM:
+            L.check(self._lib.klab_engine_gen_result(self._h, ws.data_ptr(), n, length, seq.data_ptr(), None, None, L.stream_ptr()),
+                    "klab_engine_gen_result")
+            return seq, None, None
         scores = torch.empty(B * n, dtype=torch.float32, device=ws.device)
         lens = torch.empty(B * n, dtype=torch.int32, device=ws.device)
-        L.check(self._lib.klab_engine_beam_result(self._h, ws.data_ptr(), n, seq.data_ptr(), scores.data_ptr(), lens.data_ptr(), L.stream_ptr()),
-                "klab_engine_beam_result")
+        L.check(self._lib.klab_engine_gen_result(self._h, ws.data_ptr(), n, length, seq.data_ptr(), scores.data_ptr(), lens.data_ptr(),
+                                                 L.stream_ptr()), "klab_engine_gen_result")
         return seq, scores, lens
-
-    # ---- sampling (HF `_sample`); the workspace is the caller's, the binding's is untouched ----------------------------
-    def sample_workspace_bytes(self, num_return_sequences, max_length):
-        return int(self._lib.klab_engine_sample_workspace_bytes(self._h, int(num_return_sequences), int(max_length)))
-
-    def sample_begin(self, num_return_sequences, max_length, temperature, top_k, top_p, seed, eos_id, pad_id, ws):
-        """after an evaluation-mode forward (the prefill): position 1 of every row from the prefill's position-0 logits"""
-        L.check(self._lib.klab_engine_sample_begin(self._h, int(num_return_sequences), int(max_length), float(temperature), int(top_k),
-                                                   float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(eos_id), int(pad_id), ws.data_ptr(),
-                                                   L.stream_ptr()), "klab_engine_sample_begin")
-
-    def sample_step(self, t, ws):
-        """decoder over position t for all rows, then the draw of position t + 1"""
-        L.check(self._lib.klab_engine_sample_step(self._h, int(t), ws.data_ptr(), L.stream_ptr()), "klab_engine_sample_step")
-
-    def sample_stop_word(self, ws, pos):
-        """int32 view of the stop word of position pos (1 while some row is unfinished)"""
-        p = self._lib.klab_engine_sample_stop_word(self._h, ws.data_ptr(), int(pos))
-        if not p:
-            raise ValueError("klab: bad argument to klab_engine_sample_stop_word")
-        off = p - ws.data_ptr()
-        return ws[off:off + 4].view(torch.int32)
-
-    def sample_result(self, ws, rows, length):
-        """the first `length` columns of the sampled sequences, [rows, length] int64"""
-        seq = torch.empty(int(rows), int(length), dtype=torch.int64, device=ws.device)
-        L.check(self._lib.klab_engine_sample_result(self._h, ws.data_ptr(), seq.data_ptr(), int(length), L.stream_ptr()),
-                "klab_engine_sample_result")
-        return seq
-
-    # ---- logits processors (HF's repetition penalty, n-gram ban, bad words, min length) for the sample / beam entry points ------
-    def set_logits_processors(self, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=(), min_length=0, min_new_tokens=0,
-                              pick=False, clear=False):
-        """the processor settings of the next sample_begin / beam_begin (clear=True: none, the default state); pick=True: greedy
-        decoding through the sampling entry points, the processed arg-max replacing the draw"""
-        if clear:
-            L.check(self._lib.klab_engine_set_logits_processors(self._h, None), "klab_engine_set_logits_processors")
-            return
-        words = [list(map(int, w)) for w in bad_words_ids]
-        off = [0]
-        for w in words:
-            off.append(off[-1] + len(w))
-        toks = [t for w in words for t in w]
-        off_a = (C.c_int * len(off))(*off)
-        tok_a = (C.c_int * max(1, len(toks)))(*toks)
-        cfg = L.LogitsProcCfg(float(repetition_penalty), int(no_repeat_ngram_size), int(min_length), int(min_new_tokens), len(words),
-                              C.cast(off_a, C.POINTER(C.c_int)), C.cast(tok_a, C.POINTER(C.c_int)), int(bool(pick)))
-        L.check(self._lib.klab_engine_set_logits_processors(self._h, C.byref(cfg)), "klab_engine_set_logits_processors")
 
     def backward(self, segment, dloss=None):
         L.check(self._lib.klab_engine_backward(self._h, segment, dloss.data_ptr() if dloss is not None else None, L.stream_ptr()),

@@ -381,7 +381,7 @@ class MyModel(nn.Module):
         names, defaults and checks (logits_proc.logits_processor_settings), in front of all three loops as in HF: on the fp32
         logits for greedy and sampling (before the warpers), on log_softmax(logits) for beam search; the history is the decoder
         sequence with its start token.  One `klab_logits_process_rows` per step (csrc/logits_proc.hip); greedy decoding with
-        processors runs through the sampling entry points, the processed arg-max replacing the draw.  With none of them active
+        processors runs as a decoding session of its own ("pick"), the processed arg-max replacing the draw.  With none of them active
         every path runs as without them."""
         procs = logits_processor_settings(repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens,
                                           eos_token_id=self.main_cfg.eos_token_id, vocab_size=self.main_cfg.vocab_size)
@@ -446,89 +446,63 @@ class MyModel(nn.Module):
         start = torch.full((B, 1), cfg.decoder_start_token_id, dtype=torch.int64, device=src.device)
         return torch.cat([start, tgt], dim=1)
 
-    def _generate_beam(self, pixels, src, max_length, num_beams, length_penalty, early_stopping, num_return_sequences, return_scores,
-                       procs=None):
-        """One prefill at B rows (Swin, both encoders and the cross K/V run once per sample, not per beam), then the beam state
-        lives on the device: every step is the decoder over B*num_beams rows, top-2k and HF's bookkeeping
-        (`klab_engine_beam_step`); the host reads one stop word per step.  Returns [B*num_return_sequences, L] int64 (start
-        token, pads after EOS, cropped to the longest returned hypothesis), and its scores when return_scores.  procs: the logits
-        processors' settings (logits_proc.logits_processor_settings), set on the engine for this call only."""
-        if early_stopping not in (False, True, "never"):
+    def _generate_on_device(self, pixels, src, max_length, mode, n, procs=None, num_return_sequences=None, temperature=1.0, top_k=0,
+                            top_p=1.0, length_penalty=1.0, early_stopping=False):
+        """One prefill at B rows (Swin, both encoders and the cross K/V run once per image, not per row), then a decoding session of
+        B*n rows on the device (row b*n + j: beam / sample j of image b, HF's `_expand_inputs_for_generation`): every step is the
+        decoder over B*n rows and the mode's choice of the next tokens (`klab_engine_gen_step`); the host reads one stop word per
+        step.  mode "beam": HF's `_beam_search` with n = num_beams, returning num_return_sequences hypotheses per image (start
+        token, pads after EOS, cropped to the longest returned one) and their scores.  "sample": HF's `_sample` with n =
+        num_return_sequences; the draws come from a counter hash of one 64-bit seed taken from torch's default CPU generator per
+        call (torch.manual_seed reproduces a call).  "pick": greedy decoding, the processed arg-max instead of a draw (no seed is
+        taken).  Sampling and pick return [B*n, L] int64 (start token, pad after EOS, cropped when every row is done) and None.
+        procs: the logits processors' settings (logits_proc.logits_processor_settings), None = none."""
+        if mode == "beam" and early_stopping not in (False, True, "never"):
             raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
         if max_length < 2:
             raise ValueError("max_length must count the start token and at least one generated token")
         B = src.shape[0]
         cfg = self.main_cfg
-        k = int(num_beams)
+        n = int(n)
+        seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (), dtype=torch.int64)) if mode == "sample" else 0
+        # beam search's fill value of unfinished positions is HF's `pad_token_id or eos_token_id` (a pad id of 0 yields to EOS)
+        pad = (cfg.pad_token_id or cfg.eos_token_id) if mode == "beam" else cfg.pad_token_id
         tgt = torch.full((B, max_length - 1), cfg.pad_token_id, dtype=torch.int64, device=src.device)
-        # HF's fill value of unfinished positions: `pad_token_id or eos_token_id` (a pad id of 0 yields to EOS)
-        fill = cfg.pad_token_id or cfg.eos_token_id
         was_training = self.transformer.training
         self.transformer.eval()
-        eng = None
         try:
             eng = self._engine_for(pixels, src, tgt)
             eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
-            if procs is not None:
-                eng.set_logits_processors(**procs)
-            nbytes = eng.beam_workspace_bytes(k, max_length)
+            gen = eng.gen_cfg(mode, n, max_length, cfg.eos_token_id, pad, temperature, top_k, top_p, seed, length_penalty, early_stopping,
+                              procs)
+            nbytes = eng.gen_workspace_bytes(gen)
             if nbytes == 0:
-                raise ValueError(f"beam search: unsupported num_beams={k} / max_length={max_length} for this model")
+                what = f"beam search: unsupported num_beams={n}" if mode == "beam" else f"sampling: unsupported num_return_sequences={n}"
+                raise ValueError(f"{what} / max_length={max_length} for this model")
             ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
-            eng.beam_begin(k, max_length, length_penalty, early_stopping, cfg.eos_token_id, fill, ws)
+            eng.gen_begin(gen, ws)
             cur = 1
-            while True:
-                w = int(eng.beam_stop_word(ws, cur).item())  # the one host sync per step
-                if not ((w & 1) and (w & 4) and (early_stopping is not True or (w & 2))) or cur >= max_length - 1:
-                    break
-                eng.beam_step(cur, ws)
+            while cur < max_length - 1 and eng.gen_going(ws, cur):
+                eng.gen_step(cur, ws)
                 cur += 1
-            seq, scores, lens = eng.beam_result(ws, num_return_sequences, max_length)
+            if mode != "beam":
+                return eng.gen_result(ws, n, cur + 1)[0], None
+            seq, scores, lens = eng.gen_result(ws, num_return_sequences, max_length)
         finally:
-            if procs is not None and eng is not None:
-                eng.set_logits_processors(clear=True)
             self.transformer.train(was_training)
-        seq = seq[:, :1 + int(lens.max())]
+        return seq[:, :1 + int(lens.max())], scores
+
+    def _generate_beam(self, pixels, src, max_length, num_beams, length_penalty, early_stopping, num_return_sequences, return_scores,
+                       procs=None):
+        """HF's `_beam_search` as a decoding session (_generate_on_device): the sequences, and their scores when return_scores"""
+        seq, scores = self._generate_on_device(pixels, src, max_length, "beam", num_beams, procs, num_return_sequences,
+                                               length_penalty=length_penalty, early_stopping=early_stopping)
         return (seq, scores) if return_scores else seq
 
     def _generate_sample(self, pixels, src, max_length, num_return_sequences, temperature, top_k, top_p, procs=None, pick=False):
-        """One prefill at B rows, then B*n rows (row b*n + j: sample j of image b, HF's `_expand_inputs_for_generation`) on the
-        device: every step is the decoder over B*n rows and one sampling kernel that applies HF's warpers, draws, and does
-        greedy's bookkeeping (`klab_engine_sample_step`); the host reads one stop word per step.  The draws come from a counter
-        hash of one 64-bit seed taken from torch's default CPU generator per call (torch.manual_seed reproduces a call).
-        Returns [B*n, L] int64: start token, pad after EOS, cropped when every row is done.  procs: the logits processors'
-        settings, applied before the warpers and set on the engine for this call only; pick=True (with procs, n = 1): greedy
-        decoding, the processed arg-max instead of a draw (no seed is taken)."""
-        if max_length < 2:
-            raise ValueError("max_length must count the start token and at least one generated token")
-        B = src.shape[0]
-        cfg = self.main_cfg
-        n = int(num_return_sequences)
-        seed = 0 if pick else int(torch.randint(-2 ** 63, 2 ** 63 - 1, (), dtype=torch.int64)) & 0xFFFFFFFFFFFFFFFF
-        tgt = torch.full((B, max_length - 1), cfg.pad_token_id, dtype=torch.int64, device=src.device)
-        was_training = self.transformer.training
-        self.transformer.eval()
-        eng = None
-        try:
-            eng = self._engine_for(pixels, src, tgt)
-            eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
-            if procs is not None:
-                eng.set_logits_processors(**procs, pick=pick)
-            nbytes = eng.sample_workspace_bytes(n, max_length)
-            if nbytes == 0:
-                raise ValueError(f"sampling: unsupported num_return_sequences={n} / max_length={max_length} for this model")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
-            eng.sample_begin(n, max_length, temperature, top_k, top_p, seed, cfg.eos_token_id, cfg.pad_token_id, ws)
-            cur = 1
-            while cur < max_length - 1 and int(eng.sample_stop_word(ws, cur).item()):  # the one host sync per step
-                eng.sample_step(cur, ws)
-                cur += 1
-            seq = eng.sample_result(ws, B * n, cur + 1)
-        finally:
-            if procs is not None and eng is not None:
-                eng.set_logits_processors(clear=True)
-            self.transformer.train(was_training)
-        return seq
+        """HF's `_sample` as a decoding session (_generate_on_device); pick=True: greedy decoding, the processed arg-max"""
+        return self._generate_on_device(pixels, src, max_length, "pick" if pick else "sample", num_return_sequences, procs,
+                                        temperature=temperature, top_k=top_k, top_p=top_p)[0]
 
     def _join_pending_update(self):
         """an optimizer update still running on its own stream (optim.FusedAdam(step_in_backward=True)) writes the weights:
