@@ -322,6 +322,15 @@ int klab_convert(const float* x, void* y, int dtype, long n, float scale, void* 
 int klab_add_f32(float* y, const float* x, long n, void* stream);
 
 int klab_gelu_fwd(const void* x, void* y, int dtype, long n, void* stream);
+/* Gate of the T5 v1.1 feed-forward (HF T5DenseGatedActDense): ab [M, 2F] row-major with leading dimension ldab holds the two
+ * pre-activations side by side, a = ab[:, :F] (wi_0 x) and b = ab[:, F:] (wi_1 x).
+ *   forward : h[M,F] = dropout(gelu_new(a) * b), mask = keep(seed_dev, tag, m * F + f), scale 1/(1-p)
+ *   backward: dab[:, :F] = dh * mask/(1-p) * b * gelu_new'(a),  dab[:, F:] = dh * mask/(1-p) * gelu_new(a)   (the mask is regenerated)
+ * gelu_new is the tanh approximation.  Every matrix in `dtype` (f32 | bf16), arithmetic in f32.  F % 8 == 0, ld* % 8 == 0. */
+int klab_geglu_fwd(const void* ab, long ldab, void* h, long ldh, int dtype, int M, int F, float drop_p, const uint32_t* seed_dev,
+                   uint32_t drop_tag, void* stream);
+int klab_geglu_bwd(const void* dh, long lddh, const void* ab, long ldab, void* dab, long lddab, int dtype, int M, int F, float drop_p,
+                   const uint32_t* seed_dev, uint32_t drop_tag, void* stream);
 /* Frozen-tower (forward-only) fusion of the MLP half of a Swin-V2 block, HF/swinv2:539-563 + 697-702:
  *   out[M,C] = shortcut + LayerNorm(fc2(GELU(fc1(x) + b1)) + b2) * gamma + beta,  outt = bf16(out) (optional)
  * x [M,C], w1 [4C,C], w2 [C,4C] in `dtype` (bf16 only), everything else f32.  C in {64, 128}; other widths return
@@ -370,6 +379,8 @@ typedef struct klab_t5_cfg {    /* HF/t5cfg:44-62,82-83 */
   int vocab, d_model, d_kv, n_heads, d_ff, n_layers, n_dec_layers, rel_buckets, rel_max_dist;
   float dropout, ln_eps;
   int start_id, pad_id, scale_decoder_outputs;
+  int ffn_gated;   /* 0: wo(relu(wi x)) (T5 v1.0); 1: wo(gelu_new(wi_0 x) * (wi_1 x)) (T5 v1.1 / Flan-T5, HF T5DenseGatedActDense) */
+  int tie_lm_head; /* 1: the LM head is shared.weight (v1.0); 0: lm_head.weight is a parameter of its own */
 } klab_t5_cfg;
 typedef struct klab_model_cfg {
   klab_swin_cfg swin;
@@ -379,6 +390,8 @@ typedef struct klab_model_cfg {
 } klab_model_cfg;
 typedef struct klab_engine klab_engine;
 
+int klab_sizeof_t5_cfg(void);    /* sizeof(klab_t5_cfg) / sizeof(klab_model_cfg): the ctypes mirrors are checked against them */
+int klab_sizeof_model_cfg(void);
 klab_engine* klab_engine_create(const klab_model_cfg* cfg); /* NULL on an invalid config (e.g. Swin width != d_model:
                                                                the reference raises at its torch.cat, model.py:23) */
 void klab_engine_destroy(klab_engine* e);

@@ -430,6 +430,7 @@ static int launch_decode_attn(const void* q, long q_bstride, const void* k, cons
     hipLaunchKernelGGL((decode_attn_kernel<T, D, false>), dim3(B * H), dim3(64), 0, s, (const T*)q, q_bstride, (const T*)k, (const T*)v, \
                        kv_bstride, ldk, kv_group, kv_slot, slot_ld, bias_row, bias_ld, (T*)ctx, ctx_bstride, H, Lk)
   switch (dk) {
+    case 8: DEC_LAUNCH(8); break;
     case 16: DEC_LAUNCH(16); break;
     case 32: DEC_LAUNCH(32); break;
     case 64: DEC_LAUNCH(64); break;

@@ -42,8 +42,10 @@ struct ParamInfo {
   long farena_off = -1; // element offset in the f32 side arena (fused bias vectors)
 };
 
-struct T5LayerIdx { int q, k, v, o, relb, ln0, cq, ck, cv, co, ln1, wi, wo, ln2; };
-struct T5Idx { int shared; std::vector<T5LayerIdx> enc, dec; int enc_final, dec_final; };
+// gated feed-forward (klab_t5_cfg.ffn_gated): wi = wi_0, wi1 = wi_1, adjacent in the weight arena and in the gradient buffer (one
+// [2 d_ff, d_model] operand); otherwise wi1 = -1.  lm_head = -1 when the head is tied to shared.weight; head = the LM-head operand.
+struct T5LayerIdx { int q, k, v, o, relb, ln0, cq, ck, cv, co, ln1, wi, wi1, wo, ln2; };
+struct T5Idx { int shared, lm_head = -1, head = -1; std::vector<T5LayerIdx> enc, dec; int enc_final, dec_final; };
 struct SwinBlockIdx { int ls, c0w, c0b, c2w, qw, qb, kw, vw, vb, pw, pb, ln1w, ln1b, f1w, f1b, f2w, f2b, ln2w, ln2b; };
 struct SwinStageIdx { std::vector<SwinBlockIdx> blk; int redw, mnw, mnb; };
 struct SwinIdx { int pew, peb, penw, penb; std::vector<SwinStageIdx> st; int lnw, lnb; };
@@ -52,6 +54,7 @@ struct T5LayerBufs {
   void *xn1, *qkv, *ctx; float *lse, *rstd1;
   void *xn2, *qc, *ctx2; float *lse2, *rstd2;
   void *xn3, *hmid; float* rstd3;
+  void* ab;  // gated feed-forward: the two pre-activations [M, 2 d_ff]
 };
 struct T5StackBufs {
   std::vector<float*> h;
@@ -143,7 +146,7 @@ struct klab_engine {
   T5StackBufs lang, enc, dec;
   // greedy decoding with a K/V cache (klab_engine_decode_step): one position per sample, contiguous [B, .] rows
   float* dc_h[2] = {nullptr, nullptr}; float* dc_rstd = nullptr;
-  void *dc_xn = nullptr, *dc_q = nullptr, *dc_ctx = nullptr, *dc_hmid = nullptr, *dc_out = nullptr, *dc_logits = nullptr;
+  void *dc_xn = nullptr, *dc_q = nullptr, *dc_ctx = nullptr, *dc_hmid = nullptr, *dc_ab = nullptr, *dc_out = nullptr, *dc_logits = nullptr;
   // the decoding session (klab_engine_gen_*) begun last on this binding
   GenRun gen;
   // lang scratch (no grad => reused across layers)
@@ -151,6 +154,7 @@ struct klab_engine {
   void* logits = nullptr; float *loss_row = nullptr, *inv_n = nullptr, *loss = nullptr;
   float *dh_a = nullptr, *dh_b = nullptr, *dxn = nullptr, *denc = nullptr;
   void *dctx = nullptr, *ds_ws = nullptr;
+  void* dh_ff = nullptr;  // gated feed-forward: wo's dgrad output in front of the gate backward (consumed at once on the main stream)
   // per-sub-layer gradient operands (no buffer is rewritten inside a backward segment, so the weight-gradient GEMMs
   // can trail on the side stream with read-after-write events only)
   std::vector<void*> dy_pool, dhmid_pool, dqkv_pool, dqc_pool;
@@ -219,6 +223,8 @@ int add_param(std::vector<ParamInfo>& v, const std::string& name, std::vector<lo
 void build_t5_params(const klab_t5_cfg& c, bool encoder_only, std::vector<ParamInfo>& v, T5Idx& ix) {
   const long d = c.d_model, inner = (long)c.n_heads * c.d_kv, ff = c.d_ff;
   ix.shared = add_param(v, "shared.weight", {c.vocab, d});
+  ix.lm_head = (!encoder_only && !c.tie_lm_head) ? add_param(v, "lm_head.weight", {c.vocab, d}) : -1;
+  ix.head = ix.lm_head >= 0 ? ix.lm_head : ix.shared;
   auto stack = [&](const char* pre, int nl, bool dec, std::vector<T5LayerIdx>& L, int& fin) {
     for (int i = 0; i < nl; ++i) {
       T5LayerIdx l;
@@ -242,7 +248,12 @@ void build_t5_params(const klab_t5_cfg& c, bool encoder_only, std::vector<ParamI
         li = 2;
       }
       std::string fp = bp + "layer." + std::to_string(li) + ".";
-      l.wi = add_param(v, fp + "DenseReluDense.wi.weight", {ff, d});
+      if (c.ffn_gated) {
+        l.wi = add_param(v, fp + "DenseReluDense.wi_0.weight", {ff, d});
+        l.wi1 = add_param(v, fp + "DenseReluDense.wi_1.weight", {ff, d});
+      } else {
+        l.wi = add_param(v, fp + "DenseReluDense.wi.weight", {ff, d});
+      }
       l.wo = add_param(v, fp + "DenseReluDense.wo.weight", {d, ff});
       l.ln2 = add_param(v, fp + "layer_norm.weight", {d});
       L.push_back(l);
@@ -310,18 +321,18 @@ void plan_arenas(klab_engine* e) {
   // (16-element alignment: the fp8 copy of the arena uses the same element offsets as byte offsets)
   auto putw = [&](std::vector<ParamInfo>& v, int i) { if (i >= 0) { v[i].warena_off = w; w += (v[i].numel + 15) & ~15L; } };
   auto t5 = [&](std::vector<ParamInfo>& v, T5Idx& ix, bool is_main) {
-    putw(v, ix.shared);  // tied LM head operand (and nothing else: embeddings are gathered from the f32 master)
-    for (auto& l : ix.dec) { putw(v, l.q); putw(v, l.k); putw(v, l.v); putw(v, l.o); putw(v, l.cq); putw(v, l.co); putw(v, l.wi); putw(v, l.wo); }
+    putw(v, ix.head);  // the LM head operand: shared.weight when tied (and nothing else: embeddings are gathered from the f32 master)
+    for (auto& l : ix.dec) { putw(v, l.q); putw(v, l.k); putw(v, l.v); putw(v, l.o); putw(v, l.cq); putw(v, l.co); putw(v, l.wi); putw(v, l.wi1); putw(v, l.wo); }
     if (is_main && !ix.dec.empty()) {
       e->kvall_w_off = w;
       for (auto& l : ix.dec) { putw(v, l.ck); putw(v, l.cv); }
     }
-    for (auto& l : ix.enc) { putw(v, l.q); putw(v, l.k); putw(v, l.v); putw(v, l.o); putw(v, l.wi); putw(v, l.wo); }
+    for (auto& l : ix.enc) { putw(v, l.q); putw(v, l.k); putw(v, l.v); putw(v, l.o); putw(v, l.wi); putw(v, l.wi1); putw(v, l.wo); }
   };
   t5(e->P[2], e->mi, true);
   {  // lang: encoder only; shared is gathered in f32 => no arena copy
     auto& v = e->P[1];
-    for (auto& l : e->li.enc) { putw(v, l.q); putw(v, l.k); putw(v, l.v); putw(v, l.o); putw(v, l.wi); putw(v, l.wo); }
+    for (auto& l : e->li.enc) { putw(v, l.q); putw(v, l.k); putw(v, l.v); putw(v, l.o); putw(v, l.wi); putw(v, l.wi1); putw(v, l.wo); }
   }
   {
     auto& v = e->P[0];
@@ -360,11 +371,12 @@ void plan_grads(klab_engine* e) {
     put(e->mi.dec_final);
     e->seg_zero_len[0] = g;
     put(e->mi.shared);
+    put(e->mi.lm_head);
     e->buckets[0].assign(e->mi.dec.size(), klab_engine::Bucket{0, 0});
     for (size_t li = 0; li < e->mi.dec.size(); ++li) {
       auto& l = e->mi.dec[li];
       const long g0 = g;
-      put(l.q); put(l.k); put(l.v); put(l.o); put(l.cq); put(l.co); put(l.wi); put(l.wo);
+      put(l.q); put(l.k); put(l.v); put(l.o); put(l.cq); put(l.co); put(l.wi); put(l.wi1); put(l.wo);
       e->buckets[0][e->mi.dec.size() - 1 - li] = klab_engine::Bucket{g0, g - g0};  // backward visits the last layer first
     }
     e->kvall_g_off = g;
@@ -378,7 +390,7 @@ void plan_grads(klab_engine* e) {
     for (size_t li = 0; li < e->mi.enc.size(); ++li) {
       auto& l = e->mi.enc[li];
       const long g0 = g;
-      put(l.q); put(l.k); put(l.v); put(l.o); put(l.wi); put(l.wo);
+      put(l.q); put(l.k); put(l.v); put(l.o); put(l.wi); put(l.wi1); put(l.wo);
       e->buckets[1][e->mi.enc.size() - 1 - li] = klab_engine::Bucket{g0, g - g0};
     }
     e->seg_len[1] = g - e->seg_off[1];
@@ -442,6 +454,7 @@ void plan_t5_stack(Bump& b, const klab_t5_cfg& c, int nl, bool dec, bool save, i
         l.lse2 = (float*)b.take((size_t)B * H * L * 4); l.rstd2 = (float*)b.take((size_t)M * 4);
       }
       l.xn3 = b.take((size_t)M * d * es); l.hmid = b.take((size_t)M * ff * es); l.rstd3 = (float*)b.take((size_t)M * 4);
+      l.ab = c.ffn_gated ? b.take((size_t)M * 2 * ff * es) : nullptr;
       shared_l = l;
     } else {
       l = shared_l;
@@ -522,6 +535,7 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
   e->dc_rstd = (float*)b.take((size_t)B * 4);
   e->dc_xn = b.take((size_t)B * d * es); e->dc_q = b.take((size_t)B * inner * es); e->dc_ctx = b.take((size_t)B * inner * es);
   e->dc_hmid = b.take((size_t)B * ff * es); e->dc_out = b.take((size_t)B * d * es);
+  e->dc_ab = c.main.ffn_gated ? b.take((size_t)B * 2 * ff * es) : nullptr;
   e->dc_logits = b.take((size_t)B * c.main.vocab * es);
   e->loss_row = (float*)b.take((size_t)Md * 4);
   const long Mx = Me > Md ? Me : Md;
@@ -534,7 +548,8 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
     e->dy_pool.assign(3 * nl + 2, nullptr); e->dhmid_pool.assign(nl, nullptr); e->dqkv_pool.assign(nl, nullptr);
     e->dqc_pool.assign(c.main.n_dec_layers, nullptr);
     for (auto& q : e->dy_pool) q = b.take((size_t)Mx * d * es);
-    for (auto& q : e->dhmid_pool) q = b.take((size_t)Mx * ff * es);
+    for (auto& q : e->dhmid_pool) q = b.take((size_t)Mx * (c.main.ffn_gated ? 2 * ff : ff) * es);  // gated: d(a) | d(b)
+    e->dh_ff = c.main.ffn_gated ? b.take((size_t)Mx * ff * es) : nullptr;
     for (auto& q : e->dqkv_pool) q = b.take((size_t)Mx * 3 * inner * es);
     for (auto& q : e->dqc_pool) q = b.take((size_t)Md * inner * es);
   }
@@ -827,7 +842,10 @@ int t5_stack_forward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Par
     }
     // --- feed forward (HF/t5:83-94,137-141) ---
     RC(rms_fwd_for_linear(c, s.h[j], W[l.ln2], b.xn3, b.rstd3, M, d, cfg.ln_eps));
-    {
+    if (cfg.ffn_gated) {  // wi_0 | wi_1 as one N = 2 d_ff product, then the gate (HF T5DenseGatedActDense)
+      RC(linear_fwd(c, b.xn3, M, d, P[l.wi].warena_off, 2 * ff, b.ab, 2 * ff, c.dt));
+      RC(klab_geglu_fwd(b.ab, 2 * ff, b.hmid, ff, c.dt, M, ff, p, c.e->seed_dev, tag_of(stack_id, (int)i, SITE_MID), c.ws()));
+    } else {
       klab_gemm_args g = G0(c, M, ff, d, b.xn3, d, 1, woff(c, P[l.wi].warena_off), d, 1, b.hmid, ff, c.dt);
       g.act = KLAB_ACT_RELU; g.drop_p = p; g.seed_dev = c.e->seed_dev; g.drop_tag = tag_of(stack_id, (int)i, SITE_MID);
       RC(fwd_gemm(c, g, P[l.wi].warena_off));
@@ -974,7 +992,7 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
   const bool kv_in_queue = dec && dkv_all && Gflat == e->G[2] && !e->use_graph && e->kvall_g_off >= 0;
   if (group_on && Ln >= 3 && Gflat == e->G[2] && !e->use_graph) {
     auto T2 = [](int n, int k) { return (long)((n + 255) / 256) * ((k + 255) / 256); };
-    const long tl = T2(d, ff) + T2(ff, d) + T2(d, inner) + T2(3 * inner, d) + (dec ? T2(d, inner) + T2(inner, d) + (kv_in_queue ? T2(2 * inner, d) : 0) : 0);
+    const long tl = T2(d, ff) + T2(cfg.ffn_gated ? 2 * ff : ff, d) + T2(d, inner) + T2(3 * inner, d) + (dec ? T2(d, inner) + T2(inner, d) + (kv_in_queue ? T2(2 * inner, d) : 0) : 0);
     const int per_group = (int)((GROUP_TILES + tl - 1) / tl), per_layer = dec ? 7 : 4;
     if (per_group >= 2) {
       const int body = Ln - 1;
@@ -996,13 +1014,20 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
     // ---------------- FFN ----------------
     --j;
     wq.push(dy, d, b.hmid, ff, M, d, ff, G(l.wo));
-    {
-      klab_gemm_args g = G0(c, M, ff, d, dy, d, 1, woff(c, P[l.wo].warena_off), ff, 0, dhmid, ff, c.dt);
-      g.aux = b.hmid; g.ldaux = ff; g.aux_mode = KLAB_AUX_NONZERO; g.aux_scale = inv_keep;
-      RC(klab_gemm(&g, c.ws()));
+    if (cfg.ffn_gated) {  // wo dgrad -> gate backward (d(a) | d(b) side by side) -> ONE wgrad [2 d_ff, d] and ONE K = 2 d_ff dgrad
+      RC(linear_dgrad(c, dy, d, M, d, P[l.wo].warena_off, ff, e->dh_ff, c.dt));
+      RC(klab_geglu_bwd(e->dh_ff, ff, b.ab, 2 * ff, dhmid, 2 * ff, c.dt, M, ff, p, e->seed_dev, tag_of(stack_id, i, SITE_MID), c.ws()));
+      wq.push(dhmid, 2 * ff, b.xn3, d, M, 2 * ff, d, G(l.wi));  // wi_0 | wi_1 grads are adjacent
+      RC(linear_dgrad(c, dhmid, 2 * ff, M, 2 * ff, P[l.wi].warena_off, d, e->dxn, KLAB_F32));
+    } else {
+      {
+        klab_gemm_args g = G0(c, M, ff, d, dy, d, 1, woff(c, P[l.wo].warena_off), ff, 0, dhmid, ff, c.dt);
+        g.aux = b.hmid; g.ldaux = ff; g.aux_mode = KLAB_AUX_NONZERO; g.aux_scale = inv_keep;
+        RC(klab_gemm(&g, c.ws()));
+      }
+      wq.push(dhmid, ff, b.xn3, d, M, ff, d, G(l.wi));
+      RC(linear_dgrad(c, dhmid, ff, M, ff, P[l.wi].warena_off, d, e->dxn, KLAB_F32));
     }
-    wq.push(dhmid, ff, b.xn3, d, M, ff, d, G(l.wi));
-    RC(linear_dgrad(c, dhmid, ff, M, ff, P[l.wi].warena_off, d, e->dxn, KLAB_F32));
     {
       const uint32_t tprev = dec ? tag_of(stack_id, i, SITE_XOUT) : tag_of(stack_id, i, SITE_ATTN_OUT);
       dy = next_dy();
@@ -1221,6 +1246,9 @@ int swin_backward(const Ctx& c, const float* dh0, float p_in);
 // ================================================================================================
 // C ABI
 // ================================================================================================
+extern "C" int klab_sizeof_t5_cfg(void) { return (int)sizeof(klab_t5_cfg); }
+extern "C" int klab_sizeof_model_cfg(void) { return (int)sizeof(klab_model_cfg); }
+
 extern "C" klab_engine* klab_engine_create(const klab_model_cfg* cfg) {
   if (!cfg) return nullptr;
   if (cfg->dtype != KLAB_F32 && cfg->dtype != KLAB_BF16 && cfg->dtype != KLAB_FP8) return nullptr;
@@ -1229,6 +1257,12 @@ extern "C" klab_engine* klab_engine_create(const klab_model_cfg* cfg) {
   const long Cl = (long)s.embed_dim << (s.n_stages - 1);
   // no projection between the towers: ref/models/model.py:23 concatenates on the sequence axis
   if (Cl != cfg->main.d_model || cfg->lang.d_model != cfg->main.d_model) return nullptr;
+  for (const klab_t5_cfg* t : {&cfg->lang, &cfg->main}) {
+    if (!t->ffn_gated) continue;
+    // gated feed-forward: bf16 / fp32 only (the fp8 forward has no gate pass); wi_0 | wi_1 must be exactly adjacent in the 16-element
+    // aligned weight arena and in the 8-element aligned gradient buffer, and the gate kernels move 16-byte vectors
+    if (cfg->dtype == KLAB_FP8 || (t->d_ff & 7) || (((long)t->d_ff * t->d_model) & 15)) return nullptr;
+  }
   klab_engine* e = new klab_engine();
   e->cfg = *cfg;
   if (cfg->dtype == KLAB_FP8) { e->fp8 = true; e->cfg.dtype = KLAB_BF16; }  // storage, backward and every non-GEMM kernel: bf16
@@ -1728,14 +1762,14 @@ extern "C" int klab_engine_forward(klab_engine* e, const float* pixels, const lo
   }
   {
     const int Md = B * e->Lt, V = cfg.main.vocab;
-    klab_gemm_args g = G0(c, Md, V, d, e->dec.out_t, d, 1, woff(c, e->P[2][e->mi.shared].warena_off), d, 1, e->logits, V, c.dt);
+    klab_gemm_args g = G0(c, Md, V, d, e->dec.out_t, d, 1, woff(c, e->P[2][e->mi.head].warena_off), d, 1, e->logits, V, c.dt);
     g.alpha = cfg.main.scale_decoder_outputs ? 1.f / sqrtf((float)d) : 1.f;  // HF/t5:1044-1045
     g.name_tag = 1;
     // the LM-head launch stays outside the graphs so that the probe's HIP events can bracket it
     klab_engine::Probe& pr = e->probe[0];
     const bool probe = e->probe_on && pr.n < (int)pr.a.size();
     if (probe) { klab::tl_launch_probe.a = pr.a[pr.n]; klab::tl_launch_probe.b = pr.b[pr.n]; }
-    RC(fwd_gemm(c, g, e->P[2][e->mi.shared].warena_off));
+    RC(fwd_gemm(c, g, e->P[2][e->mi.head].warena_off));
     if (probe) {
       if (klab::tl_launch_probe.a) klab::tl_launch_probe.a = nullptr;  // (a launch path without the hook, e.g. fp8: not recorded)
       else pr.flops[pr.n++] = 2.0 * Md * (double)V * d;
@@ -1815,6 +1849,7 @@ struct DecodeRows {
   int M;
   float* h[2]; float* rstd;
   void *xn, *q, *ctx, *hmid, *out, *logits;
+  void* ab = nullptr;  // gated feed-forward: the two pre-activations [M, 2 d_ff]
   void* cache = nullptr; long cache_layer = 0; int cache_rows = 0;
   int kv_group = 1; const int* kv_slot = nullptr; long slot_ld = 0;
 };
@@ -1860,15 +1895,20 @@ int decode_rows(klab_engine* e, const Ctx& c, int t, const long long* tokens, co
     RC(proj_res(r.ctx, inner, P[l.co].warena_off));
     // feed forward
     RC(klab_rmsnorm_fwd(h, W[l.ln2], r.xn, c.dt, nullptr, r.rstd, M, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
-    RC(linear_fwd(c, r.xn, M, d, P[l.wi].warena_off, ff, r.hmid, ff, c.dt, nullptr, KLAB_ACT_RELU));
+    if (cfg.ffn_gated) {
+      RC(linear_fwd(c, r.xn, M, d, P[l.wi].warena_off, 2 * ff, r.ab, 2 * ff, c.dt));
+      RC(klab_geglu_fwd(r.ab, 2 * ff, r.hmid, ff, c.dt, M, ff, 0.f, nullptr, 0, c.ws()));
+    } else {
+      RC(linear_fwd(c, r.xn, M, d, P[l.wi].warena_off, ff, r.hmid, ff, c.dt, nullptr, KLAB_ACT_RELU));
+    }
     RC(proj_res(r.hmid, ff, P[l.wo].warena_off));
   }
   RC(klab_rmsnorm_fwd(h, W[e->mi.dec_final], r.out, c.dt, nullptr, r.rstd, M, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
   {
     const int V = cfg.vocab;
-    klab_gemm_args g = G0(c, M, V, d, r.out, d, 1, woff(c, P[e->mi.shared].warena_off), d, 1, r.logits, V, c.dt);
+    klab_gemm_args g = G0(c, M, V, d, r.out, d, 1, woff(c, P[e->mi.head].warena_off), d, 1, r.logits, V, c.dt);
     g.alpha = cfg.scale_decoder_outputs ? 1.f / sqrtf((float)d) : 1.f;  // HF/t5:1044-1045
-    RC(fwd_gemm(c, g, P[e->mi.shared].warena_off));
+    RC(fwd_gemm(c, g, P[e->mi.head].warena_off));
   }
   return 0;
 }
@@ -1887,7 +1927,7 @@ extern "C" int klab_engine_decode_step(klab_engine* e, int t, const long long* p
   DecodeRows r;
   r.M = e->B;
   r.h[0] = e->dc_h[0]; r.h[1] = e->dc_h[1]; r.rstd = e->dc_rstd;
-  r.xn = e->dc_xn; r.q = e->dc_q; r.ctx = e->dc_ctx; r.hmid = e->dc_hmid; r.out = e->dc_out; r.logits = e->dc_logits;
+  r.xn = e->dc_xn; r.q = e->dc_q; r.ctx = e->dc_ctx; r.hmid = e->dc_hmid; r.ab = e->dc_ab; r.out = e->dc_out; r.logits = e->dc_logits;
   return decode_rows(e, c, t, prev_tokens, r);
 }
 
@@ -1954,6 +1994,7 @@ size_t plan_gen(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp, 
   r.M = (int)M;
   r.h[0] = (float*)b.take(M * d * 4); r.h[1] = (float*)b.take(M * d * 4); r.rstd = (float*)b.take(M * 4);
   r.xn = b.take(M * d * es); r.q = b.take(M * inner * es); r.ctx = b.take(M * inner * es); r.hmid = b.take(M * ff * es);
+  r.ab = cfg.ffn_gated ? b.take(M * 2 * ff * es) : nullptr;
   r.out = b.take(M * d * es); r.logits = b.take(M * V * es);
   r.cache_layer = M * Lm * 3 * inner; r.cache_rows = Lm;
   r.cache = b.take((size_t)cfg.n_dec_layers * r.cache_layer * es);
@@ -2161,7 +2202,7 @@ static int backward_segment(klab_engine* e, int segment, const float* dloss_dev,
     }
     {  // d(dec_out) [Md,d] = dlogits [Md,V] @ shared [V,d]: K = vocabulary over only Md*d outputs => split-K, f32 atomics
       RC((int)hipMemsetAsync(e->dxn, 0, (size_t)Md * d * 4, c.s));
-      klab_gemm_args g = G0(c, Md, d, V, e->logits, V, 1, woff(c, e->P[2][e->mi.shared].warena_off), d, 0, e->dxn, d, KLAB_F32);
+      klab_gemm_args g = G0(c, Md, d, V, e->logits, V, 1, woff(c, e->P[2][e->mi.head].warena_off), d, 0, e->dxn, d, KLAB_F32);
       g.alpha = alpha; g.alpha_dev = dloss_dev; g.accumulate = 1; g.atomic_ok = 1;
       RC(klab_gemm(&g, c.ws()));
     }
@@ -2169,8 +2210,8 @@ static int backward_segment(klab_engine* e, int segment, const float* dloss_dev,
     // the weight gradient trails BEHIND the dgrad on the side stream (run side by side the two chip-filling GEMMs took
     // longer than one after the other); it then overlaps the decoder's first, latency-bound backward kernels
     RC(side_after_main(c));
-    {  // d shared [V,d] = dlogits^T @ dec_out  (first of the tied weight's three contributors)
-      klab_gemm_args g = G0(cs, V, d, Md, e->logits, V, 0, e->dec.out_t, d, 0, Gm + e->P[2][e->mi.shared].grad_off, d, KLAB_F32);
+    {  // d head [V,d] = dlogits^T @ dec_out  (tied: the first of shared.weight's three contributors; untied: lm_head.weight's only one)
+      klab_gemm_args g = G0(cs, V, d, Md, e->logits, V, 0, e->dec.out_t, d, 0, Gm + e->P[2][e->mi.head].grad_off, d, KLAB_F32);
       g.alpha = alpha; g.alpha_dev = dloss_dev; g.accumulate = 1; g.atomic_ok = 1;
       RC(klab_gemm(&g, cs.ws()));
     }

@@ -65,6 +65,7 @@ class T5Config:
     pad_token_id: Optional[int] = 0
     eos_token_id: int = 1
     scale_decoder_outputs: bool = True
+    tie_word_embeddings: bool = True  # False (T5 v1.1 / Flan-T5): lm_head.weight is a parameter of its own
 
     def __post_init__(self):
         if self.num_decoder_layers is None:
@@ -78,6 +79,7 @@ class T5Config:
             c.decoder_start_token_id = None
         if d.get("tie_word_embeddings", None) is False:  # HF/t5cfg:82-83
             c.scale_decoder_outputs = False
+            c.tie_word_embeddings = False
         return c
 
 
@@ -92,7 +94,7 @@ class CT5Cfg(C.Structure):
     _fields_ = [("vocab", C.c_int), ("d_model", C.c_int), ("d_kv", C.c_int), ("n_heads", C.c_int), ("d_ff", C.c_int),
                 ("n_layers", C.c_int), ("n_dec_layers", C.c_int), ("rel_buckets", C.c_int), ("rel_max_dist", C.c_int),
                 ("dropout", C.c_float), ("ln_eps", C.c_float), ("start_id", C.c_int), ("pad_id", C.c_int),
-                ("scale_decoder_outputs", C.c_int)]
+                ("scale_decoder_outputs", C.c_int), ("ffn_gated", C.c_int), ("tie_lm_head", C.c_int)]
 
 
 class CModelCfg(C.Structure):
@@ -138,6 +140,8 @@ ENGINE_SIGS = {
     "klab_engine_rng_ptr": ([C.c_void_p], C.c_void_p),
     "klab_engine_buffer": ([C.c_void_p, C.c_char_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)], C.c_void_p),
     "klab_gelu_fwd": ([C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p], C.c_int),
+    "klab_sizeof_t5_cfg": ([], C.c_int),
+    "klab_sizeof_model_cfg": ([], C.c_int),
     "klab_swin_cpb_bias_bwd": ([C.c_void_p] * 11 + [C.c_int] * 4 + [C.c_void_p], C.c_int),
     "klab_swin_cpb_bias_bwd_pz": ([C.c_void_p] * 11 + [C.c_int] * 5 + [C.c_void_p], C.c_int),
 }
@@ -156,16 +160,21 @@ def lib():
     return l
 
 
+FEED_FORWARD_PROJ = {"relu": 0, "gated-gelu": 1}  # HF/t5cfg feed_forward_proj -> klab_t5_cfg.ffn_gated
+
+
 def _c_t5(c: T5Config) -> CT5Cfg:
-    if c.feed_forward_proj != "relu":
-        raise NotImplementedError("only the v1.0 ReLU feed-forward is reachable from the reference (ref/modules/config.py:8-9)")
+    if c.feed_forward_proj not in FEED_FORWARD_PROJ:
+        raise NotImplementedError(f"feed_forward_proj {c.feed_forward_proj!r}: only the v1.0 ReLU feed-forward ('relu') and the v1.1 / "
+                                  "Flan-T5 gated gelu_new feed-forward ('gated-gelu') are implemented")
     if c.decoder_start_token_id is None:
         raise ValueError("self.model.config.decoder_start_token_id has to be defined.")  # HF/t5:622-626
     if c.pad_token_id is None:
         raise ValueError("self.model.config.pad_token_id has to be defined.")  # HF/t5:632-633
     return CT5Cfg(c.vocab_size, c.d_model, c.d_kv, c.num_heads, c.d_ff, c.num_layers, c.num_decoder_layers,
                   c.relative_attention_num_buckets, c.relative_attention_max_distance, float(c.dropout_rate),
-                  float(c.layer_norm_epsilon), int(c.decoder_start_token_id), int(c.pad_token_id), int(c.scale_decoder_outputs))
+                  float(c.layer_norm_epsilon), int(c.decoder_start_token_id), int(c.pad_token_id), int(c.scale_decoder_outputs),
+                  FEED_FORWARD_PROJ[c.feed_forward_proj], int(c.tie_word_embeddings))
 
 
 def _c_swin(c: SwinConfig) -> CSwinCfg:
@@ -248,6 +257,8 @@ class Engine:
         if lang.d_model != main.d_model:
             raise RuntimeError(f"Sizes of tensors must match except in dimension 1. Expected size {swin.hidden_size} "
                                f"but got size {lang.d_model} for tensor number 1 in the list.")
+        if dtype == "fp8" and "gated-gelu" in (lang.feed_forward_proj, main.feed_forward_proj):
+            raise NotImplementedError("dtype='fp8' with a gated-gelu feed-forward (T5 v1.1 / Flan-T5) is not implemented: use bf16")
         self._cfg = CModelCfg(_c_swin(swin), _c_t5(lang), _c_t5(main), L.dtype_code(dtype), int(self.train_swin))
         self._lib = lib()
         self._h = self._lib.klab_engine_create(C.byref(self._cfg))

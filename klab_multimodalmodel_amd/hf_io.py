@@ -17,6 +17,12 @@ KNOWN_T5 = {
     "t5-3b": dict(d_model=1024, d_kv=128, d_ff=16384, num_layers=24, num_heads=32),
     "t5-11b": dict(d_model=1024, d_kv=128, d_ff=65536, num_layers=24, num_heads=128),
 }
+# T5 v1.1 and Flan-T5 (same architectures): gated gelu_new feed-forward, LM head untied and unscaled
+_V11 = dict(feed_forward_proj="gated-gelu", tie_word_embeddings=False, scale_decoder_outputs=False)
+for _fam in ("google/t5-v1_1-", "google/flan-t5-"):
+    KNOWN_T5[_fam + "small"] = dict(d_model=512, d_kv=64, d_ff=1024, num_layers=8, num_heads=6, **_V11)
+    KNOWN_T5[_fam + "base"] = dict(d_model=768, d_kv=64, d_ff=2048, num_layers=12, num_heads=12, **_V11)
+    KNOWN_T5[_fam + "large"] = dict(d_model=1024, d_kv=64, d_ff=2816, num_layers=24, num_heads=16, **_V11)
 KNOWN_SWIN = {
     "microsoft/swinv2-tiny-patch4-window8-256": dict(image_size=256, embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window_size=8),
     "microsoft/swinv2-small-patch4-window8-256": dict(image_size=256, embed_dim=96, depths=(2, 2, 18, 2), num_heads=(3, 6, 12, 24), window_size=8),

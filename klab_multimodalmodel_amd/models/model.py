@@ -21,6 +21,12 @@ from ..logits_proc import logits_processor_settings
 TIED_T5 = ("encoder.embed_tokens.weight", "decoder.embed_tokens.weight", "lm_head.weight")  # HF/t5:902-906
 
 
+def tied_t5(cfg: T5Config):
+    """aliases of `shared.weight` in a T5ForConditionalGeneration state dict: the LM head only when the config ties it (T5 v1.1 /
+    Flan-T5 keep `lm_head.weight` as a parameter of its own)"""
+    return TIED_T5 if cfg.tie_word_embeddings else TIED_T5[:2]
+
+
 class _Node(nn.Module):
     """anonymous container so that dotted HuggingFace names become real module paths."""
 
@@ -31,6 +37,7 @@ class HFTree(nn.Module):
     def __init__(self, specs, tied: Dict[str, str] = None):
         super().__init__()
         self._order: List[str] = []
+        self._tied = tuple((tied or {}).keys())
         for spec in specs:
             self._register(spec.name, nn.Parameter(torch.empty(spec.shape, dtype=torch.float32)))
             self._order.append(spec.name)
@@ -55,7 +62,7 @@ def _init_t5_(tree: HFTree, cfg: T5Config, gen):
     d, dk, h, ff = cfg.d_model, cfg.d_kv, cfg.num_heads, cfg.d_ff
     with torch.no_grad():
         for n, p in tree.named_parameters():
-            if n in TIED_T5:
+            if n in tree._tied:
                 continue
             if n.endswith("layer_norm.weight"):
                 p.fill_(1.0)
@@ -67,7 +74,7 @@ def _init_t5_(tree: HFTree, cfg: T5Config, gen):
                 std = d ** -0.5
             elif n.endswith(".o.weight"):
                 std = (h * dk) ** -0.5
-            elif n.endswith("wi.weight"):
+            elif n.endswith(("wi.weight", "wi_0.weight", "wi_1.weight")):
                 std = d ** -0.5
             elif n.endswith("wo.weight"):
                 std = ff ** -0.5
@@ -201,7 +208,7 @@ class MyModel(nn.Module):
         self.compute_dtype = {"bf16": torch.bfloat16, "fp32": torch.float32, "fp8": "fp8", torch.bfloat16: torch.bfloat16,
                               torch.float32: torch.float32}[dt]
         self._engine = Engine(swin_cfg, lang_cfg, main_cfg, self.compute_dtype, bool(args.image_model_train))
-        tied = {a: "shared.weight" for a in TIED_T5}
+        tied = {a: "shared.weight" for a in tied_t5(main_cfg)}
         self.language_model = HFTree(self._engine.params["lang"], {"encoder.embed_tokens.weight": "shared.weight"})
         self.image_model = HFTree(self._engine.params["swin"])
         self.transformer = HFTree(self._engine.params["main"], tied)
@@ -241,7 +248,7 @@ class MyModel(nn.Module):
     @staticmethod
     def _load_tree(tree, sd):
         own = tree.state_dict()
-        missing = [k for k in own if k not in sd and k not in TIED_T5 and k != "encoder.embed_tokens.weight"]
+        missing = [k for k in own if k not in sd and k not in tree._tied]
         if "shared.weight" not in sd and "encoder.embed_tokens.weight" in sd:
             sd = dict(sd)
             sd["shared.weight"] = sd["encoder.embed_tokens.weight"]

@@ -148,6 +148,25 @@ def gelu_fwd(z, a):
     L.check(lib.klab_gelu_fwd(z.data_ptr(), a.data_ptr(), L.dtype_code(z.dtype), z.numel(), L.stream_ptr()), "klab_gelu_fwd")
 
 
+def geglu_fwd(ab, h, drop_p=0.0, seed_dev=None, tag=0):
+    """gate of the T5 v1.1 feed-forward: h [M, F] = dropout(gelu_new(ab[:, :F]) * ab[:, F:]); ab [M, 2F] (row stride free)"""
+    lib = L.load()
+    M, F = h.shape
+    assert ab.shape == (M, 2 * F) and ab.dtype == h.dtype and ab.stride(1) == 1 and h.stride(1) == 1
+    L.check(lib.klab_geglu_fwd(ab.data_ptr(), ab.stride(0), h.data_ptr(), h.stride(0), L.dtype_code(h.dtype), M, F, float(drop_p),
+                               L.ptr(seed_dev), int(tag), L.stream_ptr()), "klab_geglu_fwd")
+
+
+def geglu_bwd(dh, ab, dab, drop_p=0.0, seed_dev=None, tag=0):
+    """dab [M, 2F] = (d a | d b) of geglu_fwd from dh [M, F] and the pre-activations ab [M, 2F]; the mask is regenerated from (seed, tag)"""
+    lib = L.load()
+    M, F = dh.shape
+    assert ab.shape == (M, 2 * F) and dab.shape == (M, 2 * F) and ab.dtype == dh.dtype == dab.dtype
+    assert ab.stride(1) == 1 and dh.stride(1) == 1 and dab.stride(1) == 1
+    L.check(lib.klab_geglu_bwd(dh.data_ptr(), dh.stride(0), ab.data_ptr(), ab.stride(0), dab.data_ptr(), dab.stride(0),
+                               L.dtype_code(dh.dtype), M, F, float(drop_p), L.ptr(seed_dev), int(tag), L.stream_ptr()), "klab_geglu_bwd")
+
+
 def gelu_fwd_q8(z, a, a8, ascale):
     lib = L.load()
     rows, F = z.shape
