@@ -451,6 +451,37 @@ int klab_engine_adam_step_segment(klab_engine* e, int segment, float* m, float* 
 int klab_adam_step_range(const void* desc_dev, int ndesc, long begin4, long end4, const float* grads, float* m, float* v, void* arena,
                          int dtype, float lr, float beta1, float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
                          void* stream);
+/* Adafactor (the rule of transformers.optimization.Adafactor) for ALL parameters of the trainable T5 in four launches, whatever
+ * the number of tensors: statistics (row / column sums of g^2 + eps0, sum p^2), their reduction (EMA into R / C, mean R, RMS(p)),
+ * sum u^2, apply.  Tensors with >= 2 dims are factored (rows = product of all dims but the last), 1-D tensors keep a full second
+ * moment.  No floating-point atomics: a step is bit-reproducible.  No host read: beta2t = 1 - t^decay_rate, one_minus_beta2t and
+ * rel_step (min(1e-2 or 1e-6 t, 1/sqrt t), or lr) are host scalars; lr_t = rel_step * max(eps1, RMS(p)) (scale_parameter) and the
+ * clip factor max(1, RMS(u) / clip_threshold) are computed on the device.  Like klab_engine_adam_step it also refreshes the
+ * compute-dtype copies of the GEMM weights.  Caller-owned f32 buffers, sized by klab_engine_adafactor_state_elems:
+ *   state    R | C (each padded to 4 elements) per factored tensor, V per 1-D tensor; zero before the first step
+ *   m        first moment laid out like the "main" flat gradient buffer, or NULL (beta1 is then ignored); one_minus_beta1 is
+ *            1 - beta1 formed in double by the caller, as one_minus_beta2t is (1.f - 0.9f is 2e-7 away from 0.1)
+ *   scalars  4 per tensor: mean(R), RMS(p) before the update, RMS(u), unused
+ *   scratch  the factors rsqrt(R / mean R) | rsqrt(C), per-tile partial sums and per-tile column sums
+ * KLAB_ERR_UNSUPPORTED where the Adam table is unusable, for rows wider than 8192 (2048 when not a multiple of 4) and for
+ * tensors of 2^31 elements or more. */
+int klab_engine_adafactor_state_elems(klab_engine* e, long* state_elems, long* scalar_elems, long* scratch_elems);
+int klab_engine_adafactor_step(klab_engine* e, float* state, float* m, float* scalars, float* scratch, float beta2t, float one_minus_beta2t,
+                               float eps0, float eps1, float rel_step, float clip_threshold, float beta1, float one_minus_beta1,
+                               float weight_decay, int scale_parameter, void* stream);
+/* the engine's descriptor table copied to the host (10 longs per tensor, below), in the order of the flat-gradient views of
+ * segment 0 then segment 1: where each tensor's R | C | V lives in `state`.  Returns the number of tensors (> 0) or an error;
+ * synchronises. */
+int klab_engine_adafactor_layout(klab_engine* e, int max_n, long* out);
+/* the kernels behind it.  desc = device array of {float* p; long grad_off; long arena_off (<0: none); long rows; long cols;
+ * long state_off; long tile0; long tile_len; long part_off; long factored}; klab_adafactor_plan fills, for n tensors of
+ * (rows, cols, factored), out[4 i ..] = {state_off, tile0, tile_len, part_off} and totals = {state elems, tiles, scratch
+ * elems, scalar elems}.  rows is ignored (1) for an unfactored tensor, whose length is cols. */
+int klab_adafactor_plan(int n, const long* rows, const long* cols, const int* factored, long* out, long* totals);
+int klab_adafactor_step(const void* desc_dev, int ndesc, long state_elems, long ntiles, const float* grads, float* state, float* m,
+                        float* scalars, float* scratch, void* arena, int dtype, float beta2t, float one_minus_beta2t, float eps0, float eps1,
+                        float rel_step, float clip_threshold, float beta1, float one_minus_beta1, float weight_decay, int scale_parameter,
+                        void* stream);
 /* Greedy decoding with a K/V cache (ref/models/model.py:27-28, HF/t5:308-332): the decoder over ONE new position t >= 1 per
  * sample.  Precondition: a klab_engine_forward in evaluation mode on this binding (prefill: encoder, cross K/V, position 0),
  * then steps 1, 2, ... in order; the per-layer q|k|v buffers of the binding are the cache.  prev_tokens [B] (device) = ids

@@ -135,6 +135,7 @@ struct klab_engine {
   const void* q8_src[2] = {nullptr, nullptr}; int q8_rows[2] = {0, 0}, q8_k[2] = {0, 0};
   void* cast_desc = nullptr; int n_cast = 0; long cast_total4 = 0;      // trainable GEMM weights (cast every forward)
   void* adam_desc = nullptr; int n_adam = 0; long adam_total4 = 0, adam_split4 = 0;
+  void* af_desc = nullptr; int n_af = 0; long af_totals[4] = {0, 0, 0, 0};  // Adafactor: state elems, tiles, scratch elems, scalar elems
   // RMS-norm weight gradients of a stack: per-workgroup partials of every norm, folded by one reduction per stack
   float* rms_part = nullptr; long rms_part_stride = 0; float** rms_dst_dev[2] = {nullptr, nullptr}; int rms_ncalls[2] = {0, 0};
   void* cast_desc_frozen = nullptr; int n_cast_frozen = 0; long cast_total4_frozen = 0;  // frozen towers (cast when dirty)
@@ -515,6 +516,7 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
   e->cast_desc = b.take(sizeof(long) * 3 * 2 * (e->P[0].size() + e->P[1].size() + e->P[2].size() + c.swin.embed_dim + 1));
   e->fcast_desc = b.take(sizeof(long) * 3 * (e->P[0].size() + 1));
   e->adam_desc = b.take(sizeof(long) * 4 * (e->P[2].size() + 1));
+  e->af_desc = b.take(sizeof(long) * 10 * (e->P[2].size() + 1));
   {
     const int nle = c.main.n_layers, nldx = c.main.n_dec_layers;
     const int ncmax = (2 * nle + 1) > (3 * nldx + 1) ? (2 * nle + 1) : (3 * nldx + 1);
@@ -1485,6 +1487,7 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
       if (er != hipSuccess) return (int)er;
     }
   }
+  std::vector<long> adam_tab;  // host copies of both optimizer tables stay alive until their one synchronise
   {  // fused Adam descriptors: every trainable tensor of the main T5 (tied tables appear once)
     std::vector<long> d;
     long pre = 0; int n = 0;
@@ -1502,10 +1505,39 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
       }
     }
     e->n_adam = ok ? n : 0; e->adam_total4 = pre;
-    if (e->n_adam) {
+    if (e->n_adam) {  // (the synchronise is shared with the Adafactor table below: adam_tab lives until then)
       hipError_t er = hipMemcpyAsync(e->adam_desc, d.data(), d.size() * sizeof(long), hipMemcpyHostToDevice, hs);
       if (er != hipSuccess) return (int)er;
-      er = hipStreamSynchronize(hs);
+    }
+    adam_tab.swap(d);
+  }
+  {  // fused Adafactor descriptors: the same tensors in the same order; rows = product of all dims but the last, 1-D = unfactored
+    std::vector<long> rows, cols, idx;
+    std::vector<int> fact;
+    for (int seg = 0; seg < 2; ++seg)
+      for (size_t i = 0; i < e->P[2].size(); ++i) {
+        const ParamInfo& p = e->P[2][i];
+        if (p.grad_off < 0 || (p.grad_off >= e->seg_off[1]) != (seg == 1)) continue;
+        const long c = p.shape.empty() ? 1 : p.shape.back();
+        fact.push_back(p.shape.size() >= 2); rows.push_back(p.shape.size() >= 2 ? p.numel / c : 1);
+        cols.push_back(p.shape.size() >= 2 ? c : p.numel); idx.push_back((long)i);
+      }
+    const int n = (int)idx.size();
+    std::vector<long> plan((size_t)n * 4), d;
+    e->n_af = 0;
+    if (e->n_adam == n && n > 0 && klab_adafactor_plan(n, rows.data(), cols.data(), fact.data(), plan.data(), e->af_totals) == KLAB_OK) {
+      for (int k = 0; k < n; ++k) {
+        const ParamInfo& p = e->P[2][idx[k]];
+        const long v[10] = {(long)e->W[2][idx[k]], p.grad_off, p.warena_off, rows[k], cols[k], plan[k * 4 + 0], plan[k * 4 + 1],
+                            plan[k * 4 + 2], plan[k * 4 + 3], (long)fact[k]};
+        d.insert(d.end(), v, v + 10);
+      }
+      hipError_t er = hipMemcpyAsync(e->af_desc, d.data(), d.size() * sizeof(long), hipMemcpyHostToDevice, hs);
+      if (er != hipSuccess) return (int)er;
+      e->n_af = n;
+    }
+    if (e->n_adam) {
+      hipError_t er = hipStreamSynchronize(hs);
       if (er != hipSuccess) return (int)er;
     }
   }
@@ -1681,6 +1713,30 @@ extern "C" int klab_engine_adam_step(klab_engine* e, float* m, float* v, float l
   if (!e->n_adam) return KLAB_ERR_UNSUPPORTED;
   return klab_adam_step(e->adam_desc, e->n_adam, e->adam_total4, e->G[2], m, v, e->warena, e->cfg.dtype, lr, beta1, beta2, eps, weight_decay,
                         bias_corr1, bias_corr2, stream);
+}
+
+extern "C" int klab_engine_adafactor_state_elems(klab_engine* e, long* state_elems, long* scalar_elems, long* scratch_elems) {
+  if (!e || !state_elems || !scalar_elems || !scratch_elems) return KLAB_ERR_BADARG;
+  if (!e->n_af) return KLAB_ERR_UNSUPPORTED;
+  *state_elems = e->af_totals[0]; *scalar_elems = e->af_totals[3]; *scratch_elems = e->af_totals[2];
+  return KLAB_OK;
+}
+
+extern "C" int klab_engine_adafactor_layout(klab_engine* e, int max_n, long* out) {
+  if (!e || !out) return KLAB_ERR_BADARG;
+  if (!e->n_af) return KLAB_ERR_UNSUPPORTED;
+  if (max_n < e->n_af) return KLAB_ERR_BADARG;
+  hipError_t er = hipMemcpy(out, e->af_desc, sizeof(long) * 10 * e->n_af, hipMemcpyDeviceToHost);
+  return er != hipSuccess ? (int)er : e->n_af;
+}
+
+extern "C" int klab_engine_adafactor_step(klab_engine* e, float* state, float* m, float* scalars, float* scratch, float beta2t,
+                                          float one_minus_beta2t, float eps0, float eps1, float rel_step, float clip_threshold, float beta1,
+                                          float one_minus_beta1, float weight_decay, int scale_parameter, void* stream) {
+  if (!e || !e->bound || !state || !scalars || !scratch || !e->G[2]) return KLAB_ERR_BADARG;
+  if (!e->n_af) return KLAB_ERR_UNSUPPORTED;
+  return klab_adafactor_step(e->af_desc, e->n_af, e->af_totals[0], e->af_totals[1], e->G[2], state, m, scalars, scratch, e->warena, e->cfg.dtype,
+                             beta2t, one_minus_beta2t, eps0, eps1, rel_step, clip_threshold, beta1, one_minus_beta1, weight_decay, scale_parameter, stream);
 }
 
 extern "C" int klab_engine_adam_step_segment(klab_engine* e, int segment, float* m, float* v, float lr, float beta1, float beta2, float eps,

@@ -132,6 +132,10 @@ ENGINE_SIGS = {
                                C.c_float, C.c_void_p], C.c_int),
     "klab_engine_adam_step_segment": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.c_float, C.c_float, C.c_void_p], C.c_int),
+    "klab_engine_adafactor_state_elems": ([C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)], C.c_int),
+    "klab_engine_adafactor_layout": ([C.c_void_p, C.c_int, C.POINTER(C.c_long)], C.c_int),
+    "klab_engine_adafactor_step": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_float] * 9 + [C.c_int, C.c_void_p],
+                                   C.c_int),
     "klab_engine_probe_enable": ([C.c_void_p, C.c_int], C.c_int),
     "klab_engine_probe_read": ([C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_double)], C.c_int),
     "klab_engine_loss_ptr": ([C.c_void_p], C.c_void_p),
@@ -453,6 +457,31 @@ class Engine:
             return
         L.check(self._lib.klab_engine_adam_step(self._h, m.data_ptr(), v.data_ptr(), lr, beta1, beta2, eps, weight_decay, bias_corr1,
                                                 bias_corr2, L.stream_ptr()), "klab_engine_adam_step")
+
+    def adafactor_sizes(self):
+        """(state, scalar, scratch) element counts of the f32 buffers klab_engine_adafactor_step works on"""
+        a, b, c = C.c_long(0), C.c_long(0), C.c_long(0)
+        L.check(self._lib.klab_engine_adafactor_state_elems(self._h, C.byref(a), C.byref(b), C.byref(c)), "klab_engine_adafactor_state_elems")
+        return a.value, b.value, c.value
+
+    def adafactor_layout(self):
+        """per tensor, in scalar-slot order: (param data_ptr, rows, cols, state_off, factored).  R = state[off : off + rows],
+        C = state[off + round_up4(rows) : ... + cols]; an unfactored tensor's V = state[off : off + cols].  Synchronises."""
+        n = self.adafactor_sizes()[1] // 4
+        buf = (C.c_long * (10 * n))()
+        rc = self._lib.klab_engine_adafactor_layout(self._h, n, buf)
+        if rc != n:
+            L.check(rc if rc < 0 else L.ERR_BADARG, "klab_engine_adafactor_layout")
+        return [(buf[10 * i], buf[10 * i + 3], buf[10 * i + 4], buf[10 * i + 5], bool(buf[10 * i + 9])) for i in range(n)]
+
+    def adafactor_step(self, state, m, scalars, scratch, beta2t, one_minus_beta2t, eps0, eps1, rel_step, clip_threshold, beta1,
+                       one_minus_beta1, weight_decay, scale_parameter):
+        """transformers' Adafactor update for every parameter of the trainable T5 in four launches (+ refreshed bf16 copies);
+        m = None: no first moment"""
+        L.check(self._lib.klab_engine_adafactor_step(self._h, state.data_ptr(), None if m is None else m.data_ptr(), scalars.data_ptr(),
+                                                     scratch.data_ptr(), beta2t, one_minus_beta2t, eps0, eps1, rel_step, clip_threshold,
+                                                     beta1, one_minus_beta1, weight_decay, int(bool(scale_parameter)), L.stream_ptr()),
+                "klab_engine_adafactor_step")
 
     def set_bucket_events(self, on=True):
         """record the per-layer bucket events during backward (a data-parallel reducer is attached)"""

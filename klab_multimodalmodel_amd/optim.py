@@ -1,4 +1,4 @@
-"""Fused Adam for the native MyModel.
+"""Fused optimizers for the native MyModel: Adam and Adafactor (`FusedAdafactor`, at the end of the file).
 
 Drop-in for the reference's `torch.optim.Adam(model.module.transformer.parameters(), lr=args.lr)` (ref/train.py:28): same
 constructor arguments, same update rule (no amsgrad, L2 weight decay), `param_groups` / LR schedulers / `zero_grad` /
@@ -16,6 +16,7 @@ latency-bound encoder backward; `step()` then updates segment 1 and joins.  Same
 every step after a change of circumstances (`_fast_ok`) run the ordinary way.  Measured on configs[1] (one MI355X): 6.67 ms/step
 against 6.63 without -- the co-running streaming kernel slows the chain by as much as it hides -- so nothing turns it on by default.
 """
+import math
 import weakref
 
 import torch
@@ -225,3 +226,256 @@ class FusedAdam(Optimizer):
             self._fallback = _TorchAdam(self.param_groups)
             self._fallback.param_groups = self.param_groups
             self._fallback.state = self.state
+
+
+class FusedAdafactor(Optimizer):
+    """Drop-in for `transformers.optimization.Adafactor` (the optimizer T5 v1.1 / Flan-T5 were pre-trained with): the same
+    constructor, the same update rule, the same `state_dict()` keys (`step`, `RMS`, `exp_avg_sq_row` + `exp_avg_sq_col` or
+    `exp_avg_sq`, `exp_avg` with `beta1`), so a state saved by either class loads into the other and continues.
+
+    When the parameters are exactly the trainable T5 of one bound klab MyModel and their `.grad`s are views of the engine's flat
+    gradient buffer (the test of `FusedAdam._fast_ok`), `step()` is four HIP launches over all tensors (csrc/adafactor.hip):
+    statistics, their reduction, the update's norm, apply.  The step reads nothing back: `t`, `beta2t` and the relative step are
+    host scalars, everything that depends on RMS(p) / RMS(u) stays on the device.  It has no floating-point atomics, so a step
+    is bit-reproducible, and the apply pass also rewrites the compute-dtype copies the next forward's GEMMs read.  In every other
+    situation (foreign parameters, CPU tensors, several groups, an unbound engine, a tensor shape the kernels do not cover) the
+    same rule runs per parameter in plain torch, inside this file: `transformers` is never imported.  The state moves between
+    the two forms as needed.
+
+    Not supported: `step_in_backward` and segment-wise updates (FusedAdam's overlap with the backward / the DDP all-reduce).
+    RMS(u) of a tensor needs all of its gradient, and the step joins a pending klab DDP reduction before it starts."""
+
+    def __init__(self, params, lr=None, eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, weight_decay=0.0,
+                 scale_parameter=True, relative_step=True, warmup_init=False):
+        if lr is not None and relative_step:
+            raise ValueError("Cannot combine manual `lr` and `relative_step=True` options")
+        if warmup_init and not relative_step:
+            raise ValueError("`warmup_init=True` requires `relative_step=True`")
+        defaults = dict(lr=lr, eps=eps, clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=beta1, weight_decay=weight_decay,
+                        scale_parameter=scale_parameter, relative_step=relative_step, warmup_init=warmup_init)
+        super().__init__(params, defaults)
+        self._flat_live = False  # True: the state lives in the flat buffers below, self.state is stale
+        self._steps = 0
+        self._st = self._m = self._scal = self._scratch = None
+        self._slots = None  # [(param, rows, cols, state_off, factored, m_off)] in scalar-slot order
+        self._owner = None
+        self._bound_key = None
+        self._refused = None  # (model, binding) whose tensors the kernels turned down
+        self._fb_reason = None
+
+    # ---- the rule's host scalars ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _rel_step(group, t):
+        if group["relative_step"]:
+            return min(1e-6 * t if group["warmup_init"] else 1e-2, 1.0 / math.sqrt(t))
+        return group["lr"]
+
+    _find_owner = FusedAdam._find_owner
+
+    def _fast_ok(self):
+        """(model, None) when the fused path applies, else (None, reason): FusedAdam's ownership test."""
+        if len(self.param_groups) != 1:
+            return None, "several param groups"
+        g = self.param_groups[0]
+        model = self._find_owner()
+        if model is None:
+            return None, "parameters not owned by one klab MyModel"
+        if model._flat.get("main") is None or model._engine.shape is None:
+            return None, "engine not bound yet"
+        views = {id(p): v for p, v, mn in (model._views or []) if mn == "main"}
+        mine = {id(p) for p in g["params"]}
+        if mine != {id(p) for p in model.transformer.ordered() if p.requires_grad} or set(views) != mine:
+            return None, "not exactly the trainable T5 parameters"
+        for p in g["params"]:
+            v = views[id(p)]
+            if p.grad is None or p.grad.data_ptr() != v.data_ptr():
+                return None, "gradients are not views of the flat buffer"
+        return model, None
+
+    # ---- flat state <-> per-parameter (HF) state ------------------------------------------------------------------------------
+    def _attach(self, model):
+        """allocate the flat buffers for `model`'s bound engine; False when the kernels do not cover its tensors"""
+        eng = model._engine
+        try:
+            n_state, n_scal, n_scratch = eng.adafactor_sizes()
+            layout = eng.adafactor_layout()
+        except NotImplementedError:
+            return False
+        by_ptr = {p.data_ptr(): (p, v.storage_offset()) for p, v, mn in model._views if mn == "main" and p.requires_grad}
+        if len(layout) != len(by_ptr) or any(ptr not in by_ptr for ptr, *_ in layout):
+            return False
+        flat = model._flat["main"]
+        self._slots = [(by_ptr[ptr][0], rows, cols, off, fact, by_ptr[ptr][1]) for ptr, rows, cols, off, fact in layout]
+        self._st = torch.zeros(n_state, dtype=torch.float32, device=flat.device)
+        self._scal = torch.zeros(n_scal, dtype=torch.float32, device=flat.device)
+        self._scratch = torch.zeros(n_scratch, dtype=torch.float32, device=flat.device)
+        self._m = torch.zeros_like(flat) if self.param_groups[0]["beta1"] is not None else None
+        self._owner = weakref.ref(model)
+        self._bound_key = model._bound_key
+        return True
+
+    def _slot_views(self, slot):
+        p, rows, cols, off, fact, moff = slot
+        if fact:
+            c0 = off + ((rows + 3) & ~3)
+            sq = {"exp_avg_sq_row": self._st[off:off + rows].view(p.shape[:-1]), "exp_avg_sq_col": self._st[c0:c0 + cols].view(p.shape[-1:])}
+        else:
+            sq = {"exp_avg_sq": self._st[off:off + cols].view(p.shape)}
+        if self._m is not None:
+            sq["exp_avg"] = self._m[moff:moff + p.numel()].view(p.shape)
+        return sq
+
+    def _export(self):
+        """flat buffers -> self.state (copies, HF keys)"""
+        if not self._flat_live:
+            return
+        for i, slot in enumerate(self._slots):
+            st = {"step": self._steps, "RMS": self._scal[4 * i + 1].clone()}
+            st.update({k: v.clone() for k, v in self._slot_views(slot).items()})
+            self.state[slot[0]] = st
+
+    def _import(self):
+        """self.state -> flat buffers; the step count is the parameters' common one"""
+        steps = 0
+        self._st.zero_()
+        if self._m is not None:
+            self._m.zero_()
+        dev = self._st.device
+        rms = []  # one column write at the end instead of a device->host read per tensor
+        for slot in self._slots:
+            st = self.state.get(slot[0]) or {}
+            for k, v in self._slot_views(slot).items():
+                if k in st:
+                    v.copy_(st[k])
+            rms.append(torch.as_tensor(st.get("RMS", 0.0), dtype=torch.float32).to(dev).reshape(()))
+            steps = max(steps, int(st.get("step", 0)))
+        self._scal.view(-1, 4)[:, 1] = torch.stack(rms)
+        self._steps = steps
+        self.state.clear()
+        self._flat_live = True
+
+    # ---- torch.optim API ------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        model, why = self._fast_ok()
+        if model is not None and self._refused == (id(model), model._bound_key):
+            model, why = None, "a tensor shape the Adafactor kernels do not cover"
+        if model is not None and (self._st is None or self._owner is None or self._owner() is not model
+                                  or (self._m is None) != (self.param_groups[0]["beta1"] is None)):
+            self._export()
+            self._flat_live = False
+            if not self._attach(model):
+                self._st = None
+                self._refused = (id(model), model._bound_key)  # asked once per binding, not on every step
+                model, why = None, "a tensor shape the Adafactor kernels do not cover"
+        if model is None:
+            for grp in self.param_groups:  # gradients may still be in flight (klab DDP overlap_optimizer): join before torch reads them
+                for p in grp["params"]:
+                    ref = getattr(p, "_klab_owner", None)
+                    owner = ref() if ref is not None else None
+                    red = getattr(owner, "_pending_reduce", None) if owner is not None else None
+                    if red is not None:
+                        owner._pending_reduce = None
+                        red.finish()
+            self._fb_reason = why
+            self._export()
+            self._flat_live = False
+            self._step_fallback()
+            return loss
+        if not self._flat_live:
+            self._import()
+        if model._bound_key != self._bound_key:  # re-bound to another batch shape: same tensors, same layout
+            if model._engine.adafactor_sizes() != (self._st.numel(), self._scal.numel(), self._scratch.numel()):
+                raise RuntimeError("FusedAdafactor: the engine's Adafactor layout changed under a live optimizer state")
+            self._bound_key = model._bound_key
+        g = self.param_groups[0]
+        self._steps += 1
+        t = self._steps
+        beta2t = 1.0 - math.pow(t, g["decay_rate"])
+        red = getattr(model, "_pending_reduce", None)
+        if red is not None:  # klab DDP(overlap_optimizer=True): RMS(u) needs every gradient, so the whole reduction is joined first
+            model._pending_reduce = None
+            red.finish()
+        side = getattr(model, "_pending_opt_stream", None)
+        if side is not None:  # an in-backward update of another optimizer still writes the weights
+            torch.cuda.current_stream(self._st.device).wait_stream(side)
+            model._pending_opt_stream = None
+        model._engine.adafactor_step(self._st, self._m, self._scal, self._scratch, beta2t, 1.0 - beta2t, float(g["eps"][0]), float(g["eps"][1]),
+                                     float(self._rel_step(g, t)), float(g["clip_threshold"]), float(g["beta1"] or 0.0),
+                                     1.0 - float(g["beta1"] or 0.0), float(g["weight_decay"]), g["scale_parameter"])
+        model._note_optimizer_step()
+        return loss
+
+    def _step_fallback(self):
+        """the same rule per parameter in plain torch, on self.state"""
+        for group in self.param_groups:
+            eps0, eps1 = group["eps"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("Adafactor does not support sparse gradients.")
+                grad = p.grad.float() if p.grad.dtype in (torch.float16, torch.bfloat16) else p.grad
+                factored = grad.dim() >= 2
+                st = self.state[p]
+                if len(st) == 0:
+                    st["step"] = 0
+                    st["RMS"] = 0
+                    if group["beta1"] is not None:
+                        st["exp_avg"] = torch.zeros_like(grad)
+                    if factored:
+                        st["exp_avg_sq_row"] = grad.new_zeros(grad.shape[:-1])
+                        st["exp_avg_sq_col"] = grad.new_zeros(grad.shape[:-2] + grad.shape[-1:])
+                    else:
+                        st["exp_avg_sq"] = torch.zeros_like(grad)
+                else:
+                    for k in ("exp_avg", "exp_avg_sq_row", "exp_avg_sq_col", "exp_avg_sq"):
+                        if k in st:
+                            st[k] = st[k].to(grad)
+                    if group["beta1"] is not None and "exp_avg" not in st:
+                        st["exp_avg"] = torch.zeros_like(grad)
+                w = p.float() if p.dtype in (torch.float16, torch.bfloat16) else p
+                st["step"] = t = int(st["step"]) + 1
+                st["RMS"] = rms_p = w.norm(2) / (w.numel() ** 0.5)
+                lr = self._rel_step(group, t) * (max(eps1, rms_p) if group["scale_parameter"] else 1.0)
+                beta2t = 1.0 - math.pow(t, group["decay_rate"])
+                sq = grad ** 2 + eps0
+                if factored:
+                    row, col = st["exp_avg_sq_row"], st["exp_avg_sq_col"]
+                    row.mul_(beta2t).add_(sq.mean(dim=-1), alpha=1.0 - beta2t)
+                    col.mul_(beta2t).add_(sq.mean(dim=-2), alpha=1.0 - beta2t)
+                    rf = (row / row.mean(dim=-1, keepdim=True)).rsqrt_().unsqueeze(-1)
+                    u = torch.mul(rf, col.unsqueeze(-2).rsqrt()).mul_(grad)
+                else:
+                    v = st["exp_avg_sq"]
+                    v.mul_(beta2t).add_(sq, alpha=1.0 - beta2t)
+                    u = v.rsqrt().mul_(grad)
+                rms_u = u.norm(2) / (u.numel() ** 0.5)
+                u.div_((rms_u / group["clip_threshold"]).clamp_(min=1.0)).mul_(lr)
+                if group["beta1"] is not None:
+                    u = st["exp_avg"].mul_(group["beta1"]).add_(u, alpha=1 - group["beta1"])
+                if group["weight_decay"] != 0:
+                    w.add_(w, alpha=-group["weight_decay"] * lr)
+                w.add_(-u)
+                if w is not p:
+                    p.copy_(w)
+
+    def state_dict(self):
+        """transformers.optimization.Adafactor-compatible (copies of the flat state when the fused path is live)."""
+        self._export()
+        sd = super().state_dict()
+        if self._flat_live:
+            self.state.clear()  # the flat buffers stay the live state; `sd` keeps the copies
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """transformers.optimization.Adafactor-compatible.  The loaded state is kept per parameter; the next `step()` moves it
+        into the flat buffers when the fused path applies (the model must have been bound by one forward), else the torch rule
+        continues from it."""
+        super().load_state_dict(state_dict)
+        self._flat_live = False
+        self._steps = 0
