@@ -482,17 +482,11 @@ int klab_adafactor_step(const void* desc_dev, int ndesc, long state_elems, long 
                         float* scalars, float* scratch, void* arena, int dtype, float beta2t, float one_minus_beta2t, float eps0, float eps1,
                         float rel_step, float clip_threshold, float beta1, float one_minus_beta1, float weight_decay, int scale_parameter,
                         void* stream);
-/* Greedy decoding with a K/V cache (ref/models/model.py:27-28, HF/t5:308-332): the decoder over ONE new position t >= 1 per
- * sample.  Precondition: a klab_engine_forward in evaluation mode on this binding (prefill: encoder, cross K/V, position 0),
- * then steps 1, 2, ... in order; the per-layer q|k|v buffers of the binding are the cache.  prev_tokens [B] (device) = ids
- * generated at position t-1.  Logits of position t: klab_engine_buffer("logits_step") [B, vocab].                        */
-int klab_engine_decode_step(klab_engine* e, int t, const long long* prev_tokens, void* stream);
-/* one query row per (batch, head) against cached keys / values (element strides; bias_row [H, bias_ld] or NULL) */
-int klab_t5_decode_attn(int dtype, const void* q, long q_bstride, const void* k, const void* v, long kv_bstride, long ldk,
-                        const float* bias_row, long bias_ld, void* ctx, long ctx_bstride, int B, int H, int Lk, int dk, void* stream);
-/* the same for R = B*k beam rows.  Key j of query row r is read at row  s*kv_bstride + j*ldk  (element offsets from k / v) where
- * s = kv_slot[r*slot_ld + j] when kv_slot (int32 [R, slot_ld]) is given, else s = r / kv_group (cross-attention: k beams share
- * their sample's encoder K/V).  kv_group 1 and kv_slot NULL is klab_t5_decode_attn, bit for bit.                          */
+/* decoding over a K/V cache: one query row per (row, head) of R rows against cached keys / values (element strides; bias_row
+ * [H, bias_ld] or NULL; scores are unscaled, HF/t5:196-197).  Key j of query row r is read at row  s*kv_bstride + j*ldk  (element
+ * offsets from k / v) where s = kv_slot[r*slot_ld + j] when kv_slot (int32 [R, slot_ld]) is given (beam search: the beams' key-slot
+ * tables), else s = r / kv_group (kv_group 1: every row its own keys; cross-attention: the kv_group rows of a sample share its
+ * encoder K/V).                                                                                                             */
 int klab_t5_beam_decode_attn(int dtype, const void* q, long q_bstride, const void* k, const void* v, long kv_bstride, long ldk,
                              int kv_group, const int* kv_slot, long slot_ld, const float* bias_row, long bias_ld, void* ctx,
                              long ctx_bstride, int R, int H, int Lk, int dk, void* stream);
@@ -595,7 +589,8 @@ typedef struct {
   int n_bad; const int* bad_off; const int* bad_tok;
 } klab_logits_proc_cfg;
 
-/* ---- decoding sessions on an engine binding: HF's `_beam_search`, `_sample`, and greedy decoding behind the processors ----
+/* ---- decoding sessions on an engine binding: HF's `_beam_search`, `_sample` and greedy decoding (ref/models/model.py:27-28,
+ * HF/t5:308-332) -- the one way the engine decodes over a K/V cache --------------------------------------------------------------
  * One prefill at B rows, then M = B*n rows on the device (row b*n + j: beam / sample j of image b, HF's
  * `_expand_inputs_for_generation`; the n rows of an image share its cross-attention K/V).  The workspace
  * (klab_engine_gen_workspace_bytes; 0 = unsupported settings) is caller-owned and separate from the binding's: decoder scratch
@@ -617,6 +612,9 @@ typedef struct {
  * gen_stop_word: device address of the stop word of position pos, written by the step that chose it.  Beam search goes on iff
  *   bits 1 and 4 are set and, with early_stopping True, bit 2 (see klab_beam_update); sampling and pick go on while it is
  *   non-zero (some row unfinished).
+ * gen_buffer: a view into ws for tests and diagnostics (NULL before gen_begin or for another name) -- "logits": [M, vocab] in the
+ *   compute dtype, the logits gen_step decoded last; "tokens": [M, 1] int64 (*dtype is left alone), the decoder inputs of the
+ *   next gen_step.
  * gen_result: beam search: the first n <= num_beams of each sample's finished pool (sorted by score), length = max_length:
  *   seq [B*n, max_length] int64, scores [B*n] f32, len [B*n] int32 (generated tokens, the start token excluded).  Sampling
  *   and pick: n = the session's n, the first length <= (last position chosen) + 1 columns of the sequences into seq
@@ -634,6 +632,7 @@ size_t klab_engine_gen_workspace_bytes(klab_engine* e, const klab_gen_cfg* cfg);
 int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, void* ws, void* stream);
 int klab_engine_gen_step(klab_engine* e, int t, void* ws, void* stream);
 const int* klab_engine_gen_stop_word(klab_engine* e, void* ws, int pos);
+const void* klab_engine_gen_buffer(klab_engine* e, void* ws, const char* name, long* rows, long* cols, int* dtype);
 int klab_engine_gen_result(klab_engine* e, void* ws, int n, int length, long long* seq, float* scores, int* len, void* stream);
 /* segment 0: LM head + decoder + tied embedding; 1: encoder; 2: Swin (no-op unless train_swin).
  * dloss_dev: device scalar d(objective)/d(loss) (NULL = 1).                                       */

@@ -443,19 +443,6 @@ static int launch_decode_attn(const void* q, long q_bstride, const void* k, cons
 }
 }  // namespace klab
 
-extern "C" int klab_t5_decode_attn(int dtype, const void* q, long q_bstride, const void* k, const void* v, long kv_bstride, long ldk,
-                                   const float* bias_row, long bias_ld, void* ctx, long ctx_bstride, int B, int H, int Lk, int dk,
-                                   void* stream) {
-  using namespace klab;
-  if (!q || !k || !v || !ctx || B <= 0 || H <= 0 || Lk <= 0) return KLAB_ERR_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == KLAB_BF16)
-    return launch_decode_attn<bf16_t>(q, q_bstride, k, v, kv_bstride, ldk, 1, nullptr, 0, bias_row, bias_ld, ctx, ctx_bstride, B, H, Lk, dk, s);
-  if (dtype == KLAB_F32)
-    return launch_decode_attn<float>(q, q_bstride, k, v, kv_bstride, ldk, 1, nullptr, 0, bias_row, bias_ld, ctx, ctx_bstride, B, H, Lk, dk, s);
-  return KLAB_ERR_BADARG;
-}
-
 extern "C" int klab_t5_beam_decode_attn(int dtype, const void* q, long q_bstride, const void* k, const void* v, long kv_bstride, long ldk,
                                         int kv_group, const int* kv_slot, long slot_ld, const float* bias_row, long bias_ld, void* ctx,
                                         long ctx_bstride, int R, int H, int Lk, int dk, void* stream) {

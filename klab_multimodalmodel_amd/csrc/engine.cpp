@@ -145,9 +145,6 @@ struct klab_engine {
   const int *enc_bucket = nullptr, *dec_bucket = nullptr, *lang_bucket = nullptr;
   std::vector<const float*> swin_coords; std::vector<const int*> swin_index; std::vector<int> swin_ntab;
   T5StackBufs lang, enc, dec;
-  // greedy decoding with a K/V cache (klab_engine_decode_step): one position per sample, contiguous [B, .] rows
-  float* dc_h[2] = {nullptr, nullptr}; float* dc_rstd = nullptr;
-  void *dc_xn = nullptr, *dc_q = nullptr, *dc_ctx = nullptr, *dc_hmid = nullptr, *dc_ab = nullptr, *dc_out = nullptr, *dc_logits = nullptr;
   // the decoding session (klab_engine_gen_*) begun last on this binding
   GenRun gen;
   // lang scratch (no grad => reused across layers)
@@ -533,12 +530,6 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
   e->kv_all = b.take((size_t)Me * nld * 2 * inner * es);
   e->dkv_all = b.take((size_t)Me * nld * 2 * inner * es);
   e->logits = b.take((size_t)Md * c.main.vocab * es);
-  e->dc_h[0] = (float*)b.take((size_t)B * d * 4); e->dc_h[1] = (float*)b.take((size_t)B * d * 4);
-  e->dc_rstd = (float*)b.take((size_t)B * 4);
-  e->dc_xn = b.take((size_t)B * d * es); e->dc_q = b.take((size_t)B * inner * es); e->dc_ctx = b.take((size_t)B * inner * es);
-  e->dc_hmid = b.take((size_t)B * ff * es); e->dc_out = b.take((size_t)B * d * es);
-  e->dc_ab = c.main.ffn_gated ? b.take((size_t)B * 2 * ff * es) : nullptr;
-  e->dc_logits = b.take((size_t)B * c.main.vocab * es);
   e->loss_row = (float*)b.take((size_t)Md * 4);
   const long Mx = Me > Md ? Me : Md;
   e->dh_a = (float*)b.take((size_t)Mx * d * 4);
@@ -1893,20 +1884,19 @@ extern "C" const void* klab_engine_buffer(const klab_engine* e, const char* name
   if (!strcmp(name, "encoder_out")) { set((long)e->B * e->Le, d, e->cfg.dtype); return e->enc.out_t; }
   if (!strcmp(name, "decoder_out")) { set((long)e->B * e->Lt, d, e->cfg.dtype); return e->dec.out_t; }
   if (!strcmp(name, "logits")) { set((long)e->B * e->Lt, e->cfg.main.vocab, e->cfg.dtype); return e->logits; }
-  if (!strcmp(name, "logits_step")) { set((long)e->B, e->cfg.main.vocab, e->cfg.dtype); return e->dc_logits; }
   return nullptr;
 }
 
 namespace {
-// The rows of one decoder step over the self-attention K/V cache: greedy decoding (B rows; layer i's cache is the binding's
-// q|k|v buffer, row block b at b*Lt) or beam search (B*k rows; layer i's cache at cache + i*cache_layer, slot block s at
-// s*max_length, key j of row r in slot kv_slot[r][j]; the k beams of a sample share its cross-attention K/V).
+// The rows of one decoder step of a decoding session over its self-attention K/V cache (plan_gen): M = B*n rows; layer i's cache
+// at cache + i*cache_layer, slot block s at s*cache_rows; key j of row r in slot kv_slot[r][j] (beam search) or in the row's own
+// slot r (kv_slot NULL); the kv_group = n rows of a sample share its cross-attention K/V.
 struct DecodeRows {
   int M;
   float* h[2]; float* rstd;
   void *xn, *q, *ctx, *hmid, *out, *logits;
   void* ab = nullptr;  // gated feed-forward: the two pre-activations [M, 2 d_ff]
-  void* cache = nullptr; long cache_layer = 0; int cache_rows = 0;
+  void* cache; long cache_layer; int cache_rows;
   int kv_group = 1; const int* kv_slot = nullptr; long slot_ld = 0;
 };
 
@@ -1918,7 +1908,7 @@ int decode_rows(klab_engine* e, const Ctx& c, int t, const long long* tokens, co
   const int M = r.M, Lt = e->Lt, Le = e->Le, d = cfg.d_model, H = cfg.n_heads, dk = cfg.d_kv, inner = H * dk, ff = cfg.d_ff;
   const int nld = cfg.n_dec_layers;
   const long kv_ld = (long)nld * 2 * inner;
-  const long self_ld = (long)(r.cache ? r.cache_rows : Lt) * 3 * inner;  // elements between the row blocks of two slots
+  const long self_ld = (long)r.cache_rows * 3 * inner;  // elements between the row blocks of two slots
   RC(klab_embed_fwd(tokens, 0, 1, cfg.start_id, cfg.pad_id, W[e->mi.shared], cfg.vocab, r.h[0], M, d, 0.f, nullptr, 0, e->err_dev,
                     c.ws()));
   float* h = r.h[0];
@@ -1932,7 +1922,7 @@ int decode_rows(klab_engine* e, const Ctx& c, int t, const long long* tokens, co
   };
   for (int i = 0; i < nld; ++i) {
     const T5LayerIdx& l = e->mi.dec[i];
-    void* qkv = r.cache ? eoff(c, r.cache, (long)i * r.cache_layer) : e->dec.L[i].qkv;
+    void* qkv = eoff(c, r.cache, (long)i * r.cache_layer);
     // self attention over the cache
     RC(klab_rmsnorm_fwd(h, W[l.ln0], r.xn, c.dt, nullptr, r.rstd, M, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
     {
@@ -1970,25 +1960,9 @@ int decode_rows(klab_engine* e, const Ctx& c, int t, const long long* tokens, co
 }
 }  // namespace
 
-// Greedy decoding with a K/V cache (ref/models/model.py:27-28 -> generate; HF/t5:308-332): the decoder over ONE new position
-// t >= 1 per sample.  Precondition: a klab_engine_forward in evaluation mode on this binding (the prefill: encoder output,
-// cross-attention K/V of all layers, the decoder's position-bias table, and -- position 0 being the start token whatever the
-// target holds -- the self-attention K/V rows of position 0), then decode steps 1, 2, ... in order.  The per-layer q|k|v
-// buffer [B*Lt, 3*inner] of the training path IS the cache: the new position's fused projection is written into row
-// b*Lt + t, attention reads rows b*Lt + 0..t.  prev_tokens [B] = the ids generated at position t-1 (the decoder input at t,
-// HF/t5:618-637).  Result: logits of position t in the "logits_step" buffer [B, vocab].
-extern "C" int klab_engine_decode_step(klab_engine* e, int t, const long long* prev_tokens, void* stream) {
-  if (!e || !e->bound || !prev_tokens || t < 1 || t >= e->Lt) return KLAB_ERR_BADARG;
-  Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
-  DecodeRows r;
-  r.M = e->B;
-  r.h[0] = e->dc_h[0]; r.h[1] = e->dc_h[1]; r.rstd = e->dc_rstd;
-  r.xn = e->dc_xn; r.q = e->dc_q; r.ctx = e->dc_ctx; r.hmid = e->dc_hmid; r.ab = e->dc_ab; r.out = e->dc_out; r.logits = e->dc_logits;
-  return decode_rows(e, c, t, prev_tokens, r);
-}
-
-// ---- decoding sessions (HF `_beam_search`, `_sample`, greedy behind the logits processors): one prefill at B rows, then B*n rows
-// on the device in a workspace of their own, owned by the caller ----------------------------------------------------------------
+// ---- decoding sessions (HF `_beam_search`, `_sample`, greedy decoding with or without the logits processors; ref/models/model.py:
+// 27-28 -> generate, HF/t5:308-332): one prefill at B rows, then B*n rows on the device in a workspace of their own, owned by the
+// caller ---------------------------------------------------------------------------------------------------------------------------
 namespace {
 // the logits processors of a session (HF's RepetitionPenalty, NoRepeatNGram, NoBadWords, MinLength, MinNewTokensLength) from cfg
 // (NULL: none), checked against this binding
@@ -2208,6 +2182,23 @@ extern "C" const int* klab_engine_gen_stop_word(klab_engine* e, void* ws, int po
   GenWs w;
   plan_gen(e, e->gen.cfg, e->gen.lp, ws, w);
   return w.stop + pos;
+}
+
+extern "C" const void* klab_engine_gen_buffer(klab_engine* e, void* ws, const char* name, long* rows, long* cols, int* dtype) {
+  if (!e || !ws || !name || e->gen.cur < 1) return nullptr;
+  GenWs w;
+  plan_gen(e, e->gen.cfg, e->gen.lp, ws, w);
+  if (rows) *rows = w.rows.M;
+  if (!strcmp(name, "logits")) {
+    if (cols) *cols = e->cfg.main.vocab;
+    if (dtype) *dtype = e->cfg.dtype;
+    return w.rows.logits;
+  }
+  if (!strcmp(name, "tokens")) {
+    if (cols) *cols = 1;
+    return w.prev;
+  }
+  return nullptr;
 }
 
 extern "C" int klab_engine_gen_result(klab_engine* e, void* ws, int n, int length, long long* seq, float* scores, int* len, void* stream) {

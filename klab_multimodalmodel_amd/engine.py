@@ -118,11 +118,11 @@ ENGINE_SIGS = {
                           C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                           C.POINTER(C.c_void_p), C.c_void_p], C.c_int),
     "klab_engine_forward": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p], C.c_int),
-    "klab_engine_decode_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_gen_workspace_bytes": ([C.c_void_p, C.POINTER(L.GenCfg)], C.c_size_t),
     "klab_engine_gen_begin": ([C.c_void_p, C.POINTER(L.GenCfg), C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_gen_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_gen_stop_word": ([C.c_void_p, C.c_void_p, C.c_int], C.c_void_p),
+    "klab_engine_gen_buffer": ([C.c_void_p, C.c_void_p, C.c_char_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)], C.c_void_p),
     "klab_engine_gen_result": ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_backward": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_set_graph": ([C.c_void_p, C.c_int], C.c_int),
@@ -375,12 +375,8 @@ class Engine:
             L.check(rc, "klab_engine_set_loss_out")
         return rc == 1
 
-    def decode_step(self, t, prev_tokens):
-        """decoder over position t (>= 1) only, self-attention K/V from the binding's cache; logits -> buffer("logits_step")"""
-        L.check(self._lib.klab_engine_decode_step(self._h, int(t), prev_tokens.data_ptr(), L.stream_ptr()), "klab_engine_decode_step")
-
-    # ---- decoding sessions (HF `_beam_search`, `_sample`, greedy behind the processors); the workspace is the caller's, the
-    # binding's is untouched -------------------------------------------------------------------------------------------------
+    # ---- decoding sessions (HF `_beam_search`, `_sample`, greedy decoding); the workspace is the caller's, the binding's is
+    # untouched ----------------------------------------------------------------------------------------------------------------
     GEN_MODES = {"pick": L.GEN_PICK, "sample": L.GEN_SAMPLE, "beam": L.GEN_BEAM}
     EARLY_STOPPING = {False: 0, True: 1, "never": 2}
 
@@ -428,6 +424,17 @@ class Engine:
         if self._gen.mode != L.GEN_BEAM:
             return w != 0
         return bool((w & 1) and (w & 4) and (self._gen.early_stopping != 1 or (w & 2)))
+
+    def gen_buffer(self, ws, name):
+        """a view into ws -- "logits": [B*n, vocab], the logits gen_step decoded last; "tokens": [B*n] int64, the next step's inputs"""
+        rows, cols, dt = C.c_long(), C.c_long(), C.c_int()
+        p = self._lib.klab_engine_gen_buffer(self._h, ws.data_ptr(), name.encode(), C.byref(rows), C.byref(cols), C.byref(dt))
+        if not p:
+            raise KeyError(name)
+        tdt = torch.int64 if name == "tokens" else torch.float32 if dt.value == L.F32 else torch.bfloat16
+        off = p - ws.data_ptr()
+        v = ws[off:off + rows.value * cols.value * tdt.itemsize].view(tdt)
+        return v if name == "tokens" else v.view(rows.value, cols.value)
 
     def gen_result(self, ws, n, length):
         """beam search: (sequences [B*n, length = max_length] int64, scores [B*n] f32, generated lengths [B*n] int32) of the first n

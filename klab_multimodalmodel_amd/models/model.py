@@ -378,18 +378,22 @@ class MyModel(nn.Module):
                  num_return_sequences=1, return_scores=False, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_length=0, min_new_tokens=None):
         """greedy decoding with HF's default generation settings (ref/models/model.py:28: max_length 20, no sampling).
-        Prefill = one evaluation-mode forward (Swin, both encoders, the cross K/V of all layers, decoder position 0); every
-        further token runs the decoder over ONE new position against the per-layer K/V cache (`klab_engine_decode_step`,
-        SURVEY §8 row f-3; HF/t5:308-332).  kv_cache=False keeps the round-1 form -- decoder + LM head over the whole prefix per
-        token -- as the cross-check of the cache.
-        num_beams > 1: HF's beam search (`_beam_search`, `generate(num_beams=...)`) on the device -- see _generate_beam.
-        do_sample=True: HF's `_sample` with temperature -> top-k -> top-p on the device -- see _generate_sample.
+        Every kv_cache=True call is one decoding session on the device (_generate_on_device; SURVEY §8 row f-3, HF/t5:308-332):
+        prefill = one evaluation-mode forward (Swin, both encoders, the cross K/V of all layers, decoder position 0), then every
+        further token runs the decoder over ONE new position against the session's per-layer K/V cache and chooses the next token
+        on the device; the host reads one stop word per step.  Plain greedy decoding is the "pick" session without processors.
+        kv_cache=False (greedy without processors only) is the independent cross-check of the cache: a host loop that re-runs
+        decoder + LM head over the whole prefix per token.
+        num_beams > 1: HF's beam search (`_beam_search`, `generate(num_beams=...)`) -- see _generate_beam.
+        do_sample=True: HF's `_sample` with temperature -> top-k -> top-p -- see _generate_sample.
         repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens: HF's logits processors with HF's
         names, defaults and checks (logits_proc.logits_processor_settings), in front of all three loops as in HF: on the fp32
         logits for greedy and sampling (before the warpers), on log_softmax(logits) for beam search; the history is the decoder
-        sequence with its start token.  One `klab_logits_process_rows` per step (csrc/logits_proc.hip); greedy decoding with
-        processors runs as a decoding session of its own ("pick"), the processed arg-max replacing the draw.  With none of them active
-        every path runs as without them."""
+        sequence with its start token.  One `klab_logits_process_rows` per step (csrc/logits_proc.hip); in a pick session it also
+        takes the arg-max (lowest id among ties, as torch.argmax), pads finished rows and sets the stop word.
+        Limit: sampling, pick and beam search with processors need vocab_size <= 32768 (the register row of
+        klab_logits_process_rows; every supported T5 checkpoint has 32100-32128) and raise ValueError above it, plain greedy
+        decoding included; a session also needs max_length >= 2.  kv_cache=False has neither limit."""
         procs = logits_processor_settings(repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens,
                                           eos_token_id=self.main_cfg.eos_token_id, vocab_size=self.main_cfg.vocab_size)
         if do_sample:
@@ -419,11 +423,11 @@ class MyModel(nn.Module):
                                        return_scores, procs)
         if return_scores:
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence scores)")
-        if procs is not None:
-            if not kv_cache:
-                raise ValueError("logits processors run on the K/V cache only: repetition_penalty, no_repeat_ngram_size, bad_words_ids, "
-                                 "min_length and min_new_tokens need kv_cache=True")
+        if kv_cache:
             return self._generate_sample(pixels, src, max_length, 1, 1.0, 0, 1.0, procs, pick=True)
+        if procs is not None:
+            raise ValueError("logits processors run on the K/V cache only: repetition_penalty, no_repeat_ngram_size, bad_words_ids, "
+                             "min_length and min_new_tokens need kv_cache=True")
         B = src.shape[0]
         cfg = self.main_cfg
         steps = max_length - 1
@@ -432,17 +436,11 @@ class MyModel(nn.Module):
         was_training = self.transformer.training
         self.transformer.eval()
         try:
-            nxt = None
+            eng = self._engine_for(pixels, src, tgt)
             for t in range(steps):
-                eng = self._engine_for(pixels, src, tgt)
-                if t == 0 or not kv_cache:
-                    eng.forward(pixels, src, tgt, training=(8 if t > 0 else 0) | (2 if t > 0 else 0), seed=self._seed_base, want_grad=False)
-                    logits = eng.buffer("logits").view(B, steps, -1)[:, t].float()
-                else:
-                    eng.decode_step(t, nxt)
-                    logits = eng.buffer("logits_step").float()
-                nxt = logits.argmax(-1)
-                nxt = torch.where(done, torch.full_like(nxt, cfg.pad_token_id), nxt).contiguous()
+                eng.forward(pixels, src, tgt, training=(8 if t > 0 else 0) | (2 if t > 0 else 0), seed=self._seed_base, want_grad=False)
+                nxt = eng.buffer("logits").view(B, steps, -1)[:, t].float().argmax(-1)
+                nxt = torch.where(done, torch.full_like(nxt, cfg.pad_token_id), nxt)
                 tgt[:, t] = nxt
                 done |= nxt == cfg.eos_token_id
                 if bool(done.all()):
@@ -484,7 +482,8 @@ class MyModel(nn.Module):
                               procs)
             nbytes = eng.gen_workspace_bytes(gen)
             if nbytes == 0:
-                what = f"beam search: unsupported num_beams={n}" if mode == "beam" else f"sampling: unsupported num_return_sequences={n}"
+                what = {"beam": f"beam search: unsupported num_beams={n}", "sample": f"sampling: unsupported num_return_sequences={n}",
+                        "pick": f"greedy decoding on the K/V cache: unsupported vocab_size={cfg.vocab_size}"}[mode]
                 raise ValueError(f"{what} / max_length={max_length} for this model")
             ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
             eng.gen_begin(gen, ws)

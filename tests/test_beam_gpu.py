@@ -71,8 +71,40 @@ def test_beam_topk_kernel_matches_torch(V, k, dtype):
 
 
 # ---- klab_t5_beam_decode_attn ----------------------------------------------------------------------------------------------
+def _attn_formula(q, k, v, bias, dt):
+    """T5's decode attention on the host in dtype dt: q [R, H, dk], k / v [R, Lk, H, dk], bias [H, Lk] or None -> [R, H*dk];
+    unscaled q.k + the bias row, softmax, .v (HF/t5:196-197)"""
+    q, k, v = q.cpu().to(dt), k.cpu().to(dt), v.cpu().to(dt)
+    s = torch.einsum("rhc,rjhc->rhj", q, k)
+    if bias is not None:
+        s = s + bias.cpu().to(dt)[None]
+    return torch.einsum("rhj,rjhc->rhc", torch.softmax(s, -1), v).reshape(q.shape[0], -1)
+
+
+# Largest |kernel - fp64 formula| of the former plain one-row entry point (removed since: the same kernel with kv_group 1 and no
+# table) on the two fp32 inputs of the test below, measured on an MI355X at the commit before its removal: 9.110e-07 (slot-table
+# case, Lk 6 with bias) and 1.0756e-06 (kv_group case, Lk 11 without); torch's own fp32 evaluation of the formula is at 1.030e-06 and
+# 1.039e-06.  The test allows 4x the kernel's figure: it uses the fast exponential and a lane-split reduction order.  In bf16 the
+# bound is 2x the error of torch's own bf16 evaluation of the formula against fp64, computed in the test (measured: torch 1.825e-02
+# and 2.458e-02, the kernel 6.97e-03 and 7.28e-03).
+DECODE_ATTN_FP32_ERR = {"slot": 9.110426046898823e-07, "group": 1.0755508413895498e-06}
+
+
+def _check_against_formula(case, out, q, k, v, bias, dtype):
+    ref = _attn_formula(q, k, v, bias, torch.float64)
+    err = float((out.cpu().double() - ref).abs().max())
+    if dtype == torch.float32:
+        bound = 4 * DECODE_ATTN_FP32_ERR[case]
+    else:
+        bound = 2 * float((_attn_formula(q, k, v, bias, dtype).double() - ref).abs().max())
+    print(case, dtype, "max |kernel - fp64|", err, "bound", bound)
+    assert err <= bound, (case, dtype, err, bound)
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_beam_decode_attn_slot_table_matches_gather(dtype):
+    """the key-slot table against the same kernel on a gathered copy of the cache (kv_group 1, no table), kv_group against a
+    repeated copy of the keys, and both against the fp64 formula on the host"""
     L, lib = _lib()
     g = torch.Generator().manual_seed(3)
     H, dk, B, k, Lmax, Lk, Le = 2, 32, 3, 4, 9, 6, 11
@@ -90,19 +122,24 @@ def test_beam_decode_attn_slot_table_matches_gather(dtype):
     rows = (slot[:, :Lk].long() * Lmax + torch.arange(Lk, device="cuda")).reshape(-1)
     gath = cache[rows].contiguous()  # [R*Lk, 3*inner]
     ref = torch.empty_like(out)
-    L.check(lib.klab_t5_decode_attn(dt, q.data_ptr(), 3 * inner, gath[:, inner:].data_ptr(), gath[:, 2 * inner:].data_ptr(), Lk * 3 * inner,
-                                    3 * inner, bias.data_ptr(), Lmax, ref.data_ptr(), inner, R, H, Lk, dk, L.stream_ptr()), "klab_t5_decode_attn")
+    L.check(lib.klab_t5_beam_decode_attn(dt, q.data_ptr(), 3 * inner, gath[:, inner:].data_ptr(), gath[:, 2 * inner:].data_ptr(),
+                                         Lk * 3 * inner, 3 * inner, 1, None, 0, bias.data_ptr(), Lmax, ref.data_ptr(), inner, R, H, Lk, dk,
+                                         L.stream_ptr()), "klab_t5_beam_decode_attn")
     tol = 1e-6 if dtype == torch.float32 else 1e-2
     assert torch.allclose(out.float(), ref.float(), atol=tol, rtol=0)
+    gv = gath.view(R, Lk, 3, H, dk)
+    _check_against_formula("slot", out, q[:, :inner].view(R, H, dk), gv[:, :, 1], gv[:, :, 2], bias[:, :Lk], dtype)
     # kv_group: k query rows per sample share the sample's keys
     kv = torch.randn(B * Le, 2 * inner, generator=g).to(dtype).cuda()
     qc = torch.randn(R, inner, generator=g).to(dtype).cuda()
     L.check(lib.klab_t5_beam_decode_attn(dt, qc.data_ptr(), inner, kv.data_ptr(), kv[:, inner:].data_ptr(), Le * 2 * inner, 2 * inner, k,
                                          None, 0, None, 0, out.data_ptr(), inner, R, H, Le, dk, L.stream_ptr()), "klab_t5_beam_decode_attn")
     kve = kv.view(B, Le, 2 * inner).repeat_interleave(k, 0).reshape(R * Le, 2 * inner).contiguous()
-    L.check(lib.klab_t5_decode_attn(dt, qc.data_ptr(), inner, kve.data_ptr(), kve[:, inner:].data_ptr(), Le * 2 * inner, 2 * inner, None, 0,
-                                    ref.data_ptr(), inner, R, H, Le, dk, L.stream_ptr()), "klab_t5_decode_attn")
+    L.check(lib.klab_t5_beam_decode_attn(dt, qc.data_ptr(), inner, kve.data_ptr(), kve[:, inner:].data_ptr(), Le * 2 * inner, 2 * inner, 1,
+                                         None, 0, None, 0, ref.data_ptr(), inner, R, H, Le, dk, L.stream_ptr()), "klab_t5_beam_decode_attn")
     assert torch.allclose(out.float(), ref.float(), atol=tol, rtol=0)
+    kv4 = kve.view(R, Le, 2, H, dk)
+    _check_against_formula("group", out, qc.view(R, H, dk), kv4[:, :, 0], kv4[:, :, 1], None, dtype)
 
 
 # ---- klab_beam_update against a torch restatement of HF's helpers (transformers/generation/utils.py) --------------------------

@@ -276,9 +276,10 @@ def test_neutral_processors_match_plain_paths():
     for name in ("tiny_a", "tiny_b"):
         m, g = _build(name, "fp32", _eos_row(name))
         pix, src = g["inputs"]["pixel_values"].cuda(), g["inputs"]["src_ids"].cuda()
-        greedy = m.generate(pix, src, max_length=12)
+        greedy = m.generate(pix, src, max_length=12, kv_cache=False)  # the host loop over the whole prefix: the independent path
         forced = m._generate_sample(pix, src, 12, 1, 1.0, 0, 1.0, dict(NEUTRAL), pick=True)
         assert torch.equal(greedy, forced), (name, greedy, forced)
+        assert torch.equal(m.generate(pix, src, max_length=12), greedy), name
         a, sa = m.generate(pix, src, max_length=12, num_beams=4, return_scores=True)
         b, sb = m._generate_beam(pix, src, 12, 4, 1.0, False, 1, True, dict(NEUTRAL))
         assert torch.equal(a, b) and torch.allclose(sa, sb, atol=1e-5, rtol=0), (name, a, b)

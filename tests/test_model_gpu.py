@@ -333,10 +333,11 @@ def test_generate_greedy_matches_oracle_argmax():
 
 
 def test_generate_kv_cache_matches_prefix_recompute():
-    """per-token decoding over the K/V cache (klab_engine_decode_step: one new position per sample, the layer's
-    q|k|v buffer as the cache, cross K/V from the prefill) yields token for token what re-running the decoder over the whole
-    prefix yields -- fp32: identical ids and logits to 1e-5; bf16: logits within bf16 round-off (an argmax may flip on a near-tie
-    of random-weight logits, so ids are compared where the top-2 margin is clear)."""
+    """decoding over the K/V cache (the decoding session: one new position per row, the session's per-layer
+    q|k|v cache, cross K/V from the prefill) yields token for token what re-running the decoder over the whole prefix yields --
+    fp32: identical ids and logits to 1e-5; bf16: logits within bf16 round-off (an argmax may flip on a near-tie of
+    random-weight logits, so ids are compared in fp32 only).  The step-level half drives a pick session by hand and overwrites
+    the tokens it chose with a fixed prefix before every step."""
     for dtype in (torch.float32, torch.bfloat16):
         m, g = build("tiny_b", dtype, False)
         inp = g["inputs"]
@@ -349,6 +350,7 @@ def test_generate_kv_cache_matches_prefix_recompute():
         # step-level check on a fixed prefix: logits of position t from the cache path vs the full-prefix path
         B = src.shape[0]
         steps = 11
+        cfg = m.main_cfg
         tgt = torch.randint(2, g["t5_cfg"].vocab_size, (B, steps), generator=torch.Generator().manual_seed(1)).cuda()
         eng = m._engine_for(pix, src, tgt)
         m.transformer.eval()
@@ -357,9 +359,14 @@ def test_generate_kv_cache_matches_prefix_recompute():
             full = eng.buffer("logits").view(B, steps, -1).float().clone()  # teacher-forced logits of every position
             # replay the same prefix through the cache: decoder input at t is tgt[:, t-1] (shift right)
             eng.forward(pix, src, torch.zeros_like(tgt), training=0, seed=m._seed_base, want_grad=False)  # prefill with another target
+            gen = eng.gen_cfg("pick", 1, steps + 1, cfg.eos_token_id, cfg.pad_token_id)
+            ws = torch.empty(eng.gen_workspace_bytes(gen), dtype=torch.uint8, device="cuda")
+            eng.gen_begin(gen, ws)
             for t in range(1, steps):
-                eng.decode_step(t, tgt[:, t - 1].contiguous())
-                step = eng.buffer("logits_step").float()
+                eng.gen_buffer(ws, "tokens").copy_(tgt[:, t - 1])
+                eng.gen_step(t, ws)
+                step = eng.gen_buffer(ws, "logits").float()
+                assert step.shape == full[:, t].shape
                 err = rel_l2(step.cpu(), full[:, t].cpu())
                 assert err < (1e-5 if dtype == torch.float32 else 2e-2), (dtype, t, err)
 
