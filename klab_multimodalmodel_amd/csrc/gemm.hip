@@ -198,8 +198,6 @@ template <int OFF> __device__ __forceinline__ u32x2 lds_read_tr(unsigned addr) {
 __device__ __forceinline__ void mfma_bf16_asm(f32x4& acc, const u32x4& x, const u32x4& y) {
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(x), "v"(y));
 }
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
 // at most g groups of LPS LDS-DMA instructions may stay in flight
 template <int LPS> __device__ __forceinline__ void wait_groups(int g) {
   switch (g) {
@@ -210,16 +208,18 @@ template <int LPS> __device__ __forceinline__ void wait_groups(int g) {
   }
 }
 
-template <int ROWS, bool KMAJOR, int NWAVES = 4, int NFRAG = ROWS / 32>
+// E: bf16_t, or char for K-major fp8 (the K-major image is byte-wise: a 64-byte row is 32 bf16 or 64 e4m3 values of k)
+template <int ROWS, bool KMAJOR, int NWAVES = 4, int NFRAG = ROWS / 32, typename E = bf16_t>
 struct GldsOperand {
+  static_assert(KMAJOR || sizeof(E) == 2, "the transposing LDS read is a 16-bit one");
   static constexpr int L = ROWS / (16 * NWAVES);   // LDS-DMA instructions per wave per stage
   static constexpr int BYTES = ROWS * 64;          // one stage of this operand
   static constexpr int NF = NFRAG;                 // 16-row fragments per wave (2 x 2 waves: the wave owns ROWS/2 rows)
   static constexpr int RPF = KMAJOR ? 1 : 2;       // LDS read instructions per fragment
-  const bf16_t* src[L];
+  const E* src[L];
   long kstep;                                      // elements to advance per k-tile
   unsigned foff[KMAJOR ? 1 : NF];                  // per-lane LDS byte offsets of the fragments inside a stage
-  __device__ __forceinline__ void init(const bf16_t* base, long ld, int row0, int nrows, int wave, int lane, int wrow0) {
+  __device__ __forceinline__ void init(const E* base, long ld, int row0, int nrows, int wave, int lane, int wrow0) {
     if constexpr (KMAJOR) {
       const int lrow = lane >> 2, lpos = lane & 3;
       const int lchunk = lpos ^ (((lrow >> 2) & 1) << 1);
@@ -227,9 +227,9 @@ struct GldsOperand {
       for (int i = 0; i < L; ++i) {
         int r = row0 + (wave * L + i) * 16 + lrow;
         r = r < nrows ? r : nrows - 1;             // rows past the edge are never stored
-        src[i] = base + (long)r * ld + lchunk * 8;
+        src[i] = base + (long)r * ld + lchunk * (16 / (int)sizeof(E));
       }
-      kstep = 32;
+      kstep = 64 / (int)sizeof(E);
       const int fr = lane & 15, fc = lane >> 4;    // fragment i sits 16 rows = 1024 B further: an immediate offset
       foff[0] = (unsigned)((wrow0 + fr) * 64 + ((fc ^ (((fr >> 2) & 1) << 1)) * 16));
     } else {
@@ -273,195 +273,41 @@ struct GldsOperand {
   }
 };
 
-// Software-pipelined, hand-scheduled main loop.  Per k-tile t a wave: waits until k-tile t+1 has landed (counted
-// vmcnt) + one s_barrier, then issues its MFMAs on the fragments of t (already in registers) with the LDS reads of
-// t+1 (other register set) and the LDS-DMA of t+S-1 slotted into the gaps between them.  Before this rewrite the
-// three phases ran back to back in each wave (measured additive: DMA issue + LDS latency + MFMA).
+// The workgroup's share of an LDS-DMA ring kernel: its output tile (bm0, bn0) and its k-tiles [kt0, kt0 + nt) of BK -- block
+// bid / tiles takes the bid / tiles'th of p.splits equal K ranges.  Textual for the same reason as gemm_glds_loop.h.
+#define KLAB_GLDS_WORK(BK)                                                              \
+  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);                      \
+  const int tile = bid % tiles, split = bid / tiles;                                    \
+  int bm0, bn0;                                                                         \
+  tile_of_block(p, BM, BN, tile, bm0, bn0);                                             \
+  const int nt_all = p.K / (BK);                                                        \
+  const int per = (nt_all + p.splits - 1) / p.splits;                                   \
+  const int kt0 = split * per, kt1 = (kt0 + per < nt_all) ? kt0 + per : nt_all;         \
+  const int nt = kt1 - kt0;                                                             \
+  if (nt <= 0) return;
+
+// 4 waves (2 x 2) on a BM x BN tile, any operand layout; ATOMIC: split-K partial sums added to C with float atomics
 template <int BM, int BN, bool AK, bool BKM, bool ATOMIC>
 __device__ __forceinline__ void gemm_glds_body(const GemmP& p, const int bid = blockIdx.x) {
   typedef bf16_t T;
-  constexpr int BK = 32, S = KLAB_GLDS_STAGES;
-  static_assert(S == 4, "the steady-state loop is unrolled over a 4-stage ring");
   constexpr int WTM = BM / 2, WTN = BN / 2, MI = WTM / 16, NI = WTN / 16;
   typedef GldsOperand<BM, AK> OA;
   typedef GldsOperand<BN, BKM> OB;
-  constexpr int ABYTES = OA::BYTES, STAGE = OA::BYTES + OB::BYTES;
-  constexpr int LPS = OA::L + OB::L;                    // LDS-DMA instructions per wave per stage
-  constexpr int NRA = MI * OA::RPF, NRB = NI * OB::RPF;  // LDS read instructions per wave per k-tile
-  constexpr int NMMA = MI * NI, NOTH = NRA + NRB + LPS;
-  static_assert(S * STAGE <= 65536, "immediate LDS offsets");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = (wave >> 1) * WTM, wn = (wave & 1) * WTN;
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  const int tile = bid % tiles, split = bid / tiles;
-  int bm0, bn0;
-  tile_of_block(p, BM, BN, tile, bm0, bn0);
-  const int nt_all = p.K / BK;
-  const int per = (nt_all + p.splits - 1) / p.splits;
-  const int kt0 = split * per, kt1 = (kt0 + per < nt_all) ? kt0 + per : nt_all;
-  const int nt = kt1 - kt0;
-  if (nt <= 0) return;
+  KLAB_GLDS_WORK(32)
 
   OA oa; OB ob;
   oa.init(reinterpret_cast<const T*>(p.A), p.lda, bm0, p.M, wave, lane, wm);
   ob.init(reinterpret_cast<const T*>(p.B), p.ldb, bn0, p.N, wave, lane, wn);
-  // k-tiles are visited in a per-workgroup rotated order: workgroups that share an A or B panel start together,
-  // and in lockstep they would all hit the same few L2 channels at once; rotating by the tile coordinates spreads
-  // each panel's readers over its whole K extent (only the fp32 summation order changes).
-  const int skew = ((bm0 / BM) * 5 + (bn0 / BN) * 3) % nt;
-  auto ktile = [&](int t) { int kk = t + skew; return kt0 + (kk >= nt ? kk - nt : kk); };
-  const unsigned sbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-
-  f32x4 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  u32x4 a0[MI], b0[NI], a1[MI], b1[NI];
-
-  // "other" operation o of a step: first the LDS reads of the next k-tile (early, so they have the rest of the step to
-  // land), then the LDS-DMA instructions.  SN = ring slot of the k-tile being read, SD = slot being refilled.
-#define KLAB_OTHER(O, SN, SD, NA, NB, DO_DMA, KT)                                                          \
-  if constexpr ((O) < NRA) oa.template read1<(O), (SN) * STAGE>(sbase, NA);                                \
-  else if constexpr ((O) < NRA + NRB) ob.template read1<(O) - NRA, (SN) * STAGE + ABYTES>(sbase, NB);       \
-  else if (DO_DMA) {                                                                                       \
-    constexpr int d = (O) - NRA - NRB;                                                                     \
-    if constexpr (d < OA::L) oa.issue1(d, KT, smem + (SD) * STAGE, wave);                                  \
-    else ob.issue1(d - OA::L, KT, smem + (SD) * STAGE + ABYTES, wave);                                     \
-  }
-  // MFMAs of the current fragments (CA, CB) with the other operations spread between them
-  auto mma_and = [&](auto sn_c, auto sd_c, const u32x4 (&ca)[MI], const u32x4 (&cb)[NI], u32x4 (&na)[MI], u32x4 (&nb)[NI],
-                     bool do_read, bool do_dma, int kt) {
-    constexpr int SN = decltype(sn_c)::value, SD = decltype(sd_c)::value;
-    auto other = [&](auto oc) {
-      constexpr int O = decltype(oc)::value;
-      if constexpr (O < NRA + NRB) { if (do_read) { KLAB_OTHER(O, SN, SD, na, nb, false, kt) } }
-      else { KLAB_OTHER(O, SN, SD, na, nb, do_dma, kt) }
-    };
-    auto unroll_other = [&](auto kc) {  // operations [k*NOTH/NMMA, (k+1)*NOTH/NMMA)
-      constexpr int k = decltype(kc)::value, lo = k * NOTH / NMMA, hi = (k + 1) * NOTH / NMMA;
-      if constexpr (hi - lo > 0) other(std::integral_constant<int, lo>{});
-      if constexpr (hi - lo > 1) other(std::integral_constant<int, lo + 1>{});
-      if constexpr (hi - lo > 2) other(std::integral_constant<int, lo + 2>{});
-      if constexpr (hi - lo > 3) other(std::integral_constant<int, lo + 3>{});
-      static_assert(hi - lo <= 4, "at most four slotted operations per MFMA gap");
-    };
-    auto one = [&](auto kc) {
-      constexpr int k = decltype(kc)::value, i = k / NI, j = k % NI;
-      if constexpr (ATOMIC) mfma_bf16_asm(acc[i][j], ca[i], cb[j]);
-      else mfma_bf16_asm(acc[i][j], cb[j], ca[i]);
-      unroll_other(kc);
-    };
-    [&]<int... Ks>(std::integer_sequence<int, Ks...>) { (one(std::integral_constant<int, Ks>{}), ...); }(std::make_integer_sequence<int, NMMA>{});
-  };
-
-  // prologue: k-tiles 0 .. S-1 fill the whole ring, the fragments of k-tile 0 come in
-#pragma unroll
-  for (int t = 0; t < S; ++t)
-    if (t < nt) {
-#pragma unroll
-      for (int d = 0; d < OA::L; ++d) oa.issue1(d, ktile(t), smem + t * STAGE, wave);
-#pragma unroll
-      for (int d = 0; d < OB::L; ++d) ob.issue1(d, ktile(t), smem + t * STAGE + ABYTES, wave);
-    }
-  wait_groups<LPS>((nt < S ? nt : S) - 1);  // k-tile 0 has landed
-  __builtin_amdgcn_s_barrier();
-  [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (oa.template read1<Rs, 0>(sbase, a0), ...); }(std::make_integer_sequence<int, NRA>{});
-  [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (ob.template read1<Rs, ABYTES>(sbase, b0), ...); }(std::make_integer_sequence<int, NRB>{});
-
-  int t = 0;
-  // one pipeline step on k-tile t held in (CA, CB) = ring slot SC: once every wave has its fragments of t in registers
-  // (lgkmcnt + barrier) slot SC is refilled with k-tile t+S, while k-tile t+1 (slot SC+1) is read into (NA, NB)
-#define KLAB_STEP(SC, CA, CB, NA, NB)                                                                                  \
-  {                                                                                                                   \
-    wait_lgkmcnt<0>();              /* fragments of k-tile t (issued one step ago) */                                  \
-    wait_vmcnt<(S - 2) * LPS>();    /* k-tile t+1 landed; S-2 younger groups stay in flight */                         \
-    __builtin_amdgcn_s_barrier();   /* t+1 visible to all waves; all waves hold k-tile t in registers: slot SC is free */ \
-    mma_and(std::integral_constant<int, ((SC) + 1) % S>{}, std::integral_constant<int, (SC)>{}, CA, CB, NA, NB, true, true, ktile(t + S)); \
-    ++t;                                                                                                              \
-  }
-  while (t + S + 3 < nt) {  // four straight-line steps: every step still has a k-tile to issue
-    KLAB_STEP(0, a0, b0, a1, b1)
-    KLAB_STEP(1, a1, b1, a0, b0)
-    KLAB_STEP(2, a0, b0, a1, b1)
-    KLAB_STEP(3, a1, b1, a0, b0)
-  }
-#undef KLAB_STEP
-  // Tail (t is a multiple of S; at most S+3 k-tiles): not pipelined.  Each step reads its own fragments into (a1, b1)
-  // and consumes them at once, so no asm-loaded register is live across a branch: hipcc copies such values at control
-  // flow merges, and a copy placed right behind the asm ds_read would pick the register up before the data lands.
-  auto mma_plain = [&](const u32x4 (&ca)[MI], const u32x4 (&cb)[NI]) {
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        if constexpr (ATOMIC) mfma_bf16_asm(acc[i][j], ca[i], cb[j]);
-        else mfma_bf16_asm(acc[i][j], cb[j], ca[i]);
-      }
-  };
-#define KLAB_TAIL(SC, FIRST)                                                                                              \
-  {                                                                                                                     \
-    if constexpr (!(FIRST)) {                                                                                           \
-      const int rem = nt - 1 - t;                                                                                       \
-      wait_groups<LPS>(rem < S - 1 ? rem : S - 1); /* k-tile t landed */                                                 \
-      __builtin_amdgcn_s_barrier();               /* ... for every wave */                                              \
-      [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (oa.template read1<Rs, (SC) * STAGE>(sbase, a1), ...); }(std::make_integer_sequence<int, NRA>{});          \
-      [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (ob.template read1<Rs, (SC) * STAGE + ABYTES>(sbase, b1), ...); }(std::make_integer_sequence<int, NRB>{}); \
-    }                                                                                                                   \
-    wait_lgkmcnt<0>();                                                                                                  \
-    if (t + S < nt) {                                                                                                   \
-      __builtin_amdgcn_s_barrier(); /* every wave holds k-tile t in registers: slot SC is free */                        \
-      _Pragma("unroll") for (int d = 0; d < OA::L; ++d) oa.issue1(d, ktile(t + S), smem + (SC) * STAGE, wave);           \
-      _Pragma("unroll") for (int d = 0; d < OB::L; ++d) ob.issue1(d, ktile(t + S), smem + (SC) * STAGE + ABYTES, wave);  \
-    }                                                                                                                   \
-    if constexpr (FIRST) mma_plain(a0, b0); /* prefetched by the prologue or by the last steady step */                  \
-    else mma_plain(a1, b1);                                                                                             \
-    ++t;                                                                                                                \
-  }
-  // Exactly four k-tiles left, all of them already issued (K a multiple of 128 -- every T5 / Swin width): they drain through the
-  // same pipelined step as the steady state, without the DMA slot (the general tail below reads each tile's fragments and waits
-  // for them before its MFMAs: three exposed LDS round trips per tile of C).  The fragments of k-tile t are waited for BEFORE the
-  // branch, so that a register copy hipcc may place at the branch cannot pick up data that has not landed.
-  wait_lgkmcnt<0>();
-  if (nt - t == 4) {
-    wait_vmcnt<2 * LPS>();
-    __builtin_amdgcn_s_barrier();
-    mma_and(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, a0, b0, a1, b1, true, false, 0);
-    wait_lgkmcnt<0>();
-    wait_vmcnt<LPS>();
-    __builtin_amdgcn_s_barrier();
-    mma_and(std::integral_constant<int, 2>{}, std::integral_constant<int, 1>{}, a1, b1, a0, b0, true, false, 0);
-    wait_lgkmcnt<0>();
-    wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-    mma_and(std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{}, a0, b0, a1, b1, true, false, 0);
-    wait_lgkmcnt<0>();
-    mma_plain(a1, b1);
-    t += 4;
-    // the accumulators must not be touched before the last MFMA has retired (no interlock for inline-asm MFMAs), and hipcc places
-    // register copies at the join of the two branches: the nops go INSIDE each branch (found the hard way: the last k-tile of
-    // every product was lost)
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-  } else {
-    KLAB_TAIL(0, true)
-    while (t < nt) {
-      KLAB_TAIL(1, false)
-      if (t >= nt) break;
-      KLAB_TAIL(2, false)
-      if (t >= nt) break;
-      KLAB_TAIL(3, false)
-      if (t >= nt) break;
-      KLAB_TAIL(0, false)
-    }
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-  }
-#undef KLAB_TAIL
-#undef KLAB_OTHER
-  // MFMA results are not interlocked against the v_accvgpr_read of the epilogue when the MFMA is inline asm
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-  wait_vmcnt<0>();
+  // operands swapped (the B tile as the MFMA "A" operand: a lane's four accumulator registers are four consecutive n), except
+  // for ATOMIC, whose float atomics then cover 16 consecutive n per wave-instruction
+#define KLAB_RING_MMA(ACC, A, B) if constexpr (ATOMIC) mfma_bf16_asm(ACC, A, B); else mfma_bf16_asm(ACC, B, A);
+#define KLAB_RING_TWO_BASES 0
+#define KLAB_RING_DRAIN4 1
+#include "gemm_glds_loop.h"
   float alpha = p.alpha;
   if (p.alpha_dev) alpha *= p.alpha_dev[0];
   if constexpr (ATOMIC) {
@@ -483,171 +329,27 @@ __device__ __forceinline__ void gemm_glds_body(const GemmP& p, const int bid = b
     staged_epilogue<T, BM, BN, MI, NI>(p, acc, alpha, smem, bm0, bn0, wm, wn, tid, lane);
   }
 }
+// 8 waves (4 x 2 of 64 x 64) on a 256 x 128 tile, A K-major; the 96 KB ring needs two LDS base registers
 template <bool BKM>
 __device__ __forceinline__ void gemm_glds_w8_body(const GemmP& p, const int bid = blockIdx.x) {
   typedef bf16_t T;
   constexpr int BM = 256, BN = 128;
-  constexpr bool AK = true, ATOMIC = false;
-  constexpr int BK = 32, S = KLAB_GLDS_STAGES;
-  static_assert(S == 4, "the steady-state loop is unrolled over a 4-stage ring");
-  constexpr int WTM = BM / 4, WTN = BN / 2, MI = WTM / 16, NI = WTN / 16;  // 4 x 2 waves of 64 x 64
-  typedef GldsOperand<BM, AK, 8, MI> OA;
+  constexpr int WTM = BM / 4, WTN = BN / 2, MI = WTM / 16, NI = WTN / 16;
+  typedef GldsOperand<BM, true, 8, MI> OA;
   typedef GldsOperand<BN, BKM, 8, NI> OB;
-  constexpr int ABYTES = OA::BYTES, STAGE = OA::BYTES + OB::BYTES;
-  constexpr int LPS = OA::L + OB::L;                    // LDS-DMA instructions per wave per stage
-  constexpr int NRA = MI * OA::RPF, NRB = NI * OB::RPF;  // LDS read instructions per wave per k-tile
-  constexpr int NMMA = MI * NI, NOTH = NRA + NRB + LPS;
-  static_assert(2 * STAGE + 8192 <= 65536, "immediate LDS offsets: two stages per base register");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = (wave >> 1) * WTM, wn = (wave & 1) * WTN;  // wave 0..7
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  const int tile = bid % tiles, split = bid / tiles;
-  int bm0, bn0;
-  tile_of_block(p, BM, BN, tile, bm0, bn0);
-  const int nt_all = p.K / BK;
-  const int per = (nt_all + p.splits - 1) / p.splits;
-  const int kt0 = split * per, kt1 = (kt0 + per < nt_all) ? kt0 + per : nt_all;
-  const int nt = kt1 - kt0;
-  if (nt <= 0) return;
+  KLAB_GLDS_WORK(32)
 
   OA oa; OB ob;
   oa.init(reinterpret_cast<const T*>(p.A), p.lda, bm0, p.M, wave, lane, wm);
   ob.init(reinterpret_cast<const T*>(p.B), p.ldb, bn0, p.N, wave, lane, wn);
-  // k-tiles are visited in a per-workgroup rotated order: workgroups that share an A or B panel start together,
-  // and in lockstep they would all hit the same few L2 channels at once; rotating by the tile coordinates spreads
-  // each panel's readers over its whole K extent (only the fp32 summation order changes).
-  const int skew = ((bm0 / BM) * 5 + (bn0 / BN) * 3) % nt;
-  auto ktile = [&](int t) { int kk = t + skew; return kt0 + (kk >= nt ? kk - nt : kk); };
-  // ds_read immediates are 16 bits and the ring is 96 KB: stages 0-1 are addressed from sb0, stages 2-3 from sb1
-  const unsigned sb0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem, sb1 = sb0 + 2 * STAGE;
-#define KLAB_SB(SN) (((SN) >> 1) ? sb1 : sb0)
-#define KLAB_SO(SN) (((SN) & 1) * STAGE)
-
-  f32x4 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  u32x4 a0[MI], b0[NI], a1[MI], b1[NI];
-
-  // "other" operation o of a step: first the LDS reads of the next k-tile (early, so they have the rest of the step to
-  // land), then the LDS-DMA instructions.  SN = ring slot of the k-tile being read, SD = slot being refilled.
-#define KLAB_OTHER(O, SN, SD, NA, NB, DO_DMA, KT)                                                          \
-  if constexpr ((O) < NRA) oa.template read1<(O), KLAB_SO(SN)>(KLAB_SB(SN), NA);                           \
-  else if constexpr ((O) < NRA + NRB) ob.template read1<(O) - NRA, KLAB_SO(SN) + ABYTES>(KLAB_SB(SN), NB);  \
-  else if (DO_DMA) {                                                                                       \
-    constexpr int d = (O) - NRA - NRB;                                                                     \
-    if constexpr (d < OA::L) oa.issue1(d, KT, smem + (SD) * STAGE, wave);                                  \
-    else ob.issue1(d - OA::L, KT, smem + (SD) * STAGE + ABYTES, wave);                                     \
-  }
-  // MFMAs of the current fragments (CA, CB) with the other operations spread between them
-  auto mma_and = [&](auto sn_c, auto sd_c, const u32x4 (&ca)[MI], const u32x4 (&cb)[NI], u32x4 (&na)[MI], u32x4 (&nb)[NI],
-                     bool do_read, bool do_dma, int kt) {
-    constexpr int SN = decltype(sn_c)::value, SD = decltype(sd_c)::value;
-    auto other = [&](auto oc) {
-      constexpr int O = decltype(oc)::value;
-      if constexpr (O < NRA + NRB) { if (do_read) { KLAB_OTHER(O, SN, SD, na, nb, false, kt) } }
-      else { KLAB_OTHER(O, SN, SD, na, nb, do_dma, kt) }
-    };
-    auto unroll_other = [&](auto kc) {  // operations [k*NOTH/NMMA, (k+1)*NOTH/NMMA)
-      constexpr int k = decltype(kc)::value, lo = k * NOTH / NMMA, hi = (k + 1) * NOTH / NMMA;
-      if constexpr (hi - lo > 0) other(std::integral_constant<int, lo>{});
-      if constexpr (hi - lo > 1) other(std::integral_constant<int, lo + 1>{});
-      if constexpr (hi - lo > 2) other(std::integral_constant<int, lo + 2>{});
-      if constexpr (hi - lo > 3) other(std::integral_constant<int, lo + 3>{});
-      static_assert(hi - lo <= 4, "at most four slotted operations per MFMA gap");
-    };
-    auto one = [&](auto kc) {
-      constexpr int k = decltype(kc)::value, i = k / NI, j = k % NI;
-      if constexpr (ATOMIC) mfma_bf16_asm(acc[i][j], ca[i], cb[j]);
-      else mfma_bf16_asm(acc[i][j], cb[j], ca[i]);
-      unroll_other(kc);
-    };
-    [&]<int... Ks>(std::integer_sequence<int, Ks...>) { (one(std::integral_constant<int, Ks>{}), ...); }(std::make_integer_sequence<int, NMMA>{});
-  };
-
-  // prologue: k-tiles 0 .. S-1 fill the whole ring, the fragments of k-tile 0 come in
-#pragma unroll
-  for (int t = 0; t < S; ++t)
-    if (t < nt) {
-#pragma unroll
-      for (int d = 0; d < OA::L; ++d) oa.issue1(d, ktile(t), smem + t * STAGE, wave);
-#pragma unroll
-      for (int d = 0; d < OB::L; ++d) ob.issue1(d, ktile(t), smem + t * STAGE + ABYTES, wave);
-    }
-  wait_groups<LPS>((nt < S ? nt : S) - 1);  // k-tile 0 has landed
-  __builtin_amdgcn_s_barrier();
-  [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (oa.template read1<Rs, 0>(sb0, a0), ...); }(std::make_integer_sequence<int, NRA>{});
-  [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (ob.template read1<Rs, ABYTES>(sb0, b0), ...); }(std::make_integer_sequence<int, NRB>{});
-
-  int t = 0;
-  // one pipeline step on k-tile t held in (CA, CB) = ring slot SC: once every wave has its fragments of t in registers
-  // (lgkmcnt + barrier) slot SC is refilled with k-tile t+S, while k-tile t+1 (slot SC+1) is read into (NA, NB)
-#define KLAB_STEP(SC, CA, CB, NA, NB)                                                                                  \
-  {                                                                                                                   \
-    wait_lgkmcnt<0>();              /* fragments of k-tile t (issued one step ago) */                                  \
-    wait_vmcnt<(S - 2) * LPS>();    /* k-tile t+1 landed; S-2 younger groups stay in flight */                         \
-    __builtin_amdgcn_s_barrier();   /* t+1 visible to all waves; all waves hold k-tile t in registers: slot SC is free */ \
-    mma_and(std::integral_constant<int, ((SC) + 1) % S>{}, std::integral_constant<int, (SC)>{}, CA, CB, NA, NB, true, true, ktile(t + S)); \
-    ++t;                                                                                                              \
-  }
-  while (t + S + 3 < nt) {  // four straight-line steps: every step still has a k-tile to issue
-    KLAB_STEP(0, a0, b0, a1, b1)
-    KLAB_STEP(1, a1, b1, a0, b0)
-    KLAB_STEP(2, a0, b0, a1, b1)
-    KLAB_STEP(3, a1, b1, a0, b0)
-  }
-#undef KLAB_STEP
-  // Tail (t is a multiple of S; at most S+3 k-tiles): not pipelined.  Each step reads its own fragments into (a1, b1)
-  // and consumes them at once, so no asm-loaded register is live across a branch: hipcc copies such values at control
-  // flow merges, and a copy placed right behind the asm ds_read would pick the register up before the data lands.
-  auto mma_plain = [&](const u32x4 (&ca)[MI], const u32x4 (&cb)[NI]) {
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        if constexpr (ATOMIC) mfma_bf16_asm(acc[i][j], ca[i], cb[j]);
-        else mfma_bf16_asm(acc[i][j], cb[j], ca[i]);
-      }
-  };
-#define KLAB_TAIL(SC, FIRST)                                                                                              \
-  {                                                                                                                     \
-    if constexpr (!(FIRST)) {                                                                                           \
-      const int rem = nt - 1 - t;                                                                                       \
-      wait_groups<LPS>(rem < S - 1 ? rem : S - 1); /* k-tile t landed */                                                 \
-      __builtin_amdgcn_s_barrier();               /* ... for every wave */                                              \
-      [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (oa.template read1<Rs, KLAB_SO(SC)>(KLAB_SB(SC), a1), ...); }(std::make_integer_sequence<int, NRA>{});          \
-      [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (ob.template read1<Rs, KLAB_SO(SC) + ABYTES>(KLAB_SB(SC), b1), ...); }(std::make_integer_sequence<int, NRB>{}); \
-    }                                                                                                                   \
-    wait_lgkmcnt<0>();                                                                                                  \
-    if (t + S < nt) {                                                                                                   \
-      __builtin_amdgcn_s_barrier(); /* every wave holds k-tile t in registers: slot SC is free */                        \
-      _Pragma("unroll") for (int d = 0; d < OA::L; ++d) oa.issue1(d, ktile(t + S), smem + (SC) * STAGE, wave);           \
-      _Pragma("unroll") for (int d = 0; d < OB::L; ++d) ob.issue1(d, ktile(t + S), smem + (SC) * STAGE + ABYTES, wave);  \
-    }                                                                                                                   \
-    if constexpr (FIRST) mma_plain(a0, b0); /* prefetched by the prologue or by the last steady step */                  \
-    else mma_plain(a1, b1);                                                                                             \
-    ++t;                                                                                                                \
-  }
-  KLAB_TAIL(0, true)
-  while (t < nt) {
-    KLAB_TAIL(1, false)
-    if (t >= nt) break;
-    KLAB_TAIL(2, false)
-    if (t >= nt) break;
-    KLAB_TAIL(3, false)
-    if (t >= nt) break;
-    KLAB_TAIL(0, false)
-  }
-#undef KLAB_TAIL
-#undef KLAB_OTHER
-#undef KLAB_SB
-#undef KLAB_SO
-  // MFMA results are not interlocked against the v_accvgpr_read of the epilogue when the MFMA is inline asm
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-  wait_vmcnt<0>();
+#define KLAB_RING_MMA(ACC, A, B) mfma_bf16_asm(ACC, B, A);
+#define KLAB_RING_TWO_BASES 1
+#define KLAB_RING_DRAIN4 0
+#include "gemm_glds_loop.h"
   float alpha = p.alpha;
   if (p.alpha_dev) alpha *= p.alpha_dev[0];
   __syncthreads();  // all LDS-DMA retired (vmcnt(0) above) and all fragment reads done: LDS is free for the epilogue
@@ -862,8 +564,8 @@ static int dispatch_layout(const GemmP& p, bool atomic, hipStream_t s) {
 // tile / split-K choice: the largest tile that still gives about one workgroup per CU; when even the
 // smallest does not and the caller allows atomic accumulation, split K until the chip is covered.
 int mm8p_try(const GemmP& pin, bool atomic_ok, int force, hipStream_t s);  // mm8p.hip: 256 x 256 tiles, eight waves, BK = 64
-int mmf8_try(const GemmP& pin, const float* sa, const float* sb, long sb_stride, int force, hipStream_t s);
-int mm8p_grouped_try(const klab_gemm_args* list, int n, hipStream_t s);  // mm8p.hip: a layer's weight gradients on 256 x 256 tiles  // mmf8.hip: block-scaled fp8 MFMA
+int mmf8_try(const GemmP& pin, const float* sa, const float* sb, long sb_stride, int force, hipStream_t s);  // mmf8.hip: block-scaled fp8 MFMA
+int mm8p_grouped_try(const klab_gemm_args* list, int n, hipStream_t s);  // mm8p.hip: a layer's weight gradients on 256 x 256 tiles
 
 template <typename T>
 static int dispatch_tile(GemmP& p, bool atomic_ok, hipStream_t s, int p8_force = 0) {
@@ -1037,32 +739,6 @@ __global__ __launch_bounds__(256) void gemm_fp8_kernel(GemmP p, Fp8Scales sc) {
 // contracts k in {16 g + 0..7}, the second k in {16 g + 8..15} (g = 0..3): together all 64, each once, and since A and B use the
 // same assignment the sum is the dot product.  Same ring, same waits, same hand schedule as gemm_glds_body; half the L2 -> LDS
 // bytes per FLOP, which is what bounds these products.
-template <int ROWS>
-struct GldsOperand8 {
-  static constexpr int L = ROWS / 64, BYTES = ROWS * 64, NF = ROWS / 32, RPF = 1;
-  const char* src[L];
-  unsigned foff[1];
-  __device__ __forceinline__ void init(const char* base, long ld, int row0, int nrows, int wave, int lane, int wrow0) {
-    const int lrow = lane >> 2, lpos = lane & 3;
-    const int lchunk = lpos ^ (((lrow >> 2) & 1) << 1);
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-      int r = row0 + (wave * L + i) * 16 + lrow;
-      r = r < nrows ? r : nrows - 1;
-      src[i] = base + (long)r * ld + lchunk * 16;
-    }
-    const int fr = lane & 15, fc = lane >> 4;
-    foff[0] = (unsigned)((wrow0 + fr) * 64 + ((fc ^ (((fr >> 2) & 1) << 1)) * 16));
-  }
-  __device__ __forceinline__ void issue1(int i, int kt, char* stage, int wave) const {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[i] + (long)kt * 64),
-                                     (__attribute__((address_space(3))) void*)(stage + (wave * L + i) * 1024), 16, 0, 0);
-  }
-  template <int R, int SOFF>
-  __device__ __forceinline__ void read1(unsigned sbase, u32x4 (&fr)[NF]) const {
-    fr[R] = lds_read_b128<SOFF + R * 1024>(sbase + foff[0]);
-  }
-};
 // both halves in ONE asm statement: the compiler sees a single use of the two 128-bit registers and cannot place a copy of an
 // asm-loaded (not yet landed) register between the LDS read and its wait
 __device__ __forceinline__ void mfma_fp8_asm2(f32x4& acc, const u32x4& x, const u32x4& y) {
@@ -1075,160 +751,23 @@ __device__ __forceinline__ void mfma_fp8_asm2(f32x4& acc, const u32x4& x, const 
 template <int BM, int BN>
 __device__ __forceinline__ void gemm_glds_fp8_body(const GemmP& p, const Fp8Scales& sc, const int bid = blockIdx.x) {
   typedef bf16_t T;  // output / epilogue element type
-  constexpr bool ATOMIC = false;
-  constexpr int BK = 64, S = KLAB_GLDS_STAGES;  // a k-tile is still 64 BYTES per row: 64 e4m3 values
-  static_assert(S == 4, "the steady-state loop is unrolled over a 4-stage ring");
+  constexpr int BK = 64;  // a k-tile is still 64 BYTES per row: 64 e4m3 values
   constexpr int WTM = BM / 2, WTN = BN / 2, MI = WTM / 16, NI = WTN / 16;
-  typedef GldsOperand8<BM> OA;
-  typedef GldsOperand8<BN> OB;
-  constexpr int ABYTES = OA::BYTES, STAGE = OA::BYTES + OB::BYTES;
-  constexpr int LPS = OA::L + OB::L;                    // LDS-DMA instructions per wave per stage
-  constexpr int NRA = MI * OA::RPF, NRB = NI * OB::RPF;  // LDS read instructions per wave per k-tile
-  constexpr int NMMA = MI * NI, NOTH = NRA + NRB + LPS;
-  static_assert(S * STAGE <= 65536, "immediate LDS offsets");
+  typedef GldsOperand<BM, true, 4, BM / 32, char> OA;
+  typedef GldsOperand<BN, true, 4, BN / 32, char> OB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = (wave >> 1) * WTM, wn = (wave & 1) * WTN;
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  const int tile = bid % tiles, split = bid / tiles;
-  int bm0, bn0;
-  tile_of_block(p, BM, BN, tile, bm0, bn0);
-  const int nt_all = p.K / BK;
-  const int per = (nt_all + p.splits - 1) / p.splits;
-  const int kt0 = split * per, kt1 = (kt0 + per < nt_all) ? kt0 + per : nt_all;
-  const int nt = kt1 - kt0;
-  if (nt <= 0) return;
+  KLAB_GLDS_WORK(BK)
 
   OA oa; OB ob;
   oa.init(reinterpret_cast<const char*>(p.A), p.lda, bm0, p.M, wave, lane, wm);
   ob.init(reinterpret_cast<const char*>(p.B), p.ldb, bn0, p.N, wave, lane, wn);
-  // k-tiles are visited in a per-workgroup rotated order: workgroups that share an A or B panel start together,
-  // and in lockstep they would all hit the same few L2 channels at once; rotating by the tile coordinates spreads
-  // each panel's readers over its whole K extent (only the fp32 summation order changes).
-  const int skew = ((bm0 / BM) * 5 + (bn0 / BN) * 3) % nt;
-  auto ktile = [&](int t) { int kk = t + skew; return kt0 + (kk >= nt ? kk - nt : kk); };
-  const unsigned sbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-
-  f32x4 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  u32x4 a0[MI], b0[NI], a1[MI], b1[NI];
-
-  // "other" operation o of a step: first the LDS reads of the next k-tile (early, so they have the rest of the step to
-  // land), then the LDS-DMA instructions.  SN = ring slot of the k-tile being read, SD = slot being refilled.
-#define KLAB_OTHER(O, SN, SD, NA, NB, DO_DMA, KT)                                                          \
-  if constexpr ((O) < NRA) oa.template read1<(O), (SN) * STAGE>(sbase, NA);                                \
-  else if constexpr ((O) < NRA + NRB) ob.template read1<(O) - NRA, (SN) * STAGE + ABYTES>(sbase, NB);       \
-  else if (DO_DMA) {                                                                                       \
-    constexpr int d = (O) - NRA - NRB;                                                                     \
-    if constexpr (d < OA::L) oa.issue1(d, KT, smem + (SD) * STAGE, wave);                                  \
-    else ob.issue1(d - OA::L, KT, smem + (SD) * STAGE + ABYTES, wave);                                     \
-  }
-  // MFMAs of the current fragments (CA, CB) with the other operations spread between them
-  auto mma_and = [&](auto sn_c, auto sd_c, const u32x4 (&ca)[MI], const u32x4 (&cb)[NI], u32x4 (&na)[MI], u32x4 (&nb)[NI],
-                     bool do_read, bool do_dma, int kt) {
-    constexpr int SN = decltype(sn_c)::value, SD = decltype(sd_c)::value;
-    auto other = [&](auto oc) {
-      constexpr int O = decltype(oc)::value;
-      if constexpr (O < NRA + NRB) { if (do_read) { KLAB_OTHER(O, SN, SD, na, nb, false, kt) } }
-      else { KLAB_OTHER(O, SN, SD, na, nb, do_dma, kt) }
-    };
-    auto unroll_other = [&](auto kc) {  // operations [k*NOTH/NMMA, (k+1)*NOTH/NMMA)
-      constexpr int k = decltype(kc)::value, lo = k * NOTH / NMMA, hi = (k + 1) * NOTH / NMMA;
-      if constexpr (hi - lo > 0) other(std::integral_constant<int, lo>{});
-      if constexpr (hi - lo > 1) other(std::integral_constant<int, lo + 1>{});
-      if constexpr (hi - lo > 2) other(std::integral_constant<int, lo + 2>{});
-      if constexpr (hi - lo > 3) other(std::integral_constant<int, lo + 3>{});
-      static_assert(hi - lo <= 4, "at most four slotted operations per MFMA gap");
-    };
-    auto one = [&](auto kc) {
-      constexpr int k = decltype(kc)::value, i = k / NI, j = k % NI;
-      mfma_fp8_asm2(acc[i][j], cb[j], ca[i]);
-      unroll_other(kc);
-    };
-    [&]<int... Ks>(std::integer_sequence<int, Ks...>) { (one(std::integral_constant<int, Ks>{}), ...); }(std::make_integer_sequence<int, NMMA>{});
-  };
-
-  // prologue: k-tiles 0 .. S-1 fill the whole ring, the fragments of k-tile 0 come in
-#pragma unroll
-  for (int t = 0; t < S; ++t)
-    if (t < nt) {
-#pragma unroll
-      for (int d = 0; d < OA::L; ++d) oa.issue1(d, ktile(t), smem + t * STAGE, wave);
-#pragma unroll
-      for (int d = 0; d < OB::L; ++d) ob.issue1(d, ktile(t), smem + t * STAGE + ABYTES, wave);
-    }
-  wait_groups<LPS>((nt < S ? nt : S) - 1);  // k-tile 0 has landed
-  __builtin_amdgcn_s_barrier();
-  [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (oa.template read1<Rs, 0>(sbase, a0), ...); }(std::make_integer_sequence<int, NRA>{});
-  [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (ob.template read1<Rs, ABYTES>(sbase, b0), ...); }(std::make_integer_sequence<int, NRB>{});
-
-  int t = 0;
-  // one pipeline step on k-tile t held in (CA, CB) = ring slot SC: once every wave has its fragments of t in registers
-  // (lgkmcnt + barrier) slot SC is refilled with k-tile t+S, while k-tile t+1 (slot SC+1) is read into (NA, NB)
-#define KLAB_STEP(SC, CA, CB, NA, NB)                                                                                  \
-  {                                                                                                                   \
-    wait_lgkmcnt<0>();              /* fragments of k-tile t (issued one step ago) */                                  \
-    wait_vmcnt<(S - 2) * LPS>();    /* k-tile t+1 landed; S-2 younger groups stay in flight */                         \
-    __builtin_amdgcn_s_barrier();   /* t+1 visible to all waves; all waves hold k-tile t in registers: slot SC is free */ \
-    mma_and(std::integral_constant<int, ((SC) + 1) % S>{}, std::integral_constant<int, (SC)>{}, CA, CB, NA, NB, true, true, ktile(t + S)); \
-    ++t;                                                                                                              \
-  }
-  while (t + S + 3 < nt) {  // four straight-line steps: every step still has a k-tile to issue
-    KLAB_STEP(0, a0, b0, a1, b1)
-    KLAB_STEP(1, a1, b1, a0, b0)
-    KLAB_STEP(2, a0, b0, a1, b1)
-    KLAB_STEP(3, a1, b1, a0, b0)
-  }
-#undef KLAB_STEP
-  // Tail (t is a multiple of S; at most S+3 k-tiles): not pipelined.  Each step reads its own fragments into (a1, b1)
-  // and consumes them at once, so no asm-loaded register is live across a branch: hipcc copies such values at control
-  // flow merges, and a copy placed right behind the asm ds_read would pick the register up before the data lands.
-  auto mma_plain = [&](const u32x4 (&ca)[MI], const u32x4 (&cb)[NI]) {
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        mfma_fp8_asm2(acc[i][j], cb[j], ca[i]);
-      }
-  };
-#define KLAB_TAIL(SC, FIRST)                                                                                              \
-  {                                                                                                                     \
-    if constexpr (!(FIRST)) {                                                                                           \
-      const int rem = nt - 1 - t;                                                                                       \
-      wait_groups<LPS>(rem < S - 1 ? rem : S - 1); /* k-tile t landed */                                                 \
-      __builtin_amdgcn_s_barrier();               /* ... for every wave */                                              \
-      [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (oa.template read1<Rs, (SC) * STAGE>(sbase, a1), ...); }(std::make_integer_sequence<int, NRA>{});          \
-      [&]<int... Rs>(std::integer_sequence<int, Rs...>) { (ob.template read1<Rs, (SC) * STAGE + ABYTES>(sbase, b1), ...); }(std::make_integer_sequence<int, NRB>{}); \
-    }                                                                                                                   \
-    wait_lgkmcnt<0>();                                                                                                  \
-    if (t + S < nt) {                                                                                                   \
-      __builtin_amdgcn_s_barrier(); /* every wave holds k-tile t in registers: slot SC is free */                        \
-      _Pragma("unroll") for (int d = 0; d < OA::L; ++d) oa.issue1(d, ktile(t + S), smem + (SC) * STAGE, wave);           \
-      _Pragma("unroll") for (int d = 0; d < OB::L; ++d) ob.issue1(d, ktile(t + S), smem + (SC) * STAGE + ABYTES, wave);  \
-    }                                                                                                                   \
-    if constexpr (FIRST) mma_plain(a0, b0); /* prefetched by the prologue or by the last steady step */                  \
-    else mma_plain(a1, b1);                                                                                             \
-    ++t;                                                                                                                \
-  }
-  KLAB_TAIL(0, true)
-  while (t < nt) {
-    KLAB_TAIL(1, false)
-    if (t >= nt) break;
-    KLAB_TAIL(2, false)
-    if (t >= nt) break;
-    KLAB_TAIL(3, false)
-    if (t >= nt) break;
-    KLAB_TAIL(0, false)
-  }
-#undef KLAB_TAIL
-#undef KLAB_OTHER
-  // MFMA results are not interlocked against the v_accvgpr_read of the epilogue when the MFMA is inline asm
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-  wait_vmcnt<0>();
+#define KLAB_RING_MMA(ACC, A, B) mfma_fp8_asm2(ACC, B, A);
+#define KLAB_RING_TWO_BASES 0
+#define KLAB_RING_DRAIN4 0
+#include "gemm_glds_loop.h"
   float alpha = p.alpha;
   if (p.alpha_dev) alpha *= p.alpha_dev[0];
   // dequantise: lane owns m = ... + (lane & 15), n = ... + (lane >> 4) * 4 + r  (the bf16 kernels' accumulator layout)

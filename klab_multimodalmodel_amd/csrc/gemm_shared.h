@@ -43,6 +43,10 @@ struct GemmP {
   int epi;  // feature set of the epilogue (EF_* bits), chosen on the host
 };
 
+// counted waits of the hand-scheduled loops: asm volatile, so hipcc neither moves them nor merges them into its own s_waitcnt
+template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+template <int N> __device__ __forceinline__ void wait_lgkmcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
+
 // Workgroup -> output tile.  Blocks are dealt round-robin over the 8 XCDs (b and b+8 share an L2), so the grid
 // is re-linearised to give every XCD one contiguous chunk of the tile sequence (bijective for any grid size),
 // and the sequence runs fastest along the dimension whose operand is SMALLER: that operand stays resident in

@@ -33,7 +33,6 @@ constexpr int NTHREADS = 512;
 constexpr int MIN_N = 64 * BN;  // narrower outputs stay with the tiled kernel
 constexpr int INFL = 4 * (R - 3);  // DMA instructions (four per k-tile and issuing wave) that may stay in flight behind the k-tile waited for
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void wg_barrier() {  // no LDS access may move across it
   asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -136,7 +135,7 @@ __global__ __launch_bounds__(NTHREADS) void klab_lmhead_areg_gemm(GemmP p) {
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt, ++j) {
       // k-tile j + 1 has landed: k-tiles up to j + R - 2 are issued, R - 3 of them younger than it
-      if (dma_wave) { if (j + R - 1 <= J) wait_vm<INFL>(); else wait_vm<0>(); }
+      if (dma_wave) { if (j + R - 1 <= J) wait_vmcnt<INFL>(); else wait_vmcnt<0>(); }
       wg_barrier();
       issue();  // k-tile j + R - 1 into the slot of k-tile j - 1: every wave is past its reads
       if (kt == 0 && tt > 0 && !dma_wave) store_tile(prev_tile);  // the tile staged before this barrier, while waves 0-3 refill the ring

@@ -109,9 +109,6 @@ __device__ __forceinline__ bf16x8 frag(const char* img, int f, int s, int lane) 
   }
 }
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 // Epilogue of one [128 x 256] slab.  The waves that own the slab park their RAW accumulators (f32) in LDS -- a store per
 // accumulator register, nothing else live -- and then all 512 threads walk the slab as whole row pieces (16 B of output per
 // lane, consecutive lanes on consecutive addresses) and apply the element-wise tail there: alpha, bias, activation, the
@@ -286,7 +283,7 @@ __device__ __forceinline__ void mm8p_body(const GemmP& p, const int bid) {
   // prologue: half-tiles 0..6; the first k-tile (0..3) must have landed, 4..6 stay in flight
   issue_half(0, W0{}, 0); issue_half(0, W1{}, 1); issue_half(0, W2{}, 2); issue_half(0, W3{}, 3);
   issue_half(1, W0{}, 4); issue_half(1, W1{}, 5); issue_half(1, W2{}, 6);
-  if (nt >= 2) wait_vm<6>(); else wait_vm<0>();
+  if (nt >= 2) wait_vmcnt<6>(); else wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
   // this wave's rows inside the half-tile images (see Operand::tile_row)
@@ -312,7 +309,7 @@ __device__ __forceinline__ void mm8p_body(const GemmP& p, const int bid) {
     issue_half(t + 1, W3{}, (BUF ^ 1) * 4 + 3);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
-    wait_lgkm0();
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -335,7 +332,7 @@ __device__ __forceinline__ void mm8p_body(const GemmP& p, const int bid) {
     issue_half(t + 2, W0{}, BUF * 4 + 0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
-    wait_lgkm0();
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -358,7 +355,7 @@ __device__ __forceinline__ void mm8p_body(const GemmP& p, const int bid) {
     issue_half(t + 2, W1{}, BUF * 4 + 1);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
-    wait_lgkm0();
+    wait_lgkmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -377,7 +374,7 @@ __device__ __forceinline__ void mm8p_body(const GemmP& p, const int bid) {
     issue_half(t + 2, W2{}, BUF * 4 + 2);
     // everything the next k-tile reads (half-tiles <= 4 t + 7) has landed once at most three younger half-tiles are in
     // flight; near the end of the k-range fewer have been issued, so the wait is for all of them
-    if (t + 2 < nt) wait_vm<6>(); else wait_vm<0>();
+    if (t + 2 < nt) wait_vmcnt<6>(); else wait_vmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -405,7 +402,7 @@ __device__ __forceinline__ void mm8p_body(const GemmP& p, const int bid) {
 
   // ---- epilogue -------------------------------------------------------------------------------------------------
   // accumulator (i, j) of this wave: tile rows  wm + (i >> 2) * 64 ... see row mapping: image row -> tile row
-  wait_vm<0>();
+  wait_vmcnt<0>();
   float alpha = p.alpha;
   if (p.alpha_dev) alpha *= p.alpha_dev[0];
   // tile row of accumulator block i (16 rows): m-half (i >> 2) lives in A half-tile (i >> 2) at image rows a_img_row0 + (i & 3) * 16,

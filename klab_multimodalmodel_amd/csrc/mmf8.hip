@@ -27,7 +27,6 @@ constexpr int BK = 128, NT = 256, S = 3;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <int ROWS>
 struct Operand {
@@ -96,7 +95,7 @@ __global__ __launch_bounds__(256) void mmf8_kernel(GemmP p, Scales sc) {
   const int unit = 0x7F7F7F7F;  // e8m0 block scales: 2^0 in every byte
   for (int t = 0; t < nt; ++t) {
     // k-tile t has landed (this wave's part; the barrier covers the others); t + 1 may stay in flight
-    if (t + 1 < nt) wait_vm<LPS>(); else wait_vm<0>();
+    if (t + 1 < nt) wait_vmcnt<LPS>(); else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     const char* As = smem + (t % S) * STAGE;
     const char* Bs = As + ABYTES;

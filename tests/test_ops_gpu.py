@@ -1105,3 +1105,57 @@ def test_gemm_eight_wave_256x128_tiles(ops, M, N, K, bk):
     c = torch.empty(M, N, device="cuda", dtype=dt)
     ops.gemm(dev(A), dev(B), c, M=M, N=N, K=K, b_kmajor=bk, bias=dev(bias), act=ops.L.ACT_RELU)
     assert rel_l2(c.float().cpu(), torch.relu(ref + bias)) < 4e-3
+
+
+# k-extent classes of the LDS-DMA ring's main loop (csrc/gemm_glds_loop.h; S = 4 stages).  nt = k-tiles per workgroup.
+_RING_BF16_K = [32, 64, 96, 128, 160, 224, 256, 288, 352, 384, 416]  # BK = 32: nt = 1, 2, 3, 4, 5, 7, 8, 9, 11, 12, 13
+_RING_CASES = ([("bf16", True, True, k) for k in _RING_BF16_K]
+               + [("bf16", True, False, 224), ("bf16", False, False, 256), ("bf16", False, True, 352)]
+               + [("w8", True, True, k) for k in (1088, 1120)]        # with 1024 / 1056 / 2048 of the test above: every nt mod 4
+               + [("fp8", True, True, k) for k in (64, 128, 256, 320, 512, 576, 768)])  # BK = 64: nt = 1, 2, 4, 5, 8, 9, 12
+
+
+@pytest.mark.parametrize("kind,ak,bk,K", _RING_CASES)
+def test_gemm_glds_ring_k_extent_classes(ops, kind, ak, bk, K):
+    """every way through the ring loop: a prologue shorter than the ring (nt < 4), the four-left drain straight after the prologue
+    (nt = 4) and after one steady round (nt = 8, 12), every exit of the general tail after no (nt = 5, 7) and one steady round
+    (nt = 9, 11, 13).  bf16: M = N = 64 is one workgroup of gemm_glds_kernel<64, 64> (reference and tolerance of
+    test_gemm_nt_epilogues / test_gemm_nn_tn_layouts); w8: gemm_glds_w8_kernel, which has no drain (those of
+    test_gemm_eight_wave_256x128_tiles); fp8: gemm_glds_fp8_kernel<64, 64> at the smallest M, N its dispatch accepts (those of
+    test_fp8_gemm_matches_emulated_quantisation)."""
+    dt = torch.bfloat16
+    if kind == "fp8":
+        from tests.helpers import fp8_rows
+        M = N = 16
+        a = rnd(M, K, seed=1, scale=2.0).to(dt)
+        b = rnd(N, K, seed=2, scale=0.05).to(dt)
+        qa, sa = fp8_rows(a)
+        qb, sb = fp8_rows(b)
+        a8, sa_k = ops.quant_fp8_rows(dev(a))
+        b8, sb_k = ops.quant_fp8_rows(dev(b))
+        ref = (qa @ qb.t()) * sa * sb.view(1, -1)
+        for out_dt in (dt, torch.float32):
+            c = torch.empty(M, N, device="cuda", dtype=out_dt)
+            ops.gemm_fp8(a8, sa_k, b8, sb_k, c)
+            assert rel_l2(c.float().cpu(), ref) < (4e-3 if out_dt == dt else 2e-4)
+        return
+    if kind == "w8":
+        M, N = 4896, 1024
+        A = rnd(M, K, seed=1).to(dt)
+        B = rnd(N, K, seed=2, scale=0.05).to(dt)
+        ref = A.float() @ B.float().t()
+        for out_dt in (dt, torch.float32):
+            c = torch.empty(M, N, device="cuda", dtype=out_dt)
+            ops.gemm(dev(A), dev(B), c, M=M, N=N, K=K)
+            assert rel_l2(c.float().cpu(), ref) < (4e-3 if out_dt == dt else 1e-5)
+        return
+    M = N = 64
+    A = rnd(*((M, K) if ak else (K, M)), seed=1).to(dt)
+    B = rnd(*((N, K) if bk else (K, N)), seed=2).to(dt)
+    ref = (A.float() if ak else A.float().t()) @ (B.float().t() if bk else B.float())
+    Cf = torch.empty(M, N, device="cuda")
+    ops.gemm(dev(A), dev(B), Cf, M=M, N=N, K=K, a_kmajor=ak, b_kmajor=bk)
+    assert rel_l2(Cf.cpu(), ref) < tol(dt)
+    Ct = torch.empty(M, N, device="cuda", dtype=dt)
+    ops.gemm(dev(A), dev(B), Ct, M=M, N=N, K=K, a_kmajor=ak, b_kmajor=bk)
+    assert rel_l2(Ct.float().cpu(), ref) < tol(dt) * 1.5
