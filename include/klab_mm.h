@@ -392,6 +392,9 @@ typedef struct klab_engine klab_engine;
 
 int klab_sizeof_t5_cfg(void);    /* sizeof(klab_t5_cfg) / sizeof(klab_model_cfg): the ctypes mirrors are checked against them */
 int klab_sizeof_model_cfg(void);
+int klab_sizeof_sample_args(void); /* likewise klab_sample_args, klab_logits_proc_args, klab_gen_cfg */
+int klab_sizeof_logits_proc_args(void);
+int klab_sizeof_gen_cfg(void);
 klab_engine* klab_engine_create(const klab_model_cfg* cfg); /* NULL on an invalid config (e.g. Swin width != d_model:
                                                                the reference raises at its torch.cat, model.py:23) */
 void klab_engine_destroy(klab_engine* e);
@@ -536,7 +539,9 @@ int klab_beam_copy_rows(int elem_bytes, const void* src, long src_ld, int src_di
  * Optional outputs (NULL: not written): warped [rows, ld_warped] f32, the processed scores (-inf = removed); done [rows]: a row
  * with done[r] != 0 draws pad_id, a row that draws eos_id gets done[r] = 1; tokens [rows]: the token; seq: seq[r*ld_seq + pos]
  * = the token (and seq[r*ld_seq] = start_id when pos == 1); stop_word: set to 1 by every row still unfinished (the caller
- * clears it).                                                                                                              */
+ * clears it); logprob: logprob[r*ld_logprob + pos] = the token's log-probability under the processed scores, log_softmax(s)[tok]
+ * = (s[tok] - M) - logf(G) with the row max M and the kept mass G = sum exp(s - M) the draw used (HF's compute_transition_scores
+ * with normalize_logits), 0 for a row with done[r] != 0 on entry.                                                           */
 typedef struct {
   int dtype;
   const void* logits; long ld; int row_div;
@@ -549,8 +554,17 @@ typedef struct {
   long long* tokens;
   long long* seq; long ld_seq; int pos;
   int* stop_word;
+  float* logprob; long ld_logprob; /* optional: logprob[r*ld_logprob + pos] (pos >= 1, ld_logprob > pos) */
 } klab_sample_args;
 int klab_sample_rows(const klab_sample_args* a, void* stream);
+/* The scores of finished sampling / pick rows from their per-token log-probabilities (csrc/sample.hip): one wave per image b < B
+ * over its n <= 64 rows b*n + j (KLAB_ERR_UNSUPPORTED above).  logprob [B*n, ld] f32 and seq [B*n, ld_seq] int64 hold positions
+ * 1 .. length - 1 (2 <= length <= ld, ld_seq).  len[r] = the generated tokens through the first eos_id, length - 1 without one (so
+ * never 0); score[r] = sum_{p = 1 .. len} logprob[r, p] / powf(len, length_penalty), summed in ascending p in fp32 by one thread
+ * (bit-reproducible; beam search's convention); order[b*n_out + i] = the row (b*n + j) of image b's i-th best score, i < n_out <= n,
+ * equal scores (two -inf included) in ascending row.  score, len and order are optional (NULL: not written).                 */
+int klab_gen_finalize(const float* logprob, long ld, const long long* seq, long ld_seq, int B, int n, int length, int eos_id,
+                      float length_penalty, int n_out, float* score, int* len, int* order, void* stream);
 
 /* ---- logits processors (HF's RepetitionPenalty, NoRepeatNGram, NoBadWords, MinLength, MinNewTokensLength, in that order;
  * csrc/logits_proc.hip) --------------------------------------------------------------------------------------------------
@@ -565,7 +579,9 @@ int klab_sample_rows(const klab_sample_args* a, void* stream);
  *   cur_len < min_length or cur_len - 1 < min_new_tokens: eos_id banned.
  * Banned = -inf.  Outputs: out [rows, ld_out] f32 (NULL allowed only with pick).  pick != 0: also the arg-max of the processed
  * row (the lowest id among equal maxima, 0 when every score is -inf) with klab_sample_rows' bookkeeping: done [rows], eos_id,
- * pad_id, tokens [rows], seq[r*ld_seq + cur_len] (and seq[r*ld_seq] = start_id when cur_len == 1), stop_word.             */
+ * pad_id, tokens [rows], seq[r*ld_seq + cur_len] (and seq[r*ld_seq] = start_id when cur_len == 1), stop_word; logprob (pick
+ * only, ignored otherwise; ld_logprob > cur_len): logprob[r*ld_logprob + cur_len] = log_softmax(processed row)[token], 0 for a row
+ * with done[r] != 0 on entry, -inf when every score is -inf.                                                             */
 typedef struct {
   int dtype;
   const void* logits; long ld; int row_div;
@@ -575,6 +591,7 @@ typedef struct {
   int n_bad; const int* bad_off; const int* bad_tok;
   float* out; long ld_out;
   int pick; int* done; int pad_id; long long* tokens; int* stop_word;
+  float* logprob; long ld_logprob; /* optional, pick only */
 } klab_logits_proc_args;
 int klab_logits_process_rows(const klab_logits_proc_args* a, void* stream);
 /* the beam top-2k of klab_beam_topk over scores that are already log-probabilities (f32, e.g. klab_logits_process_rows with
@@ -618,7 +635,14 @@ typedef struct {
  * gen_result: beam search: the first n <= num_beams of each sample's finished pool (sorted by score), length = max_length:
  *   seq [B*n, max_length] int64, scores [B*n] f32, len [B*n] int32 (generated tokens, the start token excluded).  Sampling
  *   and pick: n = the session's n, the first length <= (last position chosen) + 1 columns of the sequences into seq
- *   [B*n, length] int64 (start token, pad_id after EOS); scores and len unused (NULL).                                    */
+ *   [B*n, length] int64 (start token, pad_id after EOS); scores and len unused (NULL).
+ * want_logprobs (sampling and pick; with beam search the workspace size is 0, unsupported -- it keeps its own scores): the session
+ *   also keeps an f32 [M, max_length] buffer of per-token log-probabilities (gen_buffer "logprobs"), zeroed by gen_begin and
+ *   written by klab_sample_rows / the pick at every position (column 0 and everything after a row's EOS stay 0).  Without it a
+ *   session launches exactly what it launched before the field existed.
+ * gen_scores (want_logprobs sessions): klab_gen_finalize over the first length <= (last position chosen) + 1 columns: score [M]
+ *   f32, len [M] int32, order [B*n_out] int32 (n_out <= n <= 64; order may be NULL), and the log-probabilities themselves into
+ *   token_logprobs [M, length] f32 when not NULL.  All device memory.                                                     */
 #define KLAB_GEN_PICK 0
 #define KLAB_GEN_SAMPLE 1
 #define KLAB_GEN_BEAM 2
@@ -627,6 +651,7 @@ typedef struct {
   float temperature; int top_k; float top_p; unsigned long long seed; /* sampling only */
   float length_penalty; int early_stopping;                           /* beam search only */
   const klab_logits_proc_cfg* procs;
+  int want_logprobs;
 } klab_gen_cfg;
 size_t klab_engine_gen_workspace_bytes(klab_engine* e, const klab_gen_cfg* cfg);
 int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, void* ws, void* stream);
@@ -634,6 +659,8 @@ int klab_engine_gen_step(klab_engine* e, int t, void* ws, void* stream);
 const int* klab_engine_gen_stop_word(klab_engine* e, void* ws, int pos);
 const void* klab_engine_gen_buffer(klab_engine* e, void* ws, const char* name, long* rows, long* cols, int* dtype);
 int klab_engine_gen_result(klab_engine* e, void* ws, int n, int length, long long* seq, float* scores, int* len, void* stream);
+int klab_engine_gen_scores(klab_engine* e, void* ws, int length, int n_out, float length_penalty, float* token_logprobs, float* score,
+                           int* len, int* order, void* stream);
 /* segment 0: LM head + decoder + tied embedding; 1: encoder; 2: Swin (no-op unless train_swin).
  * dloss_dev: device scalar d(objective)/d(loss) (NULL = 1).                                       */
 int klab_engine_backward(klab_engine* e, int segment, const float* dloss_dev, void* stream);

@@ -65,7 +65,8 @@ class SampleArgs(C.Structure):  # klab_sample_args
     _fields_ = [("dtype", i32), ("logits", vp), ("ld", i64), ("row_div", i32), ("rows", i32), ("V", i32),
                 ("temperature", f32), ("top_k", i32), ("top_p", f32), ("seed", C.c_uint64), ("step", i32),
                 ("u_in", vp), ("warped", vp), ("ld_warped", i64), ("done", vp), ("eos_id", i32), ("pad_id", i32), ("start_id", i32),
-                ("tokens", vp), ("seq", vp), ("ld_seq", i64), ("pos", i32), ("stop_word", vp)]
+                ("tokens", vp), ("seq", vp), ("ld_seq", i64), ("pos", i32), ("stop_word", vp),
+                ("logprob", vp), ("ld_logprob", i64)]
 
 
 class LogitsProcArgs(C.Structure):  # klab_logits_proc_args
@@ -73,7 +74,8 @@ class LogitsProcArgs(C.Structure):  # klab_logits_proc_args
                 ("seq", vp), ("ld_seq", i64), ("cur_len", i32), ("start_id", i32),
                 ("repetition_penalty", f32), ("no_repeat_ngram_size", i32), ("min_length", i32), ("min_new_tokens", i32), ("eos_id", i32),
                 ("n_bad", i32), ("bad_off", vp), ("bad_tok", vp), ("out", vp), ("ld_out", i64),
-                ("pick", i32), ("done", vp), ("pad_id", i32), ("tokens", vp), ("stop_word", vp)]
+                ("pick", i32), ("done", vp), ("pad_id", i32), ("tokens", vp), ("stop_word", vp),
+                ("logprob", vp), ("ld_logprob", i64)]
 
 
 class LogitsProcCfg(C.Structure):  # klab_logits_proc_cfg
@@ -87,7 +89,7 @@ GEN_PICK, GEN_SAMPLE, GEN_BEAM = 0, 1, 2
 class GenCfg(C.Structure):  # klab_gen_cfg
     _fields_ = [("mode", i32), ("n", i32), ("max_length", i32), ("eos_id", i32), ("pad_id", i32),
                 ("temperature", f32), ("top_k", i32), ("top_p", f32), ("seed", C.c_uint64),
-                ("length_penalty", f32), ("early_stopping", i32), ("procs", C.POINTER(LogitsProcCfg))]
+                ("length_penalty", f32), ("early_stopping", i32), ("procs", C.POINTER(LogitsProcCfg)), ("want_logprobs", i32)]
 
 
 # every exported entry point of include/klab_mm.h: name -> argtypes (restype is always int)
@@ -125,6 +127,10 @@ SIGNATURES = {
     "klab_beam_copy_rows": [i32, vp, i64, i32, vp, i64, i32, i32, vp],
     "klab_sample_rows": [C.POINTER(SampleArgs), vp],
     "klab_logits_process_rows": [C.POINTER(LogitsProcArgs), vp],
+    "klab_gen_finalize": [vp, i64, vp, i64, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp],
+    "klab_sizeof_sample_args": [],
+    "klab_sizeof_logits_proc_args": [],
+    "klab_sizeof_gen_cfg": [],
     "klab_beam_topk_scores": [vp, i64, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "klab_dbias_reduce": [vp, i32, vp, i32, i32, i32, i32, vp],
     "klab_swin_mlp_fused": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],

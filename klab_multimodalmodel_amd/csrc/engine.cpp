@@ -1241,6 +1241,9 @@ int swin_backward(const Ctx& c, const float* dh0, float p_in);
 // ================================================================================================
 extern "C" int klab_sizeof_t5_cfg(void) { return (int)sizeof(klab_t5_cfg); }
 extern "C" int klab_sizeof_model_cfg(void) { return (int)sizeof(klab_model_cfg); }
+extern "C" int klab_sizeof_sample_args(void) { return (int)sizeof(klab_sample_args); }
+extern "C" int klab_sizeof_logits_proc_args(void) { return (int)sizeof(klab_logits_proc_args); }
+extern "C" int klab_sizeof_gen_cfg(void) { return (int)sizeof(klab_gen_cfg); }
 
 extern "C" klab_engine* klab_engine_create(const klab_model_cfg* cfg) {
   if (!cfg) return nullptr;
@@ -1990,6 +1993,7 @@ int make_procs(const klab_engine* e, const klab_logits_proc_cfg* cfg, ProcSet& l
 }
 bool gen_shape_ok(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp) {
   if (!e->bound || g.n < 1 || g.max_length < 2 || g.max_length - 1 > e->Lt) return false;
+  if (g.want_logprobs && g.mode == KLAB_GEN_BEAM) return false;  // beam search keeps its own scores
   const int V = e->cfg.main.vocab;
   switch (g.mode) {
     case KLAB_GEN_BEAM:
@@ -2011,9 +2015,11 @@ struct GenWs {
   float* fin_score; int *fin_flag, *fin_len, *unsat;
   // sampling and pick
   long long* seq; int* done;
+  float* logprob = nullptr;  // want_logprobs only: [M, max_length]
 };
 // decoder scratch, logits and self-attention cache for M = B*n rows, the mode's state, the next decoder inputs, the stop words, then
-// the processors' f32 rows [M, V] (not for pick, which writes none) and the bad-words table
+// the processors' f32 rows [M, V] (not for pick, which writes none), the bad-words table and, with want_logprobs, the per-token
+// log-probabilities [M, max_length] (last, so that every other buffer lies where it lies without them)
 size_t plan_gen(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp, void* base, GenWs& w) {
   Bump b(base);
   const klab_t5_cfg& cfg = e->cfg.main;
@@ -2047,6 +2053,7 @@ size_t plan_gen(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp, 
   w.prev = (long long*)b.take(M * 8); w.stop = (int*)b.take((long)Lm * 4);
   if (lp.on && g.mode != KLAB_GEN_PICK) w.proc = (float*)b.take(M * V * 4);
   if (!lp.table.empty()) w.table = (int*)b.take(lp.table.size() * 4);
+  if (g.want_logprobs) w.logprob = (float*)b.take(M * Lm * 4);
   return b.off;
 }
 klab_logits_proc_args proc_args(const ProcSet& lp, const int* table, int dtype, const void* logits, long ld, int row_div, int rows, int V,
@@ -2103,6 +2110,7 @@ int gen_pos(klab_engine* e, const Ctx& c, const GenWs& w, const void* logits, lo
                                         g.cfg.eos_id);
     if (g.cfg.mode == KLAB_GEN_PICK) {
       p.pick = 1; p.done = w.done; p.pad_id = g.cfg.pad_id; p.tokens = w.prev; p.stop_word = w.stop + pos;
+      p.logprob = w.logprob; p.ld_logprob = g.cfg.max_length;
       return klab_logits_process_rows(&p, c.ws());
     }
     p.out = w.proc; p.ld_out = V;
@@ -2117,6 +2125,7 @@ int gen_pos(klab_engine* e, const Ctx& c, const GenWs& w, const void* logits, lo
   a.seed = g.cfg.seed; a.step = pos;
   a.done = w.done; a.eos_id = g.cfg.eos_id; a.pad_id = g.cfg.pad_id; a.start_id = start;
   a.tokens = w.prev; a.seq = w.seq; a.ld_seq = g.cfg.max_length; a.pos = pos; a.stop_word = w.stop + pos;
+  a.logprob = w.logprob; a.ld_logprob = g.cfg.max_length;
   return klab_sample_rows(&a, c.ws());
 }
 }  // namespace
@@ -2150,6 +2159,7 @@ extern "C" int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, vo
   } else {
     RC((int)hipMemsetAsync(w.done, 0, (size_t)B * n * 4, c.s));
     RC((int)hipMemsetAsync(w.stop, 0, (size_t)Lm * 4, c.s));
+    if (w.logprob) RC((int)hipMemsetAsync(w.logprob, 0, (size_t)B * n * Lm * 4, c.s));
   }
   // position 0 (the start token) of every row: the prefill's self q|k|v row of its image, copied into the row's own slot
   for (int i = 0; i < mc.n_dec_layers; ++i)
@@ -2198,6 +2208,11 @@ extern "C" const void* klab_engine_gen_buffer(klab_engine* e, void* ws, const ch
     if (cols) *cols = 1;
     return w.prev;
   }
+  if (!strcmp(name, "logprobs") && w.logprob) {
+    if (cols) *cols = e->gen.cfg.max_length;
+    if (dtype) *dtype = KLAB_F32;
+    return w.logprob;
+  }
   return nullptr;
 }
 
@@ -2217,6 +2232,20 @@ extern "C" int klab_engine_gen_result(klab_engine* e, void* ws, int n, int lengt
   if (rc == hipSuccess) rc = hipMemcpy2DAsync(scores, n * 4, w.fin_score, k * 4, n * 4, B, hipMemcpyDeviceToDevice, s);
   if (rc == hipSuccess) rc = hipMemcpy2DAsync(len, n * 4, w.fin_len, k * 4, n * 4, B, hipMemcpyDeviceToDevice, s);
   return (int)rc;
+}
+
+extern "C" int klab_engine_gen_scores(klab_engine* e, void* ws, int length, int n_out, float length_penalty, float* token_logprobs,
+                                      float* score, int* len, int* order, void* stream) {
+  if (!e || !ws || e->gen.cur < 1 || !e->gen.cfg.want_logprobs || !score || !len) return KLAB_ERR_BADARG;
+  const klab_gen_cfg& g = e->gen.cfg;
+  if (length < 2 || length > e->gen.cur + 1) return KLAB_ERR_BADARG;
+  GenWs w;
+  plan_gen(e, g, e->gen.lp, ws, w);
+  const size_t Lm = g.max_length;
+  RC(klab_gen_finalize(w.logprob, (long)Lm, w.seq, (long)Lm, e->B, g.n, length, g.eos_id, length_penalty, n_out, score, len, order, stream));
+  if (!token_logprobs) return 0;
+  return (int)hipMemcpy2DAsync(token_logprobs, (size_t)length * 4, w.logprob, Lm * 4, (size_t)length * 4, (size_t)e->B * g.n,
+                               hipMemcpyDeviceToDevice, (hipStream_t)stream);
 }
 
 // segment 0: LM head + decoder + shared embedding; 1: encoder; 2: Swin

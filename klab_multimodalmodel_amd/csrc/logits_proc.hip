@@ -12,7 +12,8 @@
 //        penalised once, as HF's gather / scatter does), then -inf for the bans.  The bitmaps make the result independent of
 //        the order in which the atomics land;
 //     4. the dense fp32 row is written (optional in pick mode) and, in pick mode, the arg-max (lowest id among equal maxima) is
-//        taken with klab_sample_rows' bookkeeping: pad after done, done on EOS, the sequence write and the stop word.
+//        taken with klab_sample_rows' bookkeeping: pad after done, done on EOS, the sequence write and the stop word; on request
+//        also the pick's log-probability under the processed row, log_softmax(s)[tok] (one more sum-exp reduction).
 #include <math.h>
 
 #include "common.h"
@@ -156,15 +157,34 @@ __global__ __launch_bounds__(PROC_THREADS) void logits_process_rows_kernel(klab_
   }
   if (lane == 0) { s_f[0][wid] = bv; s_i[wid] = bi; }
   __syncthreads();
+  // HF's transition score of the pick: log_softmax of the processed row at its arg-max = -log(sum exp(s - max)); the waves' maxima
+  // are the row max, so the one extra reduction is the sum (s_f[1] is free since the log_softmax of step 1)
+  if (a.logprob) {
+    float M = s_f[0][0];
+    for (int q = 1; q < PROC_WAVES; ++q) M = fmaxf(M, s_f[0][q]);
+    float s = 0.f;
+    if (M > -INFINITY) {
+#pragma unroll
+      for (int c = 0; c < PROC_NPT; ++c) s += expf(v[c] - M);  // (the padding slots and the bans hold -inf: 0)
+    }
+    s = wave_sum(s);
+    if (lane == 0) s_f[1][wid] = s;
+    __syncthreads();
+  }
   if (tid != 0) return;
   for (int q = 1; q < PROC_WAVES; ++q)
     if (s_f[0][q] > bv || (s_f[0][q] == bv && s_i[q] < bi)) { bv = s_f[0][q]; bi = s_i[q]; }
   int tok = bi == INT_MAX ? 0 : bi;
-  int fin = 0;
+  int fin = 0, was = 0;
   if (a.done) {
-    fin = a.done[r];
+    fin = was = a.done[r];
     if (fin) tok = a.pad_id;
     else if (tok == a.eos_id) { fin = 1; a.done[r] = 1; }
+  }
+  if (a.logprob) {  // s[tok] is the row max: (s[tok] - max) - log(sum) = -log(sum); a row of -inf scores -inf, a row finished on entry 0
+    float S = 0.f;
+    for (int q = 0; q < PROC_WAVES; ++q) S += s_f[1][q];
+    a.logprob[(long)r * a.ld_logprob + L] = was ? 0.f : bv > -INFINITY ? -logf(S) : -INFINITY;
   }
   if (a.tokens) a.tokens[r] = tok;
   if (a.seq) {
@@ -180,7 +200,7 @@ extern "C" int klab_logits_process_rows(const klab_logits_proc_args* a, void* st
   using namespace klab;
   if (!a || !a->logits || a->rows <= 0 || a->V < 1 || a->row_div < 1 || a->ld < a->V || a->cur_len < 1 || !(a->repetition_penalty > 0.f) ||
       a->no_repeat_ngram_size < 0 || a->n_bad < 0 || (a->n_bad > 0 && (!a->bad_off || !a->bad_tok)) || (!a->out && !a->pick) ||
-      (a->out && a->ld_out < a->V) || (a->cur_len > 1 && !a->seq) || (a->pick && a->seq && a->ld_seq <= a->cur_len) ||
+      (a->out && a->ld_out < a->V) || (a->cur_len > 1 && !a->seq) || (a->pick && a->seq && a->ld_seq <= a->cur_len) || (a->pick && a->logprob && a->ld_logprob <= a->cur_len) ||
       (a->seq && a->ld_seq < a->cur_len))
     return KLAB_ERR_BADARG;
   if (a->V > PROC_THREADS * PROC_NPT || a->cur_len > PROC_MAX_HIST) return KLAB_ERR_UNSUPPORTED;

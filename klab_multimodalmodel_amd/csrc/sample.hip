@@ -13,6 +13,11 @@
 //        u * (sum of kept probability), with u in [0, 1) from sample_uniform(seed, step, row) below (or given by the caller);
 //     5. greedy's bookkeeping: a finished row (done[r]) draws pad; EOS sets done[r]; the token goes to tokens[r] and
 //        seq[r, pos]; stop_word = 1 while any row is unfinished.
+//     6. optionally the token's log-probability under the processed scores, log_softmax(s)[tok] = (s[tok] - M) - log G with the
+//        row max M and the kept mass G of step 4 (HF's compute_transition_scores(normalize_logits=True)); 0 for a finished row.
+//   klab_gen_finalize : one wave per image over the per-token log-probabilities of a finished session: each row's length (through
+//                       its first EOS), its score sum / length^length_penalty (beam search's convention), and the rows of the
+//                       image ranked by score (counting rank, ties to the lower row).
 //   The histograms live in LDS, replicated SAMPLE_REP times (lane % SAMPLE_REP; a 257-entry stride puts replicas on different
 //   banks) so that the many scores that share a top byte do not serialise on one address.  Counts and masses are integers
 //   (mass in units of 2^-40 in the upper 48 bits, count in the lower 16 of one uint64), so the result does not depend on the
@@ -258,13 +263,23 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(klab_sample
       if (tok < 0 && run > target) tok = c;
     }
   }
-  tok = j0 + (tok >= 0 ? tok : last);  // (rounding: the crossing fell past this thread's own sum -> its last kept token)
+  const int ct = tok >= 0 ? tok : last;  // (rounding: the crossing fell past this thread's own sum -> its last kept token)
+  tok = j0 + ct;
   // 5. bookkeeping
-  int fin = 0;
+  int fin = 0, was = 0;
   if (a.done) {
-    fin = a.done[r];
+    fin = was = a.done[r];
     if (fin) tok = a.pad_id;
     else if (tok == a.eos_id) { fin = 1; a.done[r] = 1; }
+  }
+  // HF's transition score of the draw: log_softmax of the processed row at the token, from the max and the kept mass the draw
+  // used (a row finished on entry draws a forced pad: 0)
+  if (a.logprob) {
+    uint32_t kt = 0;
+#pragma unroll
+    for (int c = 0; c < SAMPLE_NPT; ++c)
+      if (c == ct) kt = k[c];
+    a.logprob[(long)r * a.ld_logprob + a.pos] = was ? 0.f : (sample_val(kt) - M) - logf(G);
   }
   if (a.tokens) a.tokens[r] = tok;
   if (a.seq) {
@@ -274,12 +289,53 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(klab_sample
   if (a.stop_word && !fin) *a.stop_word = 1;  // every writer stores the same value
 }
 
+// lane j of block b owns row b*n + j: one thread sums its row in ascending position (fp32, no atomics: the same inputs give the
+// same bits), then the wave ranks the n scores by counting
+__global__ __launch_bounds__(64) void gen_finalize_kernel(const float* __restrict__ logprob, long ld, const long long* __restrict__ seq,
+                                                          long ld_seq, int n, int length, int eos_id, float length_penalty, int n_out,
+                                                          float* __restrict__ score, int* __restrict__ len, int* __restrict__ order) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const long r = (long)b * n + lane;
+  float sc = -INFINITY;
+  if (lane < n) {
+    int l = length - 1;
+    float sum = 0.f;
+    for (int p = 1; p < length; ++p) {
+      sum += logprob[r * ld + p];
+      if (seq[r * ld_seq + p] == eos_id) { l = p; break; }
+    }
+    sc = sum / powf((float)l, length_penalty);
+    if (score) score[r] = sc;
+    if (len) len[r] = l;
+  }
+  if (!order) return;
+  int rank = 0;
+  for (int i = 0; i < n; ++i) {
+    const float o = __shfl(sc, i, 64);
+    rank += (o > sc || (o == sc && i < lane)) ? 1 : 0;
+  }
+  if (lane < n && rank < n_out) order[(long)b * n_out + rank] = (int)r;
+}
+
 }  // namespace klab
+
+extern "C" int klab_gen_finalize(const float* logprob, long ld, const long long* seq, long ld_seq, int B, int n, int length, int eos_id,
+                                 float length_penalty, int n_out, float* score, int* len, int* order, void* stream) {
+  using namespace klab;
+  if (!logprob || !seq || B < 1 || n < 1 || length < 2 || ld < length || ld_seq < length || (order && (n_out < 1 || n_out > n)))
+    return KLAB_ERR_BADARG;
+  if (n > 64) return KLAB_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(gen_finalize_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, logprob, ld, seq, ld_seq, n, length, eos_id,
+                     length_penalty, n_out, score, len, order);
+  KLAB_LAUNCH_CHECK();
+  return KLAB_OK;
+}
 
 extern "C" int klab_sample_rows(const klab_sample_args* a, void* stream) {
   using namespace klab;
   if (!a || !a->logits || a->rows <= 0 || a->V < 1 || a->row_div < 1 || a->ld < a->V || !(a->temperature > 0.f) || a->top_k < 0 ||
-      !(a->top_p >= 0.f && a->top_p <= 1.f) || (a->warped && a->ld_warped < a->V) || (a->seq && (a->pos < 1 || a->ld_seq <= a->pos)))
+      !(a->top_p >= 0.f && a->top_p <= 1.f) || (a->warped && a->ld_warped < a->V) || (a->seq && (a->pos < 1 || a->ld_seq <= a->pos)) ||
+      (a->logprob && (a->pos < 1 || a->ld_logprob <= a->pos)))
     return KLAB_ERR_BADARG;
   if (a->V > SAMPLE_THREADS * SAMPLE_NPT) return KLAB_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;

@@ -124,6 +124,8 @@ ENGINE_SIGS = {
     "klab_engine_gen_stop_word": ([C.c_void_p, C.c_void_p, C.c_int], C.c_void_p),
     "klab_engine_gen_buffer": ([C.c_void_p, C.c_void_p, C.c_char_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)], C.c_void_p),
     "klab_engine_gen_result": ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "klab_engine_gen_scores": ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p], C.c_int),
     "klab_engine_backward": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_set_graph": ([C.c_void_p, C.c_int], C.c_int),
     "klab_engine_get_rng": ([C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p], C.c_int),
@@ -382,9 +384,10 @@ class Engine:
 
     @classmethod
     def gen_cfg(cls, mode, n, max_length, eos_id, pad_id, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=1.0,
-                early_stopping=False, procs=None):
+                early_stopping=False, procs=None, want_logprobs=False):
         """the klab_gen_cfg of a session; procs: the logits processors' settings (logits_proc.logits_processor_settings), None =
-        none.  The cfg keeps the C arrays it points to alive."""
+        none; want_logprobs: sampling and pick also keep every chosen token's log-probability (gen_scores).  The cfg keeps the C
+        arrays it points to alive."""
         cfg = L.GenCfg(cls.GEN_MODES[mode], int(n), int(max_length), int(eos_id), int(pad_id), float(temperature), int(top_k),
                        float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, float(length_penalty), cls.EARLY_STOPPING[early_stopping])
         if procs is not None:
@@ -398,6 +401,7 @@ class Engine:
             cfg.procs = C.pointer(L.LogitsProcCfg(float(procs["repetition_penalty"]), int(procs["no_repeat_ngram_size"]),
                                                   int(procs["min_length"]), int(procs["min_new_tokens"]), len(words),
                                                   C.cast(off_a, C.POINTER(C.c_int)), C.cast(tok_a, C.POINTER(C.c_int))))
+        cfg.want_logprobs = int(bool(want_logprobs))
         return cfg
 
     def gen_workspace_bytes(self, cfg):
@@ -426,7 +430,8 @@ class Engine:
         return bool((w & 1) and (w & 4) and (self._gen.early_stopping != 1 or (w & 2)))
 
     def gen_buffer(self, ws, name):
-        """a view into ws -- "logits": [B*n, vocab], the logits gen_step decoded last; "tokens": [B*n] int64, the next step's inputs"""
+        """a view into ws -- "logits": [B*n, vocab], the logits gen_step decoded last; "tokens": [B*n] int64, the next step's inputs;
+        "logprobs" (want_logprobs sessions): [B*n, max_length] f32, the log-probability of every token chosen so far"""
         rows, cols, dt = C.c_long(), C.c_long(), C.c_int()
         p = self._lib.klab_engine_gen_buffer(self._h, ws.data_ptr(), name.encode(), C.byref(rows), C.byref(cols), C.byref(dt))
         if not p:
@@ -450,6 +455,22 @@ class Engine:
         L.check(self._lib.klab_engine_gen_result(self._h, ws.data_ptr(), n, length, seq.data_ptr(), scores.data_ptr(), lens.data_ptr(),
                                                  L.stream_ptr()), "klab_engine_gen_result")
         return seq, scores, lens
+
+    def gen_scores(self, ws, length, n_out=None, length_penalty=1.0, want_tokens=True):
+        """a want_logprobs session's (token_logprobs [B*n, length] f32 or None, scores [B*n] f32 = sum / len ** length_penalty,
+        lengths [B*n] int32 through the first EOS, order [B*n_out] int32: each image's n_out best rows by score, or None) -- one
+        klab_gen_finalize launch, everything stays on the device"""
+        rows, length = self.shape[0] * self._gen.n, int(length)
+        dev = ws.device
+        lp = torch.empty(rows, length, dtype=torch.float32, device=dev) if want_tokens else None
+        scores = torch.empty(rows, dtype=torch.float32, device=dev)
+        lens = torch.empty(rows, dtype=torch.int32, device=dev)
+        order = torch.empty(self.shape[0] * int(n_out), dtype=torch.int32, device=dev) if n_out is not None else None
+        L.check(self._lib.klab_engine_gen_scores(self._h, ws.data_ptr(), length, int(n_out or 0), float(length_penalty),
+                                                 lp.data_ptr() if want_tokens else None, scores.data_ptr(), lens.data_ptr(),
+                                                 order.data_ptr() if order is not None else None, L.stream_ptr()),
+                "klab_engine_gen_scores")
+        return lp, scores, lens, order
 
     def backward(self, segment, dloss=None):
         L.check(self._lib.klab_engine_backward(self._h, segment, dloss.data_ptr() if dloss is not None else None, L.stream_ptr()),

@@ -376,7 +376,8 @@ class MyModel(nn.Module):
     @torch.no_grad()
     def generate(self, pixels, src, max_length=20, kv_cache=True, num_beams=1, length_penalty=1.0, early_stopping=False,
                  num_return_sequences=1, return_scores=False, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
-                 repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_length=0, min_new_tokens=None):
+                 repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_length=0, min_new_tokens=None,
+                 return_logprobs=False, best_of=None):
         """greedy decoding with HF's default generation settings (ref/models/model.py:28: max_length 20, no sampling).
         Every kv_cache=True call is one decoding session on the device (_generate_on_device; SURVEY §8 row f-3, HF/t5:308-332):
         prefill = one evaluation-mode forward (Swin, both encoders, the cross K/V of all layers, decoder position 0), then every
@@ -393,7 +394,29 @@ class MyModel(nn.Module):
         takes the arg-max (lowest id among ties, as torch.argmax), pads finished rows and sets the stop word.
         Limit: sampling, pick and beam search with processors need vocab_size <= 32768 (the register row of
         klab_logits_process_rows; every supported T5 checkpoint has 32100-32128) and raise ValueError above it, plain greedy
-        decoding included; a session also needs max_length >= 2.  kv_cache=False has neither limit."""
+        decoding included; a session also needs max_length >= 2.  kv_cache=False has neither limit.
+        return_logprobs=True (greedy and sampling on the K/V cache): returns (sequences, info) with info["token_logprobs"]
+        [rows, L] fp32 -- HF's transition score log_softmax(s)[token] of every generated token, s the processed scores the step
+        chose from (greedy: after the processors; sampling: after processors, temperature, top-k and top-p), written by the
+        choosing kernel itself; column 0 (the start token) and everything after a row's EOS are 0 -- info["lengths"] [rows] int32
+        (generated tokens through the first EOS) and info["scores"] [rows] = sum of the row's log-probabilities /
+        lengths ** length_penalty, beam search's convention.
+        best_of=N (sampling only, num_return_sequences <= N <= 64): draws N rows per image and returns the num_return_sequences
+        best by that score, best first, chosen and gathered on the device (klab_gen_finalize)."""
+        if return_logprobs or best_of is not None:
+            what = "return_logprobs" if return_logprobs else "best_of"
+            if num_beams > 1:
+                raise ValueError(f"{what} needs num_beams == 1 (beam search returns its own scores: return_scores=True)")
+            if not kv_cache:
+                raise ValueError(f"{what} runs on the K/V cache only: it needs kv_cache=True")
+        if best_of is not None:
+            if not do_sample:
+                raise ValueError("best_of ranks sampled sequences: it needs do_sample=True")
+            if not isinstance(best_of, int) or best_of < num_return_sequences:
+                raise ValueError(f"`best_of` ({best_of}) has to be an integer greater or equal to `num_return_sequences` "
+                                 f"({num_return_sequences})")
+            if best_of > 64:
+                raise ValueError(f"`best_of` ({best_of}) has to be at most 64")
         procs = logits_processor_settings(repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens,
                                           eos_token_id=self.main_cfg.eos_token_id, vocab_size=self.main_cfg.vocab_size)
         if do_sample:
@@ -413,7 +436,7 @@ class MyModel(nn.Module):
             if num_return_sequences < 1:
                 raise ValueError(f"`num_return_sequences` has to be a positive integer, but is {num_return_sequences}")
             return self._generate_sample(pixels, src, max_length, num_return_sequences, float(temperature), int(top_k), float(top_p),
-                                         procs)
+                                         procs, return_logprobs=return_logprobs, best_of=best_of, length_penalty=length_penalty)
         if num_return_sequences > num_beams:
             raise ValueError(f"`num_return_sequences` ({num_return_sequences}) has to be smaller or equal to `num_beams` ({num_beams}).")
         if num_beams > 1:
@@ -424,7 +447,8 @@ class MyModel(nn.Module):
         if return_scores:
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence scores)")
         if kv_cache:
-            return self._generate_sample(pixels, src, max_length, 1, 1.0, 0, 1.0, procs, pick=True)
+            return self._generate_sample(pixels, src, max_length, 1, 1.0, 0, 1.0, procs, pick=True, return_logprobs=return_logprobs,
+                                         length_penalty=length_penalty)
         if procs is not None:
             raise ValueError("logits processors run on the K/V cache only: repetition_penalty, no_repeat_ngram_size, bad_words_ids, "
                              "min_length and min_new_tokens need kv_cache=True")
@@ -452,7 +476,7 @@ class MyModel(nn.Module):
         return torch.cat([start, tgt], dim=1)
 
     def _generate_on_device(self, pixels, src, max_length, mode, n, procs=None, num_return_sequences=None, temperature=1.0, top_k=0,
-                            top_p=1.0, length_penalty=1.0, early_stopping=False):
+                            top_p=1.0, length_penalty=1.0, early_stopping=False, logprobs=False):
         """One prefill at B rows (Swin, both encoders and the cross K/V run once per image, not per row), then a decoding session of
         B*n rows on the device (row b*n + j: beam / sample j of image b, HF's `_expand_inputs_for_generation`): every step is the
         decoder over B*n rows and the mode's choice of the next tokens (`klab_engine_gen_step`); the host reads one stop word per
@@ -461,7 +485,10 @@ class MyModel(nn.Module):
         num_return_sequences; the draws come from a counter hash of one 64-bit seed taken from torch's default CPU generator per
         call (torch.manual_seed reproduces a call).  "pick": greedy decoding, the processed arg-max instead of a draw (no seed is
         taken).  Sampling and pick return [B*n, L] int64 (start token, pad after EOS, cropped when every row is done) and None.
-        procs: the logits processors' settings (logits_proc.logits_processor_settings), None = none."""
+        procs: the logits processors' settings (logits_proc.logits_processor_settings), None = none.
+        logprobs (sampling and pick): the session keeps every chosen token's log-probability and the second value returned is
+        info = dict(token_logprobs, scores, lengths) (see generate); with num_return_sequences < n the rows returned are each
+        image's num_return_sequences best by score, best first, ranked and gathered on the device."""
         if mode == "beam" and early_stopping not in (False, True, "never"):
             raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
         if max_length < 2:
@@ -479,7 +506,7 @@ class MyModel(nn.Module):
             eng = self._engine_for(pixels, src, tgt)
             eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
             gen = eng.gen_cfg(mode, n, max_length, cfg.eos_token_id, pad, temperature, top_k, top_p, seed, length_penalty, early_stopping,
-                              procs)
+                              procs, want_logprobs=logprobs)
             nbytes = eng.gen_workspace_bytes(gen)
             if nbytes == 0:
                 what = {"beam": f"beam search: unsupported num_beams={n}", "sample": f"sampling: unsupported num_return_sequences={n}",
@@ -492,7 +519,15 @@ class MyModel(nn.Module):
                 eng.gen_step(cur, ws)
                 cur += 1
             if mode != "beam":
-                return eng.gen_result(ws, n, cur + 1)[0], None
+                seq = eng.gen_result(ws, n, cur + 1)[0]
+                if not logprobs:
+                    return seq, None
+                n_out = num_return_sequences if num_return_sequences is not None and num_return_sequences < n else None
+                lp, scores, lens, order = eng.gen_scores(ws, cur + 1, n_out, length_penalty)
+                if order is not None:
+                    order = order.long()
+                    seq, lp, scores, lens = seq[order], lp[order], scores[order], lens[order]
+                return seq, dict(token_logprobs=lp, scores=scores, lengths=lens)
             seq, scores, lens = eng.gen_result(ws, num_return_sequences, max_length)
         finally:
             self.transformer.train(was_training)
@@ -505,10 +540,15 @@ class MyModel(nn.Module):
                                                length_penalty=length_penalty, early_stopping=early_stopping)
         return (seq, scores) if return_scores else seq
 
-    def _generate_sample(self, pixels, src, max_length, num_return_sequences, temperature, top_k, top_p, procs=None, pick=False):
-        """HF's `_sample` as a decoding session (_generate_on_device); pick=True: greedy decoding, the processed arg-max"""
-        return self._generate_on_device(pixels, src, max_length, "pick" if pick else "sample", num_return_sequences, procs,
-                                        temperature=temperature, top_k=top_k, top_p=top_p)[0]
+    def _generate_sample(self, pixels, src, max_length, num_return_sequences, temperature, top_k, top_p, procs=None, pick=False,
+                         return_logprobs=False, best_of=None, length_penalty=1.0):
+        """HF's `_sample` as a decoding session (_generate_on_device); pick=True: greedy decoding, the processed arg-max.
+        return_logprobs: (sequences, info); best_of: that many rows per image, the num_return_sequences best returned"""
+        n = num_return_sequences if best_of is None else best_of
+        seq, info = self._generate_on_device(pixels, src, max_length, "pick" if pick else "sample", n, procs,
+                                             num_return_sequences=num_return_sequences, temperature=temperature, top_k=top_k, top_p=top_p,
+                                             length_penalty=length_penalty, logprobs=return_logprobs or best_of is not None)
+        return (seq, info) if return_logprobs else seq
 
     def _join_pending_update(self):
         """an optimizer update still running on its own stream (optim.FusedAdam(step_in_backward=True)) writes the weights:
