@@ -85,6 +85,10 @@ int klab_quant_fp8_arena(const void* desc_dev, int ndesc, long total_rows, const
 /* n independent GEMMs.  Split-K weight-gradient members (bf16, both operands m-major, f32 C with accumulate + atomic_ok, no
  * epilogue extras) are batched into single launches of up to 8; every other member is run through klab_gemm. */
 int klab_gemm_grouped(const klab_gemm_args* list, int n, void* stream);
+/* the same with the choice of tile: large_tiles = 0 is klab_gemm_grouped; large_tiles = 1 runs the WHOLE list (at most 32 members) in one
+ * launch on 256 x 256 tiles without split-K or atomics when every member has that form (as above, and N >= 128, K % 64 == 0, K >= 1024,
+ * ldc % 4 == 0); a list with any other member, or with more than 32, is run whole as large_tiles = 0 would. */
+int klab_gemm_grouped_tiles(const klab_gemm_args* list, int n, int large_tiles, void* stream);
 
 /* ---- T5 RMS-norm (T5LayerNorm, HF/t5:59-72) ------------------------------------------------
  * y = drop(x * rsqrt(mean(x^2)+eps) * w); x is the f32 residual stream [rows,d]; y (dtype y_dtype)
@@ -191,7 +195,10 @@ typedef struct klab_attn_bwd_fused_args {
   klab_attn_args attn;
 } klab_attn_bwd_fused_args;
 int klab_t5_attn_bwd_fused(const klab_attn_bwd_fused_args* a, void* stream);
-/* dbias[H,Lq,Lk] += sum over nbatch slabs of ds_ws [nbatch, H, Lq, roundup(Lk,32)] (bf16), in a fixed order */
+/* dbias[H,Lq,Lk] += sum over nbatch slabs of ds_ws [nbatch, H, Lq, roundup(Lk,32)] (bf16).  nbatch <= 64: one pass over the
+ * slabs in a fixed order (bit-reproducible).  nbatch > 64: the slabs are cut into min(nbatch / 16, 32) chunks of consecutive slabs, each
+ * chunk is summed in order and the chunks' sums are added to dbias with float atomics (the last bits then vary run to run).  The pad
+ * columns Lk .. roundup(Lk,32)-1 of a slab are never read. */
 int klab_dbias_reduce(const void* ds_ws, int dtype, float* dbias, int nbatch, int H, int Lq, int Lk, void* stream);
 
 /* ---- Swin-V2 shifted-window cosine attention (HF/swinv2:389-455 + roll/partition/mask/reverse of

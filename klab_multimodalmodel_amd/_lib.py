@@ -135,6 +135,7 @@ SIGNATURES = {
     "klab_dbias_reduce": [vp, i32, vp, i32, i32, i32, i32, vp],
     "klab_swin_mlp_fused": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
     "klab_gemm_grouped": [vp, i32, vp],
+    "klab_gemm_grouped_tiles": [vp, i32, i32, vp],
     "klab_gemm_fp8": [C.POINTER(GemmArgs), vp, vp, i64, vp],
     "klab_quant_fp8_rows": [vp, i64, i32, i32, vp, i64, vp, vp],
     "klab_quant_fp8_arena": [vp, i32, i64, vp, vp, vp, vp],

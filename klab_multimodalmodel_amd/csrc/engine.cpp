@@ -900,9 +900,7 @@ struct WgradQueue {
     const bool probe = c.e->probe_on && pr.n < (int)pr.a.size();
     // (the grouped launch itself carries the events as its start / stop events: no extra packets on the stream)
     if (probe) { klab::tl_launch_probe.a = pr.a[pr.n]; klab::tl_launch_probe.b = pr.b[pr.n]; }
-    klab::tl_grouped_large_tiles = large;
-    const int grc = klab_gemm_grouped(gs.data(), (int)gs.size(), cs.ws());
-    klab::tl_grouped_large_tiles = false;
+    const int grc = klab_gemm_grouped_tiles(gs.data(), (int)gs.size(), large ? 1 : 0, cs.ws());
     RC(grc);
     if (probe) {
       if (klab::tl_launch_probe.a) klab::tl_launch_probe.a = nullptr;  // no grouped launch happened (members went through klab_gemm)

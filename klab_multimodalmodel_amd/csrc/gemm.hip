@@ -565,7 +565,7 @@ static int dispatch_layout(const GemmP& p, bool atomic, hipStream_t s) {
 // smallest does not and the caller allows atomic accumulation, split K until the chip is covered.
 int mm8p_try(const GemmP& pin, bool atomic_ok, int force, hipStream_t s);  // mm8p.hip: 256 x 256 tiles, eight waves, BK = 64
 int mmf8_try(const GemmP& pin, const float* sa, const float* sb, long sb_stride, int force, hipStream_t s);  // mmf8.hip: block-scaled fp8 MFMA
-int mm8p_grouped_try(const klab_gemm_args* list, int n, hipStream_t s);  // mm8p.hip: a layer's weight gradients on 256 x 256 tiles
+int mm8p_grouped_try(const klab_gemm_args* list, int n, bool large_tiles, hipStream_t s);  // mm8p.hip: a layer's weight gradients on 256 x 256 tiles
 
 template <typename T>
 static int dispatch_tile(GemmP& p, bool atomic_ok, hipStream_t s, int p8_force = 0) {
@@ -864,13 +864,13 @@ __global__ __launch_bounds__(256) void quant_fp8_arena_kernel(const QuantDesc* _
 
 }  // namespace klab
 
-// klab_gemm_grouped: see include/klab_mm.h.  Members that do not fit the grouped kernel's form are launched one by one.
+// klab_gemm_grouped[_tiles]: see include/klab_mm.h.  Members that do not fit the grouped kernel's form are launched one by one.
 extern "C" int klab_gemm(const klab_gemm_args* a, void* stream);
-extern "C" int klab_gemm_grouped(const klab_gemm_args* list, int n, void* stream) {
+extern "C" int klab_gemm_grouped_tiles(const klab_gemm_args* list, int n, int large_tiles, void* stream) {
   using namespace klab;
   if (!list || n < 0) return KLAB_ERR_BADARG;
-  {  // lists the engine marks with tl_grouped_large_tiles: the whole list on 256 x 256 tiles without split-K (mm8p.hip)
-    const int rc = mm8p_grouped_try(list, n, (hipStream_t)stream);
+  {  // large_tiles: the whole list on 256 x 256 tiles without split-K (mm8p.hip) when every member fits that form
+    const int rc = mm8p_grouped_try(list, n, large_tiles != 0, (hipStream_t)stream);
     if (rc != KLAB_ERR_UNSUPPORTED) return rc;
   }
   GroupP g;
@@ -929,6 +929,7 @@ extern "C" int klab_gemm_grouped(const klab_gemm_args* list, int n, void* stream
   }
   return flush();
 }
+extern "C" int klab_gemm_grouped(const klab_gemm_args* list, int n, void* stream) { return klab_gemm_grouped_tiles(list, n, 0, stream); }
 
 namespace klab {
 // klab_gemm_args -> kernel parameters + the epilogue variant (shared by the bf16 / f32 and the fp8 entry points)

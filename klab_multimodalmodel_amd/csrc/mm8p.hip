@@ -474,9 +474,9 @@ __global__ __launch_bounds__(512) void mm8p_grouped_tn_kernel(Group8P g) {
 
 // grouped weight gradients on the large tiles: returns KLAB_ERR_UNSUPPORTED unless EVERY member fits (the caller then uses the
 // 128 x 128 split-K grouped kernel for the whole list)
-int mm8p_grouped_try(const klab_gemm_args* list, int n, hipStream_t s) {
+int mm8p_grouped_try(const klab_gemm_args* list, int n, bool large_tiles, hipStream_t s) {
   using namespace p8;
-  if (!tl_grouped_large_tiles || n <= 0 || n > GROUP_MAX) return KLAB_ERR_UNSUPPORTED;
+  if (!large_tiles || n <= 0 || n > GROUP_MAX) return KLAB_ERR_UNSUPPORTED;
   Group8P g;
   g.n = 0;
   int blocks = 0;

@@ -14,10 +14,9 @@ def _seed_ptr(seed):
     return None if seed is None else seed.data_ptr()
 
 
-def gemm(A, B, C_out, *, M, N, K, a_kmajor=True, b_kmajor=True, lda=None, ldb=None, ldc=None, alpha=1.0,
-         alpha_dev=None, bias=None, act=L.ACT_NONE, aux=None, aux_mode=L.AUX_NONE, aux_scale=1.0, residual=None,
-         drop_p=0.0, seed=None, tag=0, accumulate=False, atomic_ok=False, name_tag=0):
-    lib = L.load()
+def _gemm_args(A, B, C_out, *, M, N, K, a_kmajor=True, b_kmajor=True, lda=None, ldb=None, ldc=None, alpha=1.0,
+               alpha_dev=None, bias=None, act=L.ACT_NONE, aux=None, aux_mode=L.AUX_NONE, aux_scale=1.0, residual=None,
+               drop_p=0.0, seed=None, tag=0, accumulate=False, atomic_ok=False, name_tag=0):
     a = L.GemmArgs()
     a.atomic_ok, a.name_tag = int(atomic_ok), name_tag
     a.M, a.N, a.K = M, N, K
@@ -36,8 +35,28 @@ def gemm(A, B, C_out, *, M, N, K, a_kmajor=True, b_kmajor=True, lda=None, ldb=No
     a.ldr = residual.stride(0) if residual is not None else 0
     a.r_dtype = L.dtype_code(residual.dtype) if residual is not None else 0
     a.drop_p, a.seed_dev, a.drop_tag = drop_p, _seed_ptr(seed), tag
+    return a
+
+
+def gemm(A, B, C_out, **kw):
+    """C_out = epilogue(alpha * A B^T): the keywords are the fields of klab_gemm_args (see _gemm_args)"""
+    lib = L.load()
+    a = _gemm_args(A, B, C_out, **kw)
     L.check(lib.klab_gemm(C.byref(a), L.stream_ptr()), "klab_gemm")
     return C_out
+
+
+def gemm_grouped(members, large_tiles=False):
+    """n independent GEMMs in one call (klab_gemm_grouped_tiles): `members` is a list of dicts, each holding the operands A, B, C and
+    the keywords of `gemm`.  large_tiles: ask for the 256 x 256 grouped kernel (the whole list falls back to the 128-wide grouping
+    when a member does not have its form, or when there are more than 32 members)."""
+    lib = L.load()
+    arr = (L.GemmArgs * max(len(members), 1))()
+    for i, m in enumerate(members):
+        kw = dict(m)
+        arr[i] = _gemm_args(kw.pop("A"), kw.pop("B"), kw.pop("C"), **kw)
+    L.check(lib.klab_gemm_grouped_tiles(C.cast(arr, C.c_void_p), len(members), int(bool(large_tiles)), L.stream_ptr()),
+            "klab_gemm_grouped_tiles")
 
 
 def quant_fp8_rows(x):
@@ -89,6 +108,31 @@ def rmsnorm_bwd(dy, x, w, rstd, dres=None, dx=None, dxt=None, dw=None, grp=0, gr
     L.check(lib.klab_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(), rstd.data_ptr(), L.ptr(dres), L.ptr(dx), L.ptr(dxt),
                                  L.dtype_code(dxt.dtype) if dxt is not None else 0, L.ptr(dw), rows, d, grp, grp_stride, off,
                                  p_y, tag_y, p_prev, tag_prev, _seed_ptr(seed), L.stream_ptr()), "klab_rmsnorm_bwd")
+
+
+def rmsnorm_part_rows(rows):
+    """rows of the partial-sum buffer klab_rmsnorm_bwd_part writes for `rows` input rows"""
+    return int(L.load().klab_rmsnorm_part_rows(int(rows)))
+
+
+def rmsnorm_bwd_part(dy, x, w, rstd, dw_part, dres=None, dx=None, dxt=None, grp=0, grp_stride=0, off=0, p_y=0.0, tag_y=0,
+                     p_prev=0.0, tag_prev=0, seed=None):
+    """rmsnorm_bwd with the weight gradient left as per-workgroup partial sums: dw_part [rmsnorm_part_rows(rows), d] is overwritten"""
+    lib = L.load()
+    rows, d = x.shape
+    L.check(lib.klab_rmsnorm_bwd_part(dy.data_ptr(), x.data_ptr(), w.data_ptr(), rstd.data_ptr(), L.ptr(dres), L.ptr(dx), L.ptr(dxt),
+                                      L.dtype_code(dxt.dtype) if dxt is not None else 0, dw_part.data_ptr(), rows, d, grp, grp_stride,
+                                      off, p_y, tag_y, p_prev, tag_prev, _seed_ptr(seed), L.stream_ptr()), "klab_rmsnorm_bwd_part")
+
+
+def colpart_reduce(part, call_stride, nparts, d, dsts):
+    """dsts[c][:d] += sum_b part[c * call_stride + b * d + :d] for b < nparts: `part` is a flat f32 buffer, `dsts` a list of f32
+    vectors (one per call)"""
+    lib = L.load()
+    table = torch.tensor([t.data_ptr() for t in dsts], dtype=torch.int64).to(part.device)
+    L.check(lib.klab_colpart_reduce(part.data_ptr(), int(call_stride), int(nparts), int(d), table.data_ptr(), len(dsts), L.stream_ptr()),
+            "klab_colpart_reduce")
+    return table  # (read by the kernel already enqueued: the caching allocator keeps its memory ordered behind the stream)
 
 
 def layernorm_fwd(y, gamma, beta, shortcut=None, out=None, outt=None, mean=None, rstd=None, eps=1e-5, grp=0, grp_stride=0,
@@ -243,7 +287,7 @@ def t5_attn_fused_fwd(x, gamma, w, xn, rstd, proj, ctx, lse, *, B, H, Lq, Lk, dk
 
 def t5_attn_bwd(q, k, v, ctx, lse, dctx, dq, dk_out, dv, *, B, H, Lq, Lk, dk, bias=None, causal=False, dbias=None,
                 drop_p=0.0, seed=None, tag=0, ldq=None, ldk=None, ldv=None, ldo=None, lddo=None, lddq=None, lddk=None,
-                lddv=None, ds_ws=None):
+                lddv=None, ds_ws=None, ds_defer=False):
     lib = L.load()
     a = _attn_args(q, k, v, ctx, lse, bias, causal, B, H, Lq, Lk, dk, drop_p, seed, tag,
                    ldq or q.stride(0), ldk or k.stride(0), ldv or v.stride(0), ldo or ctx.stride(0))
@@ -252,7 +296,7 @@ def t5_attn_bwd(q, k, v, ctx, lse, dctx, dq, dk_out, dv, *, B, H, Lq, Lk, dk, bi
     a.dk_out, a.lddk = dk_out.data_ptr(), lddk or dk_out.stride(0)
     a.dv, a.lddv = dv.data_ptr(), lddv or dv.stride(0)
     a.dbias = L.ptr(dbias)
-    a.ds_ws = L.ptr(ds_ws)
+    a.ds_ws, a.ds_defer = L.ptr(ds_ws), int(ds_defer)
     L.check(lib.klab_t5_attn_bwd(C.byref(a), L.stream_ptr()), "klab_t5_attn_bwd")
 
 
@@ -271,6 +315,13 @@ def t5_attn_bwd_fused(dy, w, q, k, v, ctx, lse, dq, dk_out, dv, *, B, H, Lq, Lk,
     a.dbias, a.ds_ws, a.ds_defer = L.ptr(dbias), L.ptr(ds_ws), int(ds_defer)
     fb.attn = a
     L.check(lib.klab_t5_attn_bwd_fused(C.byref(fb), L.stream_ptr()), "klab_t5_attn_bwd_fused")
+
+
+def dbias_reduce(ds_ws, dbias, *, nbatch, H, Lq, Lk):
+    """dbias [H, Lq, Lk] += sum of the nbatch stored-dS slabs ds_ws [nbatch, H, Lq, roundup(Lk, 32)] (bf16)"""
+    lib = L.load()
+    L.check(lib.klab_dbias_reduce(ds_ws.data_ptr(), L.dtype_code(ds_ws.dtype), dbias.data_ptr(), nbatch, H, Lq, Lk, L.stream_ptr()),
+            "klab_dbias_reduce")
 
 
 def _swin_args(qkv, ctx, bias, logit_scale, lse, B, R, w, shift, H, Cc, bias_table=None, v_bias=None, dv_bias=None):
@@ -342,6 +393,12 @@ def ce_fwd(logits, labels, inv_n, loss_row, loss, write_grad=True):
                             inv_n.data_ptr(), loss_row.data_ptr(), loss.data_ptr(), int(write_grad), L.stream_ptr()), "klab_ce_fwd")
 
 
+def ce_count(labels, inv_n):
+    """inv_n[0] = 1 / (number of labels != -100), 0 when there is none"""
+    lib = L.load()
+    L.check(lib.klab_ce_count(labels.data_ptr(), labels.numel(), inv_n.data_ptr(), L.stream_ptr()), "klab_ce_count")
+
+
 def embed_fwd(ids, table, out, *, shift_right=False, L_seq=1, start_id=0, pad_id=0, drop_p=0.0, seed=None, tag=0, err=None):
     lib = L.load()
     rows, d = out.shape
@@ -400,6 +457,42 @@ def colsum(dy, out):
 def convert(x, y, scale=1.0):
     lib = L.load()
     L.check(lib.klab_convert(x.data_ptr(), y.data_ptr(), L.dtype_code(y.dtype), x.numel(), scale, L.stream_ptr()), "klab_convert")
+
+
+# ---- descriptor-table kernels: `desc` is an int64 device tensor [n, fields] in the struct layout of the kernel's table ----------
+def cast_pack(desc, total4, dst):
+    """multi-tensor f32 -> dst.dtype cast into the flat buffer `dst`; desc [n, 3] rows of CastDesc {src pointer, dst_off (elements),
+    n4_prefix (exclusive prefix sum of the tensors' lengths / 4)}, total4 the sum of all lengths / 4"""
+    lib = L.load()
+    assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 3 and desc.is_contiguous()
+    L.check(lib.klab_cast_pack(desc.data_ptr(), desc.shape[0], int(total4), dst.data_ptr(), L.dtype_code(dst.dtype), L.stream_ptr()),
+            "klab_cast_pack")
+
+
+def quant_fp8_arena(desc, total_rows, arena_bf16, arena_fp8, scales):
+    """every row of the listed tensors of a bf16 arena -> e4m3 bytes at the same element offsets of arena_fp8 (uint8), the row's scale at
+    scales[(off + r*K) / 8]; desc [n, 4] rows of QuantDesc {off, rows, K, row0 (exclusive prefix sum of rows)}"""
+    lib = L.load()
+    assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 4 and desc.is_contiguous()
+    L.check(lib.klab_quant_fp8_arena(desc.data_ptr(), desc.shape[0], int(total_rows), arena_bf16.data_ptr(), arena_fp8.data_ptr(),
+                                     scales.data_ptr(), L.stream_ptr()), "klab_quant_fp8_arena")
+
+
+def adam_step(desc, total4, grads, m, v, arena, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, bias_corr1=1.0, bias_corr2=1.0,
+              begin4=None, end4=None):
+    """one torch.optim.Adam update of every tensor of the table (klab_adam_step), or of the vec4 range [begin4, end4) of its prefix
+    space (klab_adam_step_range); desc [n, 4] rows of AdamDesc {p pointer, goff (element offset into grads / m / v), aoff (element
+    offset of the compute-dtype copy in `arena`, < 0: none), n4_prefix}, total4 the sum of all lengths / 4"""
+    lib = L.load()
+    assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 4 and desc.is_contiguous()
+    hyper = (float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), float(bias_corr1), float(bias_corr2))
+    if begin4 is None and end4 is None:
+        L.check(lib.klab_adam_step(desc.data_ptr(), desc.shape[0], int(total4), grads.data_ptr(), m.data_ptr(), v.data_ptr(),
+                                   arena.data_ptr(), L.dtype_code(arena.dtype), *hyper, L.stream_ptr()), "klab_adam_step")
+    else:
+        L.check(lib.klab_adam_step_range(desc.data_ptr(), desc.shape[0], int(begin4), int(end4), grads.data_ptr(), m.data_ptr(),
+                                         v.data_ptr(), arena.data_ptr(), L.dtype_code(arena.dtype), *hyper, L.stream_ptr()),
+                "klab_adam_step_range")
 
 
 def image_preprocess(src_u8, desc, n, max_h, max_w, pixel_values, *, mid=256, out=224, filter_a=3, filter_b=2,
