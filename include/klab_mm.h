@@ -236,6 +236,15 @@ size_t klab_swin_attn_bwd_ws_bytes(int dtype, int B, int R, int w, int H, int C)
  * bf16, head dim 32, C in {64, 128, 256}, w*w <= 64; otherwise KLAB_ERR_UNSUPPORTED (caller: klab_gemm + klab_swin_attn_fwd). */
 int klab_swin_qkv_attn_fused(const void* x, const void* wqkv, const float* bqkv, void* ctx, const float* bias, const float* logit_scale,
                              int dtype, int B, int R, int w, int shift, int H, int C, void* stream);
+/* The same kernel on a pre-arranged bias image (built once per weight version from the dense bias [H, n, n] of klab_swin_cpb_bias):
+ * image [classes, H, 4, 64, 16] f32 -- query tile qt, lane, then (t, r) t-major, the order in which the score MFMA's lane holds
+ * query qt*16 + (lane & 15) x key t*16 + (lane >> 4)*4 + r.  Value: bias[h][min(q, n-1)][min(key, n-1)], -200 added where the shift
+ * regions of q and key differ, -inf where key >= n.  classes = 4 with shift > 0 (2 * (window in the last window row) + (window in
+ * the last window column)), else 1.  klab_swin_qkv_attn_fused_img takes the image in place of bias; ctx is bit-identical.      */
+size_t klab_swin_bias_image_bytes(int w, int shift, int H);
+int klab_swin_bias_image(const float* bias, float* image, int R, int w, int shift, int H, void* stream);
+int klab_swin_qkv_attn_fused_img(const void* x, const void* wqkv, const float* bqkv, void* ctx, const float* image, const float* logit_scale,
+                                 int dtype, int B, int R, int w, int shift, int H, int C, void* stream);
 int klab_swin_attn_bwd(const klab_swin_attn_args* a, void* stream);
 /* continuous position bias (HF/swinv2:376-378,418-428): coords [(2w-1)^2,2], index [n*n] are the
  * input-independent buffers of HF/swinv2:457-492; table [(2w-1)^2,H] and hidden [(2w-1)^2,512]

@@ -140,6 +140,9 @@ SIGNATURES = {
     "klab_quant_fp8_rows": [vp, i64, i32, i32, vp, i64, vp, vp],
     "klab_quant_fp8_arena": [vp, i32, i64, vp, vp, vp, vp],
     "klab_swin_qkv_attn_fused": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "klab_swin_bias_image_bytes": [i32, i32, i32],
+    "klab_swin_bias_image": [vp, vp, i32, i32, i32, i32, vp],
+    "klab_swin_qkv_attn_fused_img": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "klab_swin_linear_ln_fused": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
     "klab_swin_patch_embed_fused": [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp],
     "klab_swin_proj_ln_fused": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
@@ -207,7 +210,7 @@ def load():
     for name, argt in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.argtypes = argt
-        fn.restype = C.c_size_t if name.endswith("_ws_bytes") else i32
+        fn.restype = C.c_size_t if name.endswith("_bytes") else i32
     _lib = lib
     return lib
 

@@ -296,13 +296,15 @@ struct SwinQkvP {
   int B, R, w, shift, H;
 };
 
-template <int C>
-__global__ __launch_bounds__(64) void swin_qkv_attn_fused(SwinQkvP p) {
+// IMG: p.bias is the pre-arranged image of swin_bias_image_kernel (bias + shift mask + key padding, in the score MFMA's lane order)
+// instead of the dense [H, n, n] table: one fmaf per score, no region table, no clamped scalar fetches.
+template <int C, bool IMG>
+__device__ __forceinline__ void swin_qkv_attn_body(const SwinQkvP& p) {
   constexpr int HD = 32, KP = 80, KB = C / 32;
   __shared__ __attribute__((aligned(16))) char Kr[64 * KP];
   __shared__ __attribute__((aligned(16))) char Vt[8 * 896];
   __shared__ int tok[64];
-  __shared__ int reg[64];
+  __shared__ int reg[IMG ? 1 : 64];
   const int w = p.w, n = w * w, R = p.R, H = p.H;
   const int nWr = R / w, nW = nWr * nWr;
   const int lane = threadIdx.x, g = lane >> 4, lr = lane & 15;
@@ -318,7 +320,8 @@ __global__ __launch_bounds__(64) void swin_qkv_attn_fused(SwinQkvP p) {
       t = (b * R + y) * R + x;
       rg = p.shift > 0 ? swin_region(ys, R, w, p.shift) * 3 + swin_region(xs, R, w, p.shift) : 0;
     }
-    tok[lane] = t; reg[lane] = rg;
+    tok[lane] = t;
+    if constexpr (!IMG) reg[lane] = rg;
   }
   __syncthreads();
   bf16x8 qh[4];  // Q-hat of the 4 query tiles, kappa feature order
@@ -371,6 +374,7 @@ __global__ __launch_bounds__(64) void swin_qkv_attn_fused(SwinQkvP p) {
     load_x(0, xnext);
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
+      if constexpr (IMG) __builtin_amdgcn_sched_barrier(0);  // no loads of later tiles hoisted over this one (the register bound leaves no room)
       bf16x8 xf[KB];
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) xf[kb] = xnext[kb];
@@ -420,13 +424,21 @@ __global__ __launch_bounds__(64) void swin_qkv_attn_fused(SwinQkvP p) {
   }
   __syncthreads();
   const float scale = __expf(fminf(p.logit_scale[h], 4.6051701859880914f));
+  // image class of this window: with a shift only the last window row / column holds more than one mask region
+  const int cls = IMG && p.shift > 0 ? (wy == nWr - 1) * 2 + (wx == nWr - 1) : 0;
   auto fetch_bias = [&](int qt, f32x4 (&bv)[4]) {
-    const int q = qt * 16 + lr;
-    const float* brow = p.bias + ((long)h * n + (q < n ? q : n - 1)) * n;
+    if constexpr (IMG) {
+      const float* ip = p.bias + ((((long)cls * H + h) * 4 + qt) * 64 + lane) * 16;
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+      for (int t = 0; t < 4; ++t) bv[t] = *reinterpret_cast<const f32x4*>(ip + t * 4);
+    } else {
+      const int q = qt * 16 + lr;
+      const float* brow = p.bias + ((long)h * n + (q < n ? q : n - 1)) * n;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { const int key = t * 16 + g * 4 + r; bv[t][r] = brow[key < n ? key : n - 1]; }
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { const int key = t * 16 + g * 4 + r; bv[t][r] = brow[key < n ? key : n - 1]; }
+    }
   };
   const int nqt = (n + 15) / 16;
   f32x4 bnext[4];
@@ -436,7 +448,8 @@ __global__ __launch_bounds__(64) void swin_qkv_attn_fused(SwinQkvP p) {
     if (qt >= nqt) break;
     const int q = qt * 16 + lr;
     const int qc = q < n ? q : n - 1;
-    const int tq = tok[qc], rq = reg[qc];
+    if constexpr (IMG) __builtin_amdgcn_sched_barrier(0);
+    const int tq = tok[qc], rq = IMG ? 0 : reg[qc];
     f32x4 bcur[4] = {bnext[0], bnext[1], bnext[2], bnext[3]};
     if (qt + 1 < nqt) fetch_bias(qt + 1, bnext);
     f32x4 st[4];
@@ -450,10 +463,15 @@ __global__ __launch_bounds__(64) void swin_qkv_attn_fused(SwinQkvP p) {
       st[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qh[qt], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int key = t * 16 + g * 4 + r;
-        // branch-free (reg[] has all 64 slots, the bias fetch is clamped): -100 twice for another shift region (HF/swinv2:433-436)
-        float x = st[t][r] * scale + bcur[t][r] + (reg[key] != rq ? -200.f : 0.f);
-        x = key < n ? x : -INFINITY;
+        float x;
+        if constexpr (IMG) {
+          x = fmaf(st[t][r], scale, bcur[t][r]);  // mask and padding are in the image (a masked score ends as P = 0 either way)
+        } else {
+          const int key = t * 16 + g * 4 + r;
+          // branch-free (reg[] has all 64 slots, the bias fetch is clamped): -100 twice for another shift region (HF/swinv2:433-436)
+          x = st[t][r] * scale + bcur[t][r] + (reg[key] != rq ? -200.f : 0.f);
+          x = key < n ? x : -INFINITY;
+        }
         st[t][r] = x;
         m = fmaxf(m, x);
       }
@@ -491,6 +509,34 @@ __global__ __launch_bounds__(64) void swin_qkv_attn_fused(SwinQkvP p) {
             bf16x4{(bf16_t)o[dt][0], (bf16_t)o[dt][1], (bf16_t)o[dt][2], (bf16_t)o[dt][3]};
     }
   }
+}
+
+template <int C>
+__global__ __launch_bounds__(64) void swin_qkv_attn_fused(SwinQkvP p) { swin_qkv_attn_body<C, false>(p); }
+
+// second launch bound = waves per SIMD the register allocation must admit: 3 at C = 64 (all the 12.5 KB of LDS allow), 2 above
+template <int C>
+__global__ __launch_bounds__(64, C <= 64 ? 3 : 2) void swin_qkv_attn_fused_img(SwinQkvP p) { swin_qkv_attn_body<C, true>(p); }
+
+// bias [H, n, n] -> image [classes, H, 4, 64, 16] (klab_mm.h): one thread per float
+__global__ __launch_bounds__(256) void swin_bias_image_kernel(const float* __restrict__ bias, float* __restrict__ image, int R, int w, int shift,
+                                                              int H, int total) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int n = w * w;
+  const int r = i & 3, t = (i >> 2) & 3, lane = (i >> 4) & 63, qt = (i >> 10) & 3;
+  const int h = (i >> 12) % H, cls = (i >> 12) / H;
+  const int q = qt * 16 + (lane & 15), key = t * 16 + (lane >> 4) * 4 + r;
+  const int qc = q < n ? q : n - 1, kc = key < n ? key : n - 1;
+  // a window of class cls starts at R - w in the rows (cls & 2) / columns (cls & 1), else where every region is 0
+  const int y0 = (cls & 2) ? R - w : 0, x0 = (cls & 1) ? R - w : 0;
+  int rq = 0, rk = 0;
+  if (shift > 0) {
+    rq = ((cls & 2) ? swin_region(y0 + qc / w, R, w, shift) : 0) * 3 + ((cls & 1) ? swin_region(x0 + qc % w, R, w, shift) : 0);
+    rk = ((cls & 2) ? swin_region(y0 + kc / w, R, w, shift) : 0) * 3 + ((cls & 1) ? swin_region(x0 + kc % w, R, w, shift) : 0);
+  }
+  const float b = bias[((long)h * n + qc) * n + kc];
+  image[i] = key < n ? (rq != rk ? b + -200.f : b) : -INFINITY;
 }
 
 // Backward of the same (used when --image_model_train, ref/models/model.py:15): lane i owns query row
@@ -1185,6 +1231,35 @@ extern "C" int klab_swin_qkv_attn_fused(const void* x, const void* wqkv, const f
   if (C == 64) hipLaunchKernelGGL(swin_qkv_attn_fused<64>, dim3(B * nW * H), dim3(64), 0, s, p);
   else if (C == 128) hipLaunchKernelGGL(swin_qkv_attn_fused<128>, dim3(B * nW * H), dim3(64), 0, s, p);
   else if (C == 256) hipLaunchKernelGGL(swin_qkv_attn_fused<256>, dim3(B * nW * H), dim3(64), 0, s, p);
+  else return KLAB_ERR_UNSUPPORTED;
+  KLAB_LAUNCH_CHECK();
+  return KLAB_OK;
+}
+
+extern "C" size_t klab_swin_bias_image_bytes(int w, int shift, int H) {
+  if (w <= 0 || w * w > 64 || H <= 0 || shift < 0) return 0;
+  return (size_t)(shift > 0 ? 4 : 1) * H * 4 * 64 * 16 * sizeof(float);
+}
+
+extern "C" int klab_swin_bias_image(const float* bias, float* image, int R, int w, int shift, int H, void* stream) {
+  if (!bias || !image || R <= 0 || w <= 0 || H <= 0) return KLAB_ERR_BADARG;
+  if (w * w > 64 || R % w || shift < 0 || shift >= w) return KLAB_ERR_UNSUPPORTED;
+  const int total = (int)(klab_swin_bias_image_bytes(w, shift, H) / sizeof(float));
+  hipLaunchKernelGGL(swin_bias_image_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, bias, image, R, w, shift, H, total);
+  KLAB_LAUNCH_CHECK();
+  return KLAB_OK;
+}
+
+extern "C" int klab_swin_qkv_attn_fused_img(const void* x, const void* wqkv, const float* bqkv, void* ctx, const float* image,
+                                            const float* logit_scale, int dtype, int B, int R, int w, int shift, int H, int C, void* stream) {
+  if (!x || !wqkv || !ctx || !image || !logit_scale || B <= 0 || R <= 0 || w <= 0 || H <= 0) return KLAB_ERR_BADARG;
+  if (dtype != KLAB_BF16 || C != H * 32 || w * w > 64 || R % w || shift < 0 || shift >= w) return KLAB_ERR_UNSUPPORTED;
+  SwinQkvP p{(const bf16_t*)x, (const bf16_t*)wqkv, bqkv, (bf16_t*)ctx, image, logit_scale, B, R, w, shift, H};
+  const int nW = (R / w) * (R / w);
+  hipStream_t s = (hipStream_t)stream;
+  if (C == 64) hipLaunchKernelGGL(swin_qkv_attn_fused_img<64>, dim3(B * nW * H), dim3(64), 0, s, p);
+  else if (C == 128) hipLaunchKernelGGL(swin_qkv_attn_fused_img<128>, dim3(B * nW * H), dim3(64), 0, s, p);
+  else if (C == 256) hipLaunchKernelGGL(swin_qkv_attn_fused_img<256>, dim3(B * nW * H), dim3(64), 0, s, p);
   else return KLAB_ERR_UNSUPPORTED;
   KLAB_LAUNCH_CHECK();
   return KLAB_OK;

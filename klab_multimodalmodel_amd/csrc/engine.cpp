@@ -63,12 +63,15 @@ struct T5StackBufs {
   float* bias = nullptr; float* dbias = nullptr; const int* bucket = nullptr;
   int M = 0, Lseq = 0;
 };
+// widths at which swin_qkv_attn_fused_img measured faster than the dense-table kernel; the others keep the latter
+inline bool swin_attn_on_image(int C) { return C == 64 || C == 128 || C == 256; }
 struct SwinBlockBufs {
   float* x_in; void* xt_in;   // block input (f32 stream + dtype copy)
   void *qkv, *ctx, *po; float *lse, *mean1, *rstd1; float* h1; void* h1t;
   void *z, *a, *fo; float *mean2, *rstd2; float* h2; void* h2t;
   float *bias, *table, *hidden;
   float* btab;  // windows of more than 64 tokens: 16*sigmoid(table) [(2w-1)^2, H], looked up per score (no dense bias)
+  float* bimg;  // frozen tower, one-tile windows: bias + shift mask + key padding in the score MFMA's lane order (klab_swin_bias_image)
   int R, w, shift, H, C; long M;
 };
 struct SwinStageBufs { std::vector<SwinBlockBufs> blk; void *mg, *mo; float *mmean, *mrstd; float* xm; void* xmt; };
@@ -588,6 +591,7 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
       const bool big = n > 64 || (R % w) != 0;  // tiled / streaming attention kernels with the bias as a table (attn_swin_large.hip)
       q.bias = big ? nullptr : (float*)b.take((size_t)H * n * n * 4);
       q.btab = big ? (float*)b.take((size_t)ntab * H * 4) : nullptr;
+      q.bimg = (!big && !c.train_swin && swin_attn_on_image((int)C)) ? (float*)b.take(klab_swin_bias_image_bytes(w, q.shift, H)) : nullptr;
       q.table = (float*)b.take((size_t)ntab * H * 4);
       q.hidden = (float*)b.take((size_t)ntab * 512 * 4);
     }
@@ -1155,11 +1159,15 @@ int swin_forward(const Ctx& c, const float* pixels, float p_in, bool refresh_bia
         else
           RC(klab_swin_cpb_bias(e->swin_coords[st], e->swin_index[st], W[ix.c0w], W[ix.c0b], W[ix.c2w], q.table, q.hidden, q.bias,
                                 e->swin_ntab[st], n, q.H, 512, c.ws()));
+        if (q.bimg) RC(klab_swin_bias_image(q.bias, q.bimg, q.R, q.w, q.shift, q.H, c.ws()));
       }
       const float* qkvb = ix.qb >= 0 ? e->farena + bias_off : nullptr;
       bias_off += 3 * C;
       int qrc = KLAB_ERR_UNSUPPORTED;
-      if (!e->cfg.train_swin && q.bias)  // frozen tower, narrow stage, one-tile window: q|k|v never leave the chip
+      if (q.bimg)  // frozen tower, one-tile window: q|k|v never leave the chip; bias, mask and padding come as one pre-arranged image
+        qrc = klab_swin_qkv_attn_fused_img(xt, woff(c, P[ix.qw].warena_off), qkvb, q.ctx, q.bimg, W[ix.ls], c.dt, B, q.R, q.w, q.shift, q.H, C,
+                                           c.ws());
+      else if (!e->cfg.train_swin && q.bias)
         qrc = klab_swin_qkv_attn_fused(xt, woff(c, P[ix.qw].warena_off), qkvb, q.ctx, q.bias, W[ix.ls], c.dt, B, q.R, q.w, q.shift, q.H, C,
                                        c.ws());
       if (qrc != 0 && qrc != KLAB_ERR_UNSUPPORTED) return qrc;

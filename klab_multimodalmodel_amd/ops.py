@@ -152,6 +152,28 @@ def swin_qkv_attn_fused(x, wqkv, bqkv, ctx, bias, logit_scale, *, B, R, w, shift
                                          L.dtype_code(x.dtype), B, R, w, shift, H, C, L.stream_ptr()), "klab_swin_qkv_attn_fused")
 
 
+def swin_bias_image(bias, *, R, w, shift):
+    """Dense bias [H, n, n] (swin_cpb_bias) -> the image [classes, H, 4, 64, 16] swin_qkv_attn_fused_img reads: bias + shift mask (-200) +
+    key padding (-inf) in the score MFMA's lane order; classes = 4 with a shift (last window row x last window column), else 1."""
+    import torch
+    lib = L.load()
+    H = bias.shape[0]
+    nbytes = lib.klab_swin_bias_image_bytes(w, shift, H)
+    if nbytes == 0:
+        raise NotImplementedError("klab: unsupported shape/alignment in klab_swin_bias_image_bytes")
+    image = torch.empty(nbytes // (H * 4 * 64 * 16 * 4), H, 4, 64, 16, device=bias.device, dtype=torch.float32)
+    L.check(lib.klab_swin_bias_image(bias.data_ptr(), image.data_ptr(), R, w, shift, H, L.stream_ptr()), "klab_swin_bias_image")
+    return image
+
+
+def swin_qkv_attn_fused_img(x, wqkv, bqkv, ctx, image, logit_scale, *, B, R, w, shift, H, C):
+    """swin_qkv_attn_fused on the pre-arranged image of swin_bias_image(bias, R=R, w=w, shift=shift): the same ctx, bit for bit."""
+    lib = L.load()
+    L.check(lib.klab_swin_qkv_attn_fused_img(x.data_ptr(), wqkv.data_ptr(), L.ptr(bqkv), ctx.data_ptr(), image.data_ptr(),
+                                             logit_scale.data_ptr(), L.dtype_code(x.dtype), B, R, w, shift, H, C, L.stream_ptr()),
+            "klab_swin_qkv_attn_fused_img")
+
+
 def swin_proj_ln_fused(x, shortcut, w, b, gamma, beta, out, outt=None, eps=1e-5):
     """out = shortcut + LN(x @ w.T + b)*gamma+beta (frozen Swin-V2 attention-output half, C in {64,128})."""
     lib = L.load()
