@@ -1046,13 +1046,17 @@ static int swin_args_ok(const klab_swin_attn_args* a) {
 }
 
 static bool swin_flash_ok(int dtype, int w, int H, int C);
+// the scratch layout (swin_bwd_ws) holds the streaming kernels' table-gradient partials only for these shapes; a bias table with
+// one-tile windows on an unpadded grid runs the tiled kernels
+static bool swin_flash_shape(const klab_swin_attn_args* a) { return a->w * a->w > 64 || (a->R % a->w) != 0; }
 static int swin_attn_flash(const klab_swin_attn_args* a, bool backward, hipStream_t s);
 
 extern "C" int klab_swin_attn_fwd(const klab_swin_attn_args* a, void* stream) {
   int rc = swin_args_ok(a);
   if (rc) return rc;
   if (swin_use_large(a)) {
-    if (a->bwd_ws && a->bias_table && !a->bias && a->lse && swin_flash_ok(a->dtype, a->w, a->H, a->C)) return swin_attn_flash(a, false, (hipStream_t)stream);
+    if (a->bwd_ws && a->bias_table && !a->bias && a->lse && swin_flash_shape(a) && swin_flash_ok(a->dtype, a->w, a->H, a->C))
+      return swin_attn_flash(a, false, (hipStream_t)stream);
     return swin_attn_large_dispatch(a, false, (hipStream_t)stream);
   }
   SwinAttnP p{a->qkv, a->ctx, a->bias, a->logit_scale, a->lse, a->B, a->R, a->w, a->shift, a->H, a->C, nullptr, nullptr, nullptr, nullptr};
@@ -1160,7 +1164,8 @@ extern "C" int klab_swin_attn_bwd(const klab_swin_attn_args* a, void* stream) {
   if (rc) return rc;
   if (!a->dctx || !a->dqkv || !a->lse) return KLAB_ERR_BADARG;
   if (swin_use_large(a)) {
-    if (a->bwd_ws && a->bias_table && !a->bias && swin_flash_ok(a->dtype, a->w, a->H, a->C)) return swin_attn_flash(a, true, (hipStream_t)stream);
+    if (a->bwd_ws && a->bias_table && !a->bias && swin_flash_shape(a) && swin_flash_ok(a->dtype, a->w, a->H, a->C))
+      return swin_attn_flash(a, true, (hipStream_t)stream);
     return swin_attn_large_dispatch(a, true, (hipStream_t)stream);
   }
   SwinAttnP p{a->qkv, a->ctx, a->bias, a->logit_scale, a->lse, a->B, a->R, a->w, a->shift, a->H, a->C,

@@ -372,7 +372,8 @@ def swin_attn_fwd(qkv, ctx, bias, logit_scale, lse=None, *, B, R, w, shift, H, C
 
 def swin_attn_bwd(qkv, ctx, bias, logit_scale, lse, dctx, dqkv, dbias=None, dlogit_scale=None, *, B, R, w, shift, H, C, mfma=True,
                   bias_table=None, dbias_table=None, v_bias=None, dv_bias=None):
-    """mfma=True hands the kernel its scratch (when the shape is inside the matrix-core envelope); False forces the VALU form."""
+    """mfma=True hands the kernel its scratch (when the shape is inside the matrix-core envelope); False forces the VALU form.
+    dqkv is overwritten; dbias, dbias_table, dlogit_scale and dv_bias are ACCUMULATED into (the caller clears them)."""
     import torch
     lib = L.load()
     a = _swin_args(qkv, ctx, bias, logit_scale, lse, B, R, w, shift, H, C, bias_table, v_bias, dv_bias)

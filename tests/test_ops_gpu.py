@@ -926,11 +926,13 @@ def test_swin_mlp_fused_matches_torch(ops, M, Cc):
     h = F.gelu(x.float() @ w1.float().t() + b1).to(torch.bfloat16).float()
     y = h @ w2.float().t() + b2
     ref = sc + F.layer_norm(y, (Cc,), gm, bt, 1e-5)
-    out = torch.empty(M, Cc, device="cuda")
-    outt = torch.empty(M, Cc, device="cuda", dtype=torch.bfloat16)
+    gout = torch.full((M + 8, Cc), 7.0, device="cuda")  # 8 guard rows: nothing past row M may be written (ragged M: 300, 77)
+    goutt = torch.full((M + 8, Cc), 7.0, device="cuda", dtype=torch.bfloat16)
+    out, outt = gout[:M], goutt[:M]
     ops.swin_mlp_fused(dev(x), dev(sc), dev(w1), dev(b1), dev(w2), dev(b2), dev(gm), dev(bt), out, outt, eps=1e-5)
     assert rel_l2(out.cpu(), ref) < 4e-3
     assert rel_l2(outt.float().cpu(), ref) < 8e-3
+    assert bool((gout[M:] == 7.0).all()) and bool((goutt[M:] == 7.0).all())
     if Cc == 64:
         with pytest.raises(NotImplementedError):
             bad = torch.zeros(8, 256, device="cuda", dtype=torch.bfloat16)
@@ -951,11 +953,13 @@ def test_swin_proj_ln_fused_matches_torch(ops, M, Cc):
     b = torch.randn(Cc, generator=g) * 0.1
     gm, bt = torch.rand(Cc, generator=g) + 0.5, torch.randn(Cc, generator=g) * 0.1
     ref = sc + F.layer_norm(x.float() @ w.float().t() + b, (Cc,), gm, bt, 1e-5)
-    out = torch.empty(M, Cc, device="cuda")
-    outt = torch.empty(M, Cc, device="cuda", dtype=torch.bfloat16)
+    gout = torch.full((M + 8, Cc), 7.0, device="cuda")  # 8 guard rows: nothing past row M may be written
+    goutt = torch.full((M + 8, Cc), 7.0, device="cuda", dtype=torch.bfloat16)
+    out, outt = gout[:M], goutt[:M]
     ops.swin_proj_ln_fused(dev(x), dev(sc), dev(w), dev(b), dev(gm), dev(bt), out, outt, eps=1e-5)
     assert rel_l2(out.cpu(), ref) < 1e-3
     assert rel_l2(outt.float().cpu(), ref) < 6e-3
+    assert bool((gout[M:] == 7.0).all()) and bool((goutt[M:] == 7.0).all())
 
 
 @pytest.mark.gpu
@@ -998,9 +1002,12 @@ def test_swin_patch_embed_fused_matches_torch(ops, B, HW, Cc):
     y = conv.flatten(2).transpose(1, 2).reshape(-1, Cc).to(torch.bfloat16).float()
     ref = F.layer_norm(y, (Cc,), gamma, beta, 1e-5)
     R = HW // 4
-    out = torch.zeros(B * R * R, Cc, device="cuda")
-    outt = torch.zeros(B * R * R, Cc, device="cuda", dtype=torch.bfloat16)
+    M = B * R * R
+    gout = torch.full((M + 8, Cc), 7.0, device="cuda")  # 8 guard rows: nothing past row M may be written
+    goutt = torch.full((M + 8, Cc), 7.0, device="cuda", dtype=torch.bfloat16)
+    out, outt = gout[:M], goutt[:M]
     ops.swin_patch_embed_fused(dev(pix), dev(wp), dev(bias), dev(gamma), dev(beta), out, outt)
+    assert bool((gout[M:] == 7.0).all()) and bool((goutt[M:] == 7.0).all())
     assert rel_l2(out.cpu(), ref) < 4e-3, rel_l2(out.cpu(), ref)  # (a bf16 rounding flip of the conv output moves a normalised value by ~0.4 %)
     assert rel_l2(outt.float().cpu(), ref) < 6e-3
     with pytest.raises(NotImplementedError):
