@@ -582,6 +582,31 @@ int klab_sample_rows(const klab_sample_args* a, void* stream);
 int klab_gen_finalize(const float* logprob, long ld, const long long* seq, long ld_seq, int B, int n, int length, int eos_id,
                       float length_penalty, int n_out, float* score, int* len, int* order, void* stream);
 
+/* ---- forced decoding (csrc/force.hip) -----------------------------------------------------------------------------------------
+ * klab_force_rows: position pos of every row r < rows is TOLD, not chosen: the token is forced[r*ld_forced + pos] (int64, device;
+ * ld_forced > pos), with the bookkeeping of the two choosing kernels: a row with done[r] != 0 on entry gets pad_id; with
+ * finish_on_eos != 0 a forced eos_id sets done[r] = 1 (scoring given captions), with 0 it does not (a decoder prompt: HF does
+ * not finish a row on an EOS inside its prompt); tokens [rows], seq[r*ld_seq + pos] (and seq[r*ld_seq] = start_id when pos == 1)
+ * and stop_word as in klab_sample_rows (done, tokens, seq, stop_word optional).
+ * logprob != NULL: logprob[r*ld_logprob + pos] = log_softmax(x)[token] = (x[token] - M) - logf(sum exp(x - M)) over the raw fp32
+ * logits row (r / row_div) (element stride ld, dtype bf16 or f32; any V >= 1: no register row, so no 32768 cap), 0 for a row with
+ * done[r] != 0 on entry, -inf for a token outside [0, V) (nothing is read for it).  logprob == NULL: logits is not read at all
+ * (may be NULL).                                                                                                            */
+typedef struct {
+  int dtype;
+  const void* logits; long ld; int row_div;
+  int rows, V;
+  const long long* forced; long ld_forced;
+  int finish_on_eos;
+  int* done; int eos_id, pad_id, start_id;
+  long long* tokens;
+  long long* seq; long ld_seq; int pos;
+  int* stop_word;
+  float* logprob; long ld_logprob;
+} klab_force_args;
+int klab_force_rows(const klab_force_args* a, void* stream);
+int klab_sizeof_force_args(void);
+
 /* ---- logits processors (HF's RepetitionPenalty, NoRepeatNGram, NoBadWords, MinLength, MinNewTokensLength, in that order;
  * csrc/logits_proc.hip) --------------------------------------------------------------------------------------------------
  * klab_logits_process_rows: one processed fp32 row per row r < rows from logits row (r / row_div) (element stride ld),
@@ -662,6 +687,7 @@ typedef struct {
 #define KLAB_GEN_PICK 0
 #define KLAB_GEN_SAMPLE 1
 #define KLAB_GEN_BEAM 2
+#define KLAB_GEN_FORCE 3
 typedef struct {
   int mode, n, max_length, eos_id, pad_id;
   float temperature; int top_k; float top_p; unsigned long long seed; /* sampling only */
@@ -669,6 +695,18 @@ typedef struct {
   const klab_logits_proc_cfg* procs;
   int want_logprobs;
 } klab_gen_cfg;
+/* The forced-token table of the NEXT klab_engine_gen_begin (one-shot, as klab_engine_set_loss_out: gen_begin takes it whether it
+ * succeeds or fails, so a session begun without this call never sees a table): tokens_dev int64 [B*n, ld] on the device, owned by
+ * the caller and alive while the session runs; row r's token of position p is tokens_dev[r*ld + p], 1 <= p <= n_forced < ld
+ * (column 0, the start token's, is not read).  NULL with n_forced 0 disarms.  stream is unused today: the session's own launches
+ * read the table on the streams they are given.
+ * mode KLAB_GEN_FORCE (scoring given sequences): needs the table with n_forced >= max_length - 1, want_logprobs and no
+ *   processors; any vocabulary.  Every position is one klab_force_rows with finish_on_eos = 1 and the log-probability of the
+ *   forced token under the raw logits; workspace, gen_result and gen_scores as a pick session with want_logprobs.
+ * modes KLAB_GEN_PICK / KLAB_GEN_SAMPLE with a table (a decoder prompt, n_forced <= max_length - 1, without want_logprobs):
+ *   positions 1 .. n_forced are klab_force_rows with finish_on_eos = 0 and no logits read, the later ones run as without a
+ *   table; the processors see the prompt as history.  KLAB_GEN_BEAM with a table: KLAB_ERR_BADARG.                          */
+int klab_engine_gen_set_forced(klab_engine* e, const long long* tokens_dev, long ld, int n_forced, void* stream);
 size_t klab_engine_gen_workspace_bytes(klab_engine* e, const klab_gen_cfg* cfg);
 int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, void* ws, void* stream);
 int klab_engine_gen_step(klab_engine* e, int t, void* ws, void* stream);

@@ -78,12 +78,20 @@ class LogitsProcArgs(C.Structure):  # klab_logits_proc_args
                 ("logprob", vp), ("ld_logprob", i64)]
 
 
+class ForceArgs(C.Structure):  # klab_force_args
+    _fields_ = [("dtype", i32), ("logits", vp), ("ld", i64), ("row_div", i32), ("rows", i32), ("V", i32),
+                ("forced", vp), ("ld_forced", i64), ("finish_on_eos", i32),
+                ("done", vp), ("eos_id", i32), ("pad_id", i32), ("start_id", i32),
+                ("tokens", vp), ("seq", vp), ("ld_seq", i64), ("pos", i32), ("stop_word", vp),
+                ("logprob", vp), ("ld_logprob", i64)]
+
+
 class LogitsProcCfg(C.Structure):  # klab_logits_proc_cfg
     _fields_ = [("repetition_penalty", f32), ("no_repeat_ngram_size", i32), ("min_length", i32), ("min_new_tokens", i32),
                 ("n_bad", i32), ("bad_off", C.POINTER(i32)), ("bad_tok", C.POINTER(i32))]
 
 
-GEN_PICK, GEN_SAMPLE, GEN_BEAM = 0, 1, 2
+GEN_PICK, GEN_SAMPLE, GEN_BEAM, GEN_FORCE = 0, 1, 2, 3
 
 
 class GenCfg(C.Structure):  # klab_gen_cfg
@@ -131,6 +139,8 @@ SIGNATURES = {
     "klab_sizeof_sample_args": [],
     "klab_sizeof_logits_proc_args": [],
     "klab_sizeof_gen_cfg": [],
+    "klab_force_rows": [C.POINTER(ForceArgs), vp],
+    "klab_sizeof_force_args": [],
     "klab_beam_topk_scores": [vp, i64, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "klab_dbias_reduce": [vp, i32, vp, i32, i32, i32, i32, vp],
     "klab_swin_mlp_fused": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],

@@ -94,9 +94,17 @@ struct ProcSet {
   std::vector<int> table;
 };
 // a decoding session: its settings (cfg.procs cleared; the processors live in lp) and the last position it chose (0: none begun)
+// the forced-token table of a session (klab_engine_gen_set_forced): int64 [rows, ld] on the device, the caller's; row r's token of
+// position p is tok[r*ld + p] for 1 <= p <= n (n 0: no table)
+struct ForcedTable {
+  const long long* tok = nullptr;
+  long ld = 0;
+  int n = 0;
+};
 struct GenRun {
   klab_gen_cfg cfg{};
   ProcSet lp;
+  ForcedTable forced;
   int cur = 0;
 };
 
@@ -150,6 +158,7 @@ struct klab_engine {
   T5StackBufs lang, enc, dec;
   // the decoding session (klab_engine_gen_*) begun last on this binding
   GenRun gen;
+  ForcedTable forced_armed;  // one-shot: taken (and cleared) by the next klab_engine_gen_begin
   // lang scratch (no grad => reused across layers)
   void* kv_all = nullptr; void* dkv_all = nullptr;
   void* logits = nullptr; float *loss_row = nullptr, *inv_n = nullptr, *loss = nullptr;
@@ -1445,6 +1454,7 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
   e->seg1_zeroed = e->dbias_zeroed[0] = e->dbias_zeroed[1] = e->denc_in_dxn = false;  // (hand-offs between backward segments of the OLD binding)
   e->bias_ready[0] = e->bias_ready[1] = e->bias_ready[2] = e->dec_embed_ready = e->inv_n_ready = e->kv_wgrad_done = false;
   e->loss_out = nullptr;
+  e->forced_armed = ForcedTable();
   if (e->pe_kp != e->pe_k0)  // the padding columns of the patch-embedding weight rows: written here, never again
     RC((int)hipMemsetAsync((char*)e->warena + (size_t)e->P[0][e->si.pew].warena_off * e->es, 0,
                            (size_t)e->cfg.swin.embed_dim * e->pe_kp * e->es, hs));
@@ -2007,6 +2017,7 @@ bool gen_shape_ok(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp
     case KLAB_GEN_SAMPLE:
       return V <= 32768 && g.temperature > 0.f && g.top_k >= 0 && g.top_p >= 0.f && g.top_p <= 1.f;
     case KLAB_GEN_PICK: return V <= 32768;
+    case KLAB_GEN_FORCE: return g.want_logprobs && !lp.on;  // (klab_force_rows keeps no register row: any vocabulary)
     default: return false;
   }
 }
@@ -2092,7 +2103,9 @@ klab_beam_update_args beam_args(const klab_engine* e, const GenWs& w, int c) {
 // position pos (beam search: cur_len) of every row from logits rows r / row_div, behind the processors when the session has them:
 // beam search's top-2k of each sample and HF's update (HF hands the processors log_softmax(logits); each beam's history is its
 // running sequence, parity pos + 1), or one klab_sample_rows (HF's `_sample`: processors, then the warpers), or greedy's pick of
-// the processed arg-max
+// the processed arg-max.  A position the session's forced table covers (every position of a force session: scoring, EOS finishes
+// a row, the token's log-probability is kept; positions 1 .. n of a pick or sample session: the decoder prompt, no logits read)
+// is one klab_force_rows instead.
 int gen_pos(klab_engine* e, const Ctx& c, const GenWs& w, const void* logits, long ld, int row_div, int pos) {
   const GenRun& g = e->gen;
   const int B = e->B, n = g.cfg.n, V = e->cfg.main.vocab, start = e->cfg.main.start_id;
@@ -2109,6 +2122,18 @@ int gen_pos(klab_engine* e, const Ctx& c, const GenWs& w, const void* logits, lo
     }
     klab_beam_update_args a = beam_args(e, w, pos);
     return klab_beam_update(&a, pos, c.ws());
+  }
+  if (g.cfg.mode == KLAB_GEN_FORCE || pos <= g.forced.n) {
+    const bool score = g.cfg.mode == KLAB_GEN_FORCE;
+    klab_force_args a;
+    memset(&a, 0, sizeof(a));
+    a.dtype = c.dt; a.logits = logits; a.ld = ld; a.row_div = row_div;
+    a.rows = B * n; a.V = V;
+    a.forced = g.forced.tok; a.ld_forced = g.forced.ld; a.finish_on_eos = score ? 1 : 0;
+    a.done = w.done; a.eos_id = g.cfg.eos_id; a.pad_id = g.cfg.pad_id; a.start_id = start;
+    a.tokens = w.prev; a.seq = w.seq; a.ld_seq = g.cfg.max_length; a.pos = pos; a.stop_word = w.stop + pos;
+    if (score) { a.logprob = w.logprob; a.ld_logprob = g.cfg.max_length; }
+    return klab_force_rows(&a, c.ws());
   }
   int dt = c.dt;
   if (g.lp.on || g.cfg.mode == KLAB_GEN_PICK) {
@@ -2144,14 +2169,34 @@ extern "C" size_t klab_engine_gen_workspace_bytes(klab_engine* e, const klab_gen
 }
 
 // Precondition: klab_engine_forward in evaluation mode on this binding (the prefill; its logits row b*Lt is position 0 of sample b)
+extern "C" int klab_engine_gen_set_forced(klab_engine* e, const long long* tokens_dev, long ld, int n_forced, void* stream) {
+  (void)stream;  // the table is read by the session's own launches, on the stream they are given
+  if (!e) return KLAB_ERR_BADARG;
+  e->forced_armed = ForcedTable();
+  if (!tokens_dev && n_forced == 0) return 0;  // disarm
+  if (!tokens_dev || n_forced < 1 || ld <= n_forced) return KLAB_ERR_BADARG;
+  e->forced_armed.tok = tokens_dev; e->forced_armed.ld = ld; e->forced_armed.n = n_forced;
+  return 0;
+}
+
 extern "C" int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, void* ws, void* stream) {
-  if (!e || !cfg || !ws) return KLAB_ERR_BADARG;
+  if (!e) return KLAB_ERR_BADARG;
+  const ForcedTable forced = e->forced_armed;  // consumed whatever happens below
+  e->forced_armed = ForcedTable();
+  if (!cfg || !ws) return KLAB_ERR_BADARG;
   ProcSet lp;
   RC(make_procs(e, cfg->procs, lp));
   if (!gen_shape_ok(e, *cfg, lp)) return KLAB_ERR_BADARG;
+  // a table: never under beam search; a force session needs every position 1 .. max_length - 1 from it; a prompt (pick, sample)
+  // leaves at least nothing beyond the sequence, and keeps no log-probabilities (klab_gen_finalize would take an EOS inside the
+  // prompt for the row's end)
+  if (cfg->mode == KLAB_GEN_FORCE ? forced.n < cfg->max_length - 1
+                                  : forced.n > 0 && (cfg->mode == KLAB_GEN_BEAM || forced.n > cfg->max_length - 1 || cfg->want_logprobs))
+    return KLAB_ERR_BADARG;
   GenRun& g = e->gen;
   g.cfg = *cfg; g.cfg.procs = nullptr;
   g.lp = std::move(lp);
+  g.forced = forced;
   g.cur = 0;
   Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
   const klab_t5_cfg& mc = e->cfg.main;

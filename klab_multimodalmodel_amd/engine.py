@@ -118,6 +118,7 @@ ENGINE_SIGS = {
                           C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                           C.POINTER(C.c_void_p), C.c_void_p], C.c_int),
     "klab_engine_forward": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p], C.c_int),
+    "klab_engine_gen_set_forced": ([C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p], C.c_int),
     "klab_engine_gen_workspace_bytes": ([C.c_void_p, C.POINTER(L.GenCfg)], C.c_size_t),
     "klab_engine_gen_begin": ([C.c_void_p, C.POINTER(L.GenCfg), C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_gen_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
@@ -288,6 +289,7 @@ class Engine:
         self._keep = None
         self.shape = None
         self._gen = None  # the klab_gen_cfg of the decoding session begun last
+        self._forced = self._forced_armed = None  # forced-token tables: of that session / armed for the next gen_begin
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -379,7 +381,7 @@ class Engine:
 
     # ---- decoding sessions (HF `_beam_search`, `_sample`, greedy decoding); the workspace is the caller's, the binding's is
     # untouched ----------------------------------------------------------------------------------------------------------------
-    GEN_MODES = {"pick": L.GEN_PICK, "sample": L.GEN_SAMPLE, "beam": L.GEN_BEAM}
+    GEN_MODES = {"pick": L.GEN_PICK, "sample": L.GEN_SAMPLE, "beam": L.GEN_BEAM, "force": L.GEN_FORCE}
     EARLY_STOPPING = {False: 0, True: 1, "never": 2}
 
     @classmethod
@@ -408,8 +410,20 @@ class Engine:
         """bytes of the session's workspace; 0 = settings this binding does not support"""
         return int(self._lib.klab_engine_gen_workspace_bytes(self._h, C.byref(cfg)))
 
+    def gen_set_forced(self, tokens, n_forced):
+        """arms the forced-token table of the NEXT gen_begin (one-shot; gen_begin takes it whether it succeeds or not): tokens int64
+        [B*n, ld] on the device, contiguous, row r's token of position p in tokens[r, p] for 1 <= p <= n_forced < ld.  A "force"
+        session takes every position from it (scoring); a pick or sample session its first n_forced (a decoder prompt).  The
+        engine keeps the tensor alive until the next gen_begin after that one."""
+        if tokens.dtype != torch.int64 or tokens.dim() != 2 or not tokens.is_contiguous():
+            raise ValueError("the forced-token table must be a contiguous int64 [rows, ld] tensor")
+        L.check(self._lib.klab_engine_gen_set_forced(self._h, tokens.data_ptr(), tokens.shape[1], int(n_forced), L.stream_ptr()),
+                "klab_engine_gen_set_forced")
+        self._forced_armed = tokens
+
     def gen_begin(self, cfg, ws):
         """after an evaluation-mode forward (the prefill): the session's state, and position 1 from the prefill's position-0 logits"""
+        self._forced, self._forced_armed = self._forced_armed, None  # (the session's table stays referenced)
         L.check(self._lib.klab_engine_gen_begin(self._h, C.byref(cfg), ws.data_ptr(), L.stream_ptr()), "klab_engine_gen_begin")
         self._gen = cfg
 

@@ -7,13 +7,14 @@ MAX_BAD_WORD_TOKENS = 1024  # the device table's cap (csrc/logits_proc.hip)
 
 
 def logits_processor_settings(repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_length=0, min_new_tokens=None,
-                              *, eos_token_id, vocab_size):
-    """HF's checks, in HF's order and with HF's exception types and messages.  The decoder prompt is the one start token, so
-    HF's prompt length is 1: `min_new_tokens` (when given) replaces `min_length` by min_new_tokens + 1, whatever min_length
-    was.  Returns None when no processor would change a score, else the settings the engine runs:
+                              *, eos_token_id, vocab_size, prompt_length=1):
+    """HF's checks, in HF's order and with HF's exception types and messages.  prompt_length is HF's decoder prompt length, the
+    start token counted: 1 without generate(decoder_input_ids=...).  `min_new_tokens` (when given) replaces `min_length` by
+    min_new_tokens + prompt_length, whatever min_length was, and the kernel's own min_new_tokens test, which counts generated
+    tokens from position 1 (cur_len - 1 < min_new_tokens), is given min_new_tokens + prompt_length - 1.  Returns None when no processor would change a score, else the settings the engine runs:
     dict(repetition_penalty, no_repeat_ngram_size, bad_words_ids (entries equal to [eos] dropped), min_length, min_new_tokens)."""
     if min_new_tokens is not None:
-        min_length = min_new_tokens + 1
+        min_length = min_new_tokens + prompt_length
     out = dict(repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=[], min_length=0, min_new_tokens=0)
     # RepetitionPenaltyLogitsProcessor
     if repetition_penalty is not None and repetition_penalty != 1.0:
@@ -41,11 +42,11 @@ def logits_processor_settings(repetition_penalty=1.0, no_repeat_ngram_size=0, ba
         if not isinstance(min_length, int) or min_length < 0:
             raise ValueError(f"`min_length` has to be a non-negative integer, but is {min_length}")
         out["min_length"] = int(min_length)
-    # MinNewTokensLengthLogitsProcessor (prompt_length_to_skip = 1)
+    # MinNewTokensLengthLogitsProcessor (prompt_length_to_skip = prompt_length)
     if min_new_tokens is not None and min_new_tokens > 0:
         if not isinstance(min_new_tokens, int) or min_new_tokens < 0:
             raise ValueError(f"`min_new_tokens` has to be a positive integer, but is {min_new_tokens}")
-        out["min_new_tokens"] = int(min_new_tokens)
+        out["min_new_tokens"] = int(min_new_tokens) + prompt_length - 1
     # SequenceBiasLogitsProcessor._prepare_bias_variables (HF's first call)
     if bias is not None:
         invalid = [t for ids in bias for t in ids if t >= vocab_size]

@@ -377,7 +377,7 @@ class MyModel(nn.Module):
     def generate(self, pixels, src, max_length=20, kv_cache=True, num_beams=1, length_penalty=1.0, early_stopping=False,
                  num_return_sequences=1, return_scores=False, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_length=0, min_new_tokens=None,
-                 return_logprobs=False, best_of=None):
+                 return_logprobs=False, best_of=None, decoder_input_ids=None):
         """greedy decoding with HF's default generation settings (ref/models/model.py:28: max_length 20, no sampling).
         Every kv_cache=True call is one decoding session on the device (_generate_on_device; SURVEY §8 row f-3, HF/t5:308-332):
         prefill = one evaluation-mode forward (Swin, both encoders, the cross K/V of all layers, decoder position 0), then every
@@ -402,7 +402,22 @@ class MyModel(nn.Module):
         (generated tokens through the first EOS) and info["scores"] [rows] = sum of the row's log-probabilities /
         lengths ** length_penalty, beam search's convention.
         best_of=N (sampling only, num_return_sequences <= N <= 64): draws N rows per image and returns the num_return_sequences
-        best by that score, best first, chosen and gathered on the device (klab_gen_finalize)."""
+        best by that score, best first, chosen and gathered on the device (klab_gen_finalize).
+        decoder_input_ids (int64 [B, P]; greedy and sampling on the K/V cache, with or without processors): HF's decoder prompt.
+        The start token is prepended unless column 0 already is the start token in some row (HF's
+        `_prepare_decoder_input_ids_for_generation`); each image's prompt is shared by its num_return_sequences rows; the session
+        takes the prompt positions from a table (klab_force_rows, no logits read) and chooses the rest as without one.  As in HF
+        max_length counts the prompt, the processors see it as history (min_new_tokens counts from its end) and an EOS inside it
+        does not finish the row.  Not with num_beams > 1, kv_cache=False, return_logprobs or best_of."""
+        prompt = None
+        if decoder_input_ids is not None:
+            for bad, why in ((num_beams > 1, "num_beams > 1 (beam search takes no forced tokens)"),
+                             (not kv_cache, "kv_cache=False (the prompt is forced inside the K/V-cache session)"),
+                             (return_logprobs, "return_logprobs (an EOS inside the prompt would end the row's score)"),
+                             (best_of is not None, "best_of (an EOS inside the prompt would end the row's score)")):
+                if bad:
+                    raise ValueError(f"decoder_input_ids is not supported with {why}")
+            prompt = self._decoder_prompt(decoder_input_ids, src.shape[0], max_length)
         if return_logprobs or best_of is not None:
             what = "return_logprobs" if return_logprobs else "best_of"
             if num_beams > 1:
@@ -418,7 +433,8 @@ class MyModel(nn.Module):
             if best_of > 64:
                 raise ValueError(f"`best_of` ({best_of}) has to be at most 64")
         procs = logits_processor_settings(repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens,
-                                          eos_token_id=self.main_cfg.eos_token_id, vocab_size=self.main_cfg.vocab_size)
+                                          eos_token_id=self.main_cfg.eos_token_id, vocab_size=self.main_cfg.vocab_size,
+                                          prompt_length=1 if prompt is None else prompt.shape[1])
         if do_sample:
             if num_beams > 1:
                 raise NotImplementedError("beam sampling (do_sample=True with num_beams > 1) is not supported")
@@ -436,7 +452,8 @@ class MyModel(nn.Module):
             if num_return_sequences < 1:
                 raise ValueError(f"`num_return_sequences` has to be a positive integer, but is {num_return_sequences}")
             return self._generate_sample(pixels, src, max_length, num_return_sequences, float(temperature), int(top_k), float(top_p),
-                                         procs, return_logprobs=return_logprobs, best_of=best_of, length_penalty=length_penalty)
+                                         procs, return_logprobs=return_logprobs, best_of=best_of, length_penalty=length_penalty,
+                                         prompt=prompt)
         if num_return_sequences > num_beams:
             raise ValueError(f"`num_return_sequences` ({num_return_sequences}) has to be smaller or equal to `num_beams` ({num_beams}).")
         if num_beams > 1:
@@ -448,7 +465,7 @@ class MyModel(nn.Module):
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence scores)")
         if kv_cache:
             return self._generate_sample(pixels, src, max_length, 1, 1.0, 0, 1.0, procs, pick=True, return_logprobs=return_logprobs,
-                                         length_penalty=length_penalty)
+                                         length_penalty=length_penalty, prompt=prompt)
         if procs is not None:
             raise ValueError("logits processors run on the K/V cache only: repetition_penalty, no_repeat_ngram_size, bad_words_ids, "
                              "min_length and min_new_tokens need kv_cache=True")
@@ -475,8 +492,82 @@ class MyModel(nn.Module):
         start = torch.full((B, 1), cfg.decoder_start_token_id, dtype=torch.int64, device=src.device)
         return torch.cat([start, tgt], dim=1)
 
+    def _decoder_prompt(self, decoder_input_ids, B, max_length):
+        """HF's decoder prompt [B, Lp] on the host, start token first, from generate's decoder_input_ids (checked before anything
+        touches the device); its ids must be the model's"""
+        cfg = self.main_cfg
+        ids = torch.as_tensor(decoder_input_ids)
+        if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 1 or ids.dtype != torch.int64:
+            raise ValueError(f"decoder_input_ids has to be an int64 tensor [{B}, P] with P >= 1, got {ids.dtype} {tuple(ids.shape)}")
+        ids = ids.cpu()
+        if int(ids.min()) < 0 or int(ids.max()) >= cfg.vocab_size:
+            raise ValueError(f"decoder_input_ids holds ids outside [0, {cfg.vocab_size})")
+        first = ids[:, 0] == cfg.decoder_start_token_id
+        if not bool(first.any()):  # HF prepends the start token unless some row already begins with it
+            ids = torch.cat([torch.full((B, 1), cfg.decoder_start_token_id, dtype=torch.int64), ids], 1)
+        elif not bool(first.all()):
+            raise ValueError("decoder_input_ids: column 0 is the start token in some rows only; every row of a session starts from "
+                             "the start token, so give it in all rows or in none")
+        if ids.shape[1] >= max_length:
+            raise ValueError(f"Input length of decoder_input_ids is {ids.shape[1]}, but `max_length` is set to {max_length}. This can "
+                             "lead to unexpected behavior. You should consider increasing `max_length` or, better yet, setting "
+                             "`max_new_tokens`.")
+        return ids
+
+    @torch.no_grad()
+    def score(self, pixels, src, candidates, length_penalty=1.0, top=None):
+        """How likely each of N given captions is for each image: candidates int64 [B, N, L] as labels are (no start token, each
+        row closed by EOS, whatever follows the first EOS ignored; a row without EOS counts all L tokens), 1 <= N <= 64, L >= 1.
+        One prefill at B rows, then ONE force session of B*N rows against the shared cross K/V (Swin and both encoders run once per
+        image, not once per candidate): every position's token comes from the candidates (klab_force_rows), which also writes
+        log_softmax(logits)[token]; the L - 1 decoder steps are enqueued without a host read, then one klab_gen_finalize.
+        Returns dict(token_logprobs [B, N, L] fp32, 0 after a row's EOS; lengths [B, N] int32, tokens through the first EOS;
+        scores [B, N] = sum / lengths ** length_penalty, the convention of generate's info["scores"] (length_penalty=0: the
+        sequence log-likelihood); order [B, top or N] int64, each image's candidate indices best first, ranked on the device)."""
+        cfg = self.main_cfg
+        cand = torch.as_tensor(candidates)
+        if cand.dim() != 3 or cand.dtype != torch.int64:
+            raise ValueError(f"candidates has to be an int64 tensor [B, N, L], got {cand.dtype} {tuple(cand.shape)}")
+        B, N, L = cand.shape
+        if B != src.shape[0]:
+            raise ValueError(f"candidates holds {B} images, the batch {src.shape[0]}")
+        if N < 1 or N > 64:
+            raise ValueError(f"candidates per image ({N}) has to be between 1 and 64")
+        if L < 1:
+            raise ValueError("candidates need at least one token")
+        if top is not None and (not isinstance(top, int) or top < 1 or top > N):
+            raise ValueError(f"`top` ({top}) has to be an integer between 1 and the number of candidates ({N})")
+        if int(cand.min()) < 0 or int(cand.max()) >= cfg.vocab_size:
+            raise ValueError(f"candidates holds ids outside [0, {cfg.vocab_size})")
+        dev = src.device
+        pixels = pixels.to(torch.float32).contiguous()
+        src = src.to(torch.int64).contiguous()
+        # the session's table: column p is position p (column 0, the start token's, is not read)
+        table = torch.cat([torch.full((B * N, 1), cfg.decoder_start_token_id, dtype=torch.int64, device=dev),
+                           cand.to(dev).reshape(B * N, L)], 1).contiguous()
+        tgt = torch.full((B, L), cfg.pad_token_id, dtype=torch.int64, device=dev)
+        was_training = self.transformer.training
+        self.transformer.eval()
+        try:
+            eng = self._engine_for(pixels, src, tgt)
+            eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
+            gen = eng.gen_cfg("force", N, L + 1, cfg.eos_token_id, cfg.pad_token_id, want_logprobs=True)
+            nbytes = eng.gen_workspace_bytes(gen)
+            if nbytes == 0:
+                raise ValueError(f"scoring: unsupported candidates per image {N} / length {L} for this model")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            eng.gen_set_forced(table, L)
+            eng.gen_begin(gen, ws)
+            for t in range(1, L):  # nothing is chosen: the host has nothing to wait for
+                eng.gen_step(t, ws)
+            lp, scores, lens, order = eng.gen_scores(ws, L + 1, N if top is None else top, length_penalty)
+        finally:
+            self.transformer.train(was_training)
+        order = order.long().view(B, -1) - torch.arange(B, device=dev).view(B, 1) * N
+        return dict(token_logprobs=lp[:, 1:].reshape(B, N, L), lengths=lens.view(B, N), scores=scores.view(B, N), order=order)
+
     def _generate_on_device(self, pixels, src, max_length, mode, n, procs=None, num_return_sequences=None, temperature=1.0, top_k=0,
-                            top_p=1.0, length_penalty=1.0, early_stopping=False, logprobs=False):
+                            top_p=1.0, length_penalty=1.0, early_stopping=False, logprobs=False, prompt=None):
         """One prefill at B rows (Swin, both encoders and the cross K/V run once per image, not per row), then a decoding session of
         B*n rows on the device (row b*n + j: beam / sample j of image b, HF's `_expand_inputs_for_generation`): every step is the
         decoder over B*n rows and the mode's choice of the next tokens (`klab_engine_gen_step`); the host reads one stop word per
@@ -488,7 +579,9 @@ class MyModel(nn.Module):
         procs: the logits processors' settings (logits_proc.logits_processor_settings), None = none.
         logprobs (sampling and pick): the session keeps every chosen token's log-probability and the second value returned is
         info = dict(token_logprobs, scores, lengths) (see generate); with num_return_sequences < n the rows returned are each
-        image's num_return_sequences best by score, best first, ranked and gathered on the device."""
+        image's num_return_sequences best by score, best first, ranked and gathered on the device.
+        prompt (sampling and pick): the decoder prompt [B, Lp] with its start token (_decoder_prompt); its Lp - 1 tokens after
+        the start token are forced at positions 1 .. Lp - 1 of each image's n rows."""
         if mode == "beam" and early_stopping not in (False, True, "never"):
             raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
         if max_length < 2:
@@ -513,6 +606,8 @@ class MyModel(nn.Module):
                         "pick": f"greedy decoding on the K/V cache: unsupported vocab_size={cfg.vocab_size}"}[mode]
                 raise ValueError(f"{what} / max_length={max_length} for this model")
             ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+            if prompt is not None and prompt.shape[1] > 1:
+                eng.gen_set_forced(prompt.to(src.device).repeat_interleave(n, 0).contiguous(), prompt.shape[1] - 1)
             eng.gen_begin(gen, ws)
             cur = 1
             while cur < max_length - 1 and eng.gen_going(ws, cur):
@@ -541,13 +636,14 @@ class MyModel(nn.Module):
         return (seq, scores) if return_scores else seq
 
     def _generate_sample(self, pixels, src, max_length, num_return_sequences, temperature, top_k, top_p, procs=None, pick=False,
-                         return_logprobs=False, best_of=None, length_penalty=1.0):
+                         return_logprobs=False, best_of=None, length_penalty=1.0, prompt=None):
         """HF's `_sample` as a decoding session (_generate_on_device); pick=True: greedy decoding, the processed arg-max.
         return_logprobs: (sequences, info); best_of: that many rows per image, the num_return_sequences best returned"""
         n = num_return_sequences if best_of is None else best_of
         seq, info = self._generate_on_device(pixels, src, max_length, "pick" if pick else "sample", n, procs,
                                              num_return_sequences=num_return_sequences, temperature=temperature, top_k=top_k, top_p=top_p,
-                                             length_penalty=length_penalty, logprobs=return_logprobs or best_of is not None)
+                                             length_penalty=length_penalty, logprobs=return_logprobs or best_of is not None,
+                                             prompt=prompt)
         return (seq, info) if return_logprobs else seq
 
     def _join_pending_update(self):
