@@ -20,7 +20,9 @@ template <typename T> __device__ __forceinline__ float tanh_for(float u) {
 }
 // gelu_new(x) = 0.5 x (1 + tanh(c0 (x + c1 x^3))) and its derivative
 template <typename T> __device__ __forceinline__ void gelu_new_both(float x, float& g, float& dg) {
-  const float x2 = x * x;
+  // x^2 is capped: beyond |x| = 1e4 the tanh is +-1 either way, and an infinite x^2 (|x| >= 1.85e19) made the derivative's
+  // polynomial infinite against a factor (1 - t^2) = 0: NaN for a finite input
+  const float x2 = fminf(x * x, 1e8f);
   const float t = tanh_for<T>(kC0 * x * fmaf(kC1, x2, 1.f));
   const float hp = 0.5f * (1.f + t);
   g = x * hp;

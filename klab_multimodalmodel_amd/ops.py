@@ -192,12 +192,12 @@ def swin_mlp_fused(x, shortcut, w1, b1, w2, b2, gamma, beta, out, outt=None, eps
                                     L.stream_ptr()), "klab_swin_mlp_fused")
 
 
-def rmsnorm_fwd_q8(x, w, y, rstd, y8, yscale, eps=1e-6):
-    """fp8 mode: y (bf16) = RMS-norm(x) * w and the same rows in e4m3 (y8 uint8 [rows, d]) with one scale per row"""
+def rmsnorm_fwd_q8(x, w, y, rstd, y8, yscale, eps=1e-6, drop_p=0.0, seed=None, tag=0):
+    """fp8 mode: y (bf16) = dropout(RMS-norm(x) * w) and the same rows in e4m3 (y8 uint8 [rows, d]) with one scale per row"""
     lib = L.load()
     rows, d = x.shape
-    L.check(lib.klab_rmsnorm_fwd_q8(x.data_ptr(), w.data_ptr(), y.data_ptr(), L.ptr(rstd), y8.data_ptr(), yscale.data_ptr(), rows, d, eps, 0.0,
-                                    None, 0, L.stream_ptr()), "klab_rmsnorm_fwd_q8")
+    L.check(lib.klab_rmsnorm_fwd_q8(x.data_ptr(), w.data_ptr(), y.data_ptr(), L.ptr(rstd), y8.data_ptr(), yscale.data_ptr(), rows, d, eps,
+                                    drop_p, _seed_ptr(seed), tag, L.stream_ptr()), "klab_rmsnorm_fwd_q8")
 
 
 def layernorm_fwd_q8(y, gamma, beta, shortcut, out, outt, mean, rstd, o8, oscale, eps=1e-5):
@@ -480,6 +480,13 @@ def colsum(dy, out):
 def convert(x, y, scale=1.0):
     lib = L.load()
     L.check(lib.klab_convert(x.data_ptr(), y.data_ptr(), L.dtype_code(y.dtype), x.numel(), scale, L.stream_ptr()), "klab_convert")
+
+
+def add_f32(y, x):
+    """y += x, both f32 with a length that is a multiple of 4"""
+    lib = L.load()
+    assert y.dtype == x.dtype == torch.float32 and y.numel() == x.numel()
+    L.check(lib.klab_add_f32(y.data_ptr(), x.data_ptr(), y.numel(), L.stream_ptr()), "klab_add_f32")
 
 
 # ---- descriptor-table kernels: `desc` is an int64 device tensor [n, fields] in the struct layout of the kernel's table ----------
