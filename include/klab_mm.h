@@ -509,6 +509,17 @@ int klab_adafactor_step(const void* desc_dev, int ndesc, long state_elems, long 
 int klab_t5_beam_decode_attn(int dtype, const void* q, long q_bstride, const void* k, const void* v, long kv_bstride, long ldk,
                              int kv_group, const int* kv_slot, long slot_ld, const float* bias_row, long bias_ld, void* ctx,
                              long ctx_bstride, int R, int H, int Lk, int dk, void* stream);
+/* the attention probabilities of the same query rows, averaged over the heads (csrc/attn_map.hip; HF's `cross_attentions` with
+ * output_attentions=True, head mean): map[r*map_bstride + j] = (1/H) * sum_h softmax_j(q_h . k_{h,j} + bias_row[h, j]), f32, for
+ * r < R, j < Lk <= map_bstride.  Row r's query is read at q + (r / q_div)*q_bstride (q_div n: the prefill's one row per sample),
+ * its keys as klab_t5_beam_decode_attn reads them without a slot table (sample r / kv_group, key j at j*ldk, head h at column
+ * h*dk); V is not read and no context is written.  bias_row [H, bias_ld >= Lk] or NULL; done (int32 [R]) or NULL: a row with
+ * done[r] != 0 gets Lk zeros.  dtype bf16 or f32 (arithmetic in f32), dk in {8, 16, 32, 64, 128} (KLAB_ERR_UNSUPPORTED
+ * otherwise), any H >= 1, Lk >= 1.  The head sum runs in ascending h in f32 without atomics (bit-reproducible) and the mean is
+ * that sum times 1.0f / H.                                                                                                  */
+int klab_t5_decode_attn_map(int dtype, const void* q, long q_bstride, int q_div, const void* k, long kv_bstride, long ldk, int kv_group,
+                            const float* bias_row, long bias_ld, const int* done, float* map, long map_bstride, int R, int H, int Lk,
+                            int dk, void* stream);
 
 /* ---- beam search (HF `_beam_search`, transformers/generation/utils.py; csrc/beam.hip) ------------------------------------
  * klab_beam_topk: per sample b, the 2k best of  log_softmax(logits row b*k+j) + run_score[b*k+j]  over all j < k and tokens,
@@ -683,7 +694,9 @@ typedef struct {
  *   session launches exactly what it launched before the field existed.
  * gen_scores (want_logprobs sessions): klab_gen_finalize over the first length <= (last position chosen) + 1 columns: score [M]
  *   f32, len [M] int32, order [B*n_out] int32 (n_out <= n <= 64; order may be NULL), and the log-probabilities themselves into
- *   token_logprobs [M, length] f32 when not NULL.  All device memory.                                                     */
+ *   token_logprobs [M, length] f32 when not NULL.  All device memory.
+ * gen_set_attn / gen_attn_bytes (sampling, pick and force): the session also writes the head-mean cross-attention map of every
+ *   position into a caller-owned f32 [n_dec_layers, M, max_length, Le] buffer armed in front of gen_begin (below).             */
 #define KLAB_GEN_PICK 0
 #define KLAB_GEN_SAMPLE 1
 #define KLAB_GEN_BEAM 2
@@ -707,6 +720,22 @@ typedef struct {
  *   positions 1 .. n_forced are klab_force_rows with finish_on_eos = 0 and no logits read, the later ones run as without a
  *   table; the processors see the prompt as history.  KLAB_GEN_BEAM with a table: KLAB_ERR_BADARG.                          */
 int klab_engine_gen_set_forced(klab_engine* e, const long long* tokens_dev, long ld, int n_forced, void* stream);
+/* Cross-attention maps of the NEXT klab_engine_gen_begin (one-shot in the same way: gen_begin takes the arming whether it succeeds
+ * or fails, and a session begun without it launches exactly what it launched before these two functions existed, keeps no maps and
+ * returns bit-identical results).  maps_dev: f32 [n_dec_layers, B*n, max_length, Le] on the device (Le = image + source tokens, the
+ * encoder length of the binding), owned by the caller, alive while the session runs and NOT part of the session workspace
+ * (gen_workspace_bytes is what it is without maps); gen_attn_bytes is its size, 0 for beam search (its rows are re-parented every
+ * step; as with want_logprobs it carries no maps) and for settings gen_workspace_bytes returns 0 for.  NULL with 0 bytes disarms.
+ * gen_begin returns KLAB_ERR_BADARG when the armed buffer is smaller than gen_attn_bytes or the mode is KLAB_GEN_BEAM.
+ * maps[i, r, p, :] = the head mean of layer i's cross-attention probabilities (klab_t5_decode_attn_map) of row r's query at
+ * decoder position p - 1, i.e. the attention that produced the token of position p (the column convention of the
+ * log-probabilities).  gen_begin clears the buffer with one asynchronous memset and fills column 1 from the prefill's cross q
+ * of position 0; gen_step(t) fills column t + 1, one launch per layer beside the unchanged klab_t5_beam_decode_attn.  Column 0,
+ * columns not reached and everything after a row's EOS (the session's done flags, as the choosing kernel of the position before
+ * left them) stay 0.  No host read is added.  stream is unused today: the session's own launches clear and write the buffer on
+ * the streams they are given.                                                                                                */
+size_t klab_engine_gen_attn_bytes(klab_engine* e, const klab_gen_cfg* cfg);
+int klab_engine_gen_set_attn(klab_engine* e, float* maps_dev, size_t bytes, void* stream);
 size_t klab_engine_gen_workspace_bytes(klab_engine* e, const klab_gen_cfg* cfg);
 int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, void* ws, void* stream);
 int klab_engine_gen_step(klab_engine* e, int t, void* ws, void* stream);

@@ -129,6 +129,7 @@ SIGNATURES = {
     "klab_t5_attn_fused_fwd": [C.POINTER(AttnFusedArgs), vp],
     "klab_t5_attn_bwd_fused": [C.POINTER(AttnBwdFusedArgs), vp],
     "klab_t5_beam_decode_attn": [i32, vp, i64, vp, vp, i64, i64, i32, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp],
+    "klab_t5_decode_attn_map": [i32, vp, i64, i32, vp, i64, i64, i32, vp, i64, vp, vp, i64, i32, i32, i32, i32, vp],
     "klab_beam_topk": [i32, vp, i64, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "klab_beam_update": [C.POINTER(BeamUpdateArgs), i32, vp],
     "klab_beam_init": [C.POINTER(BeamUpdateArgs), i32, i32, vp],

@@ -101,10 +101,17 @@ struct ForcedTable {
   long ld = 0;
   int n = 0;
 };
+// the cross-attention maps of a session (klab_engine_gen_set_attn): f32 [n_dec_layers, B*n, max_length, Le] on the device, the
+// caller's (p NULL: none)
+struct AttnMaps {
+  float* p = nullptr;
+  size_t bytes = 0;
+};
 struct GenRun {
   klab_gen_cfg cfg{};
   ProcSet lp;
   ForcedTable forced;
+  AttnMaps maps;
   int cur = 0;
 };
 
@@ -159,6 +166,7 @@ struct klab_engine {
   // the decoding session (klab_engine_gen_*) begun last on this binding
   GenRun gen;
   ForcedTable forced_armed;  // one-shot: taken (and cleared) by the next klab_engine_gen_begin
+  AttnMaps attn_armed;       // one-shot in the same way
   // lang scratch (no grad => reused across layers)
   void* kv_all = nullptr; void* dkv_all = nullptr;
   void* logits = nullptr; float *loss_row = nullptr, *inv_n = nullptr, *loss = nullptr;
@@ -1455,6 +1463,8 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
   e->bias_ready[0] = e->bias_ready[1] = e->bias_ready[2] = e->dec_embed_ready = e->inv_n_ready = e->kv_wgrad_done = false;
   e->loss_out = nullptr;
   e->forced_armed = ForcedTable();
+  e->attn_armed = AttnMaps();
+  e->gen.maps = AttnMaps();  // (sized for the old binding's rows)
   if (e->pe_kp != e->pe_k0)  // the padding columns of the patch-embedding weight rows: written here, never again
     RC((int)hipMemsetAsync((char*)e->warena + (size_t)e->P[0][e->si.pew].warena_off * e->es, 0,
                            (size_t)e->cfg.swin.embed_dim * e->pe_kp * e->es, hs));
@@ -1917,6 +1927,8 @@ struct DecodeRows {
   void* ab = nullptr;  // gated feed-forward: the two pre-activations [M, 2 d_ff]
   void* cache; long cache_layer; int cache_rows;
   int kv_group = 1; const int* kv_slot = nullptr; long slot_ld = 0;
+  // optional (a session armed with klab_engine_gen_set_attn): the maps [n_dec_layers, M, cache_rows, Le] and the rows' done flags
+  float* maps = nullptr; const int* done = nullptr;
 };
 
 // the decoder over position t for r.M rows whose input ids are tokens [M], logits -> r.logits [M, vocab]
@@ -1957,6 +1969,10 @@ int decode_rows(klab_engine* e, const Ctx& c, int t, const long long* tokens, co
     RC(linear_fwd(c, r.xn, M, d, P[l.cq].warena_off, inner, r.q, inner, c.dt));
     RC(klab_t5_beam_decode_attn(c.dt, r.q, inner, eoff(c, e->kv_all, (long)i * 2 * inner), eoff(c, e->kv_all, (long)i * 2 * inner + inner),
                                 (long)Le * kv_ld, kv_ld, r.kv_group, nullptr, 0, nullptr, 0, r.ctx, inner, M, H, Le, dk, c.ws()));
+    if (r.maps)  // column t + 1 of layer i: the attention that produces the token of position t + 1
+      RC(klab_t5_decode_attn_map(c.dt, r.q, inner, 1, eoff(c, e->kv_all, (long)i * 2 * inner), (long)Le * kv_ld, kv_ld, r.kv_group, nullptr,
+                                 0, r.done, r.maps + (((long)i * M * r.cache_rows) + t + 1) * Le, (long)r.cache_rows * Le, M, H, Le, dk,
+                                 c.ws()));
     RC(proj_res(r.ctx, inner, P[l.co].warena_off));
     // feed forward
     RC(klab_rmsnorm_fwd(h, W[l.ln2], r.xn, c.dt, nullptr, r.rstd, M, d, cfg.ln_eps, 0, 0, 0, 0.f, nullptr, 0, c.ws()));
@@ -2179,14 +2195,39 @@ extern "C" int klab_engine_gen_set_forced(klab_engine* e, const long long* token
   return 0;
 }
 
+// bytes of the maps a session with these settings can carry: f32 [n_dec_layers, B*n, max_length, Le]; 0: none (beam search)
+static size_t gen_attn_bytes(const klab_engine* e, const klab_gen_cfg& g) {
+  if (g.mode == KLAB_GEN_BEAM) return 0;
+  return (size_t)e->cfg.main.n_dec_layers * e->B * g.n * g.max_length * e->Le * sizeof(float);
+}
+
+extern "C" size_t klab_engine_gen_attn_bytes(klab_engine* e, const klab_gen_cfg* cfg) {
+  ProcSet lp;
+  if (!e || !cfg || make_procs(e, cfg->procs, lp) || !gen_shape_ok(e, *cfg, lp)) return 0;
+  return gen_attn_bytes(e, *cfg);
+}
+
+extern "C" int klab_engine_gen_set_attn(klab_engine* e, float* maps_dev, size_t bytes, void* stream) {
+  (void)stream;  // the buffer is cleared and written by the session's own launches, on the stream they are given
+  if (!e) return KLAB_ERR_BADARG;
+  e->attn_armed = AttnMaps();
+  if (!maps_dev && bytes == 0) return 0;  // disarm
+  if (!maps_dev || bytes == 0) return KLAB_ERR_BADARG;
+  e->attn_armed.p = maps_dev; e->attn_armed.bytes = bytes;
+  return 0;
+}
+
 extern "C" int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, void* ws, void* stream) {
   if (!e) return KLAB_ERR_BADARG;
   const ForcedTable forced = e->forced_armed;  // consumed whatever happens below
   e->forced_armed = ForcedTable();
+  const AttnMaps maps = e->attn_armed;  // ... and so are the maps
+  e->attn_armed = AttnMaps();
   if (!cfg || !ws) return KLAB_ERR_BADARG;
   ProcSet lp;
   RC(make_procs(e, cfg->procs, lp));
   if (!gen_shape_ok(e, *cfg, lp)) return KLAB_ERR_BADARG;
+  if (maps.p && (cfg->mode == KLAB_GEN_BEAM || maps.bytes < gen_attn_bytes(e, *cfg))) return KLAB_ERR_BADARG;
   // a table: never under beam search; a force session needs every position 1 .. max_length - 1 from it; a prompt (pick, sample)
   // leaves at least nothing beyond the sequence, and keeps no log-probabilities (klab_gen_finalize would take an EOS inside the
   // prompt for the row's end)
@@ -2197,6 +2238,7 @@ extern "C" int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, vo
   g.cfg = *cfg; g.cfg.procs = nullptr;
   g.lp = std::move(lp);
   g.forced = forced;
+  g.maps = maps;
   g.cur = 0;
   Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
   const klab_t5_cfg& mc = e->cfg.main;
@@ -2216,6 +2258,16 @@ extern "C" int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, vo
   for (int i = 0; i < mc.n_dec_layers; ++i)
     RC(klab_beam_copy_rows((int)e->es, e->dec.L[i].qkv, (long)e->Lt * 3 * inner, n, eoff(c, w.rows.cache, (long)i * w.rows.cache_layer),
                            (long)Lm * 3 * inner, B * n, 3 * inner, c.ws()));
+  if (g.maps.p) {  // column 1 of every layer from the prefill's cross q of position 0 (kept by both forms of the prefill's cross
+                   // attention, t5_stack_forward), shared by the n rows of an image; every other column starts at 0
+    const int Le = e->Le;
+    const long kv_ld = (long)mc.n_dec_layers * 2 * inner;
+    RC((int)hipMemsetAsync(g.maps.p, 0, gen_attn_bytes(e, g.cfg), c.s));
+    for (int i = 0; i < mc.n_dec_layers; ++i)
+      RC(klab_t5_decode_attn_map(c.dt, e->dec.L[i].qc, (long)e->Lt * inner, n, eoff(c, e->kv_all, (long)i * 2 * inner), (long)Le * kv_ld,
+                                 kv_ld, n, nullptr, 0, w.done, g.maps.p + (((long)i * B * n * Lm) + 1) * Le, (long)Lm * Le, B * n,
+                                 mc.n_heads, Le, mc.d_kv, c.ws()));
+  }
   // position 1 (HF's first step) from the prefill's position-0 logits, shared by the n rows of an image
   RC(gen_pos(e, c, w, e->logits, (long)e->Lt * mc.vocab, n, 1));
   g.cur = 1;
@@ -2232,6 +2284,7 @@ extern "C" int klab_engine_gen_step(klab_engine* e, int t, void* ws, void* strea
   plan_gen(e, g.cfg, g.lp, ws, w);
   DecodeRows r = w.rows;
   if (g.cfg.mode == KLAB_GEN_BEAM) r.kv_slot = w.slot[t & 1];
+  if (g.maps.p) { r.maps = g.maps.p; r.done = w.done; }
   RC(decode_rows(e, c, t, w.prev, r));
   RC(gen_pos(e, c, w, r.logits, e->cfg.main.vocab, 1, t + 1));
   g.cur = t + 1;

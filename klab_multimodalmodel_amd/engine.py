@@ -119,6 +119,8 @@ ENGINE_SIGS = {
                           C.POINTER(C.c_void_p), C.c_void_p], C.c_int),
     "klab_engine_forward": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p], C.c_int),
     "klab_engine_gen_set_forced": ([C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p], C.c_int),
+    "klab_engine_gen_attn_bytes": ([C.c_void_p, C.POINTER(L.GenCfg)], C.c_size_t),
+    "klab_engine_gen_set_attn": ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
     "klab_engine_gen_workspace_bytes": ([C.c_void_p, C.POINTER(L.GenCfg)], C.c_size_t),
     "klab_engine_gen_begin": ([C.c_void_p, C.POINTER(L.GenCfg), C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_gen_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
@@ -290,6 +292,7 @@ class Engine:
         self.shape = None
         self._gen = None  # the klab_gen_cfg of the decoding session begun last
         self._forced = self._forced_armed = None  # forced-token tables: of that session / armed for the next gen_begin
+        self._attn = self._attn_armed = None  # cross-attention maps, in the same two roles
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -421,9 +424,30 @@ class Engine:
                 "klab_engine_gen_set_forced")
         self._forced_armed = tokens
 
+    def gen_attn_bytes(self, cfg):
+        """bytes of the cross-attention maps a session with these settings can carry, f32 [n_dec_layers, B*n, max_length, Le]; 0 = none
+        (beam search, or settings gen_workspace_bytes refuses)"""
+        return int(self._lib.klab_engine_gen_attn_bytes(self._h, C.byref(cfg)))
+
+    def gen_set_attn(self, buf):
+        """arms the cross-attention maps of the NEXT gen_begin (one-shot; gen_begin takes the arming whether it succeeds or not): buf a
+        contiguous f32 device tensor of at least gen_attn_bytes(cfg) bytes, read as [n_dec_layers, B*n, max_length, Le]; the session
+        clears it and writes into [i, r, p] the head-mean cross-attention of layer i that produced row r's token of position p
+        (column 0, columns not reached and everything after a row's EOS stay 0).  None disarms.  The engine keeps the tensor alive
+        until the next gen_begin after that one."""
+        if buf is None:
+            L.check(self._lib.klab_engine_gen_set_attn(self._h, None, 0, L.stream_ptr()), "klab_engine_gen_set_attn")
+            self._attn_armed = None
+            return
+        if buf.dtype != torch.float32 or not buf.is_contiguous() or not buf.is_cuda:
+            raise ValueError("the cross-attention maps must be a contiguous float32 device tensor")
+        L.check(self._lib.klab_engine_gen_set_attn(self._h, buf.data_ptr(), buf.numel() * 4, L.stream_ptr()), "klab_engine_gen_set_attn")
+        self._attn_armed = buf
+
     def gen_begin(self, cfg, ws):
         """after an evaluation-mode forward (the prefill): the session's state, and position 1 from the prefill's position-0 logits"""
         self._forced, self._forced_armed = self._forced_armed, None  # (the session's table stays referenced)
+        self._attn, self._attn_armed = self._attn_armed, None  # (... and its maps)
         L.check(self._lib.klab_engine_gen_begin(self._h, C.byref(cfg), ws.data_ptr(), L.stream_ptr()), "klab_engine_gen_begin")
         self._gen = cfg
 

@@ -8,6 +8,7 @@ wraps -- but forward + backward run in the native engine (libklab_mm.so), not in
 transformer.parameters())`, `model.module.transformer.train()/eval()`, `loss.item()`,
 `loss.backward()`, `model.module.save(...)`.
 """
+import math
 import os
 from typing import Dict, List
 
@@ -377,7 +378,7 @@ class MyModel(nn.Module):
     def generate(self, pixels, src, max_length=20, kv_cache=True, num_beams=1, length_penalty=1.0, early_stopping=False,
                  num_return_sequences=1, return_scores=False, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_length=0, min_new_tokens=None,
-                 return_logprobs=False, best_of=None, decoder_input_ids=None):
+                 return_logprobs=False, best_of=None, decoder_input_ids=None, return_cross_attention=False):
         """greedy decoding with HF's default generation settings (ref/models/model.py:28: max_length 20, no sampling).
         Every kv_cache=True call is one decoding session on the device (_generate_on_device; SURVEY §8 row f-3, HF/t5:308-332):
         prefill = one evaluation-mode forward (Swin, both encoders, the cross K/V of all layers, decoder position 0), then every
@@ -408,7 +409,21 @@ class MyModel(nn.Module):
         `_prepare_decoder_input_ids_for_generation`); each image's prompt is shared by its num_return_sequences rows; the session
         takes the prompt positions from a table (klab_force_rows, no logits read) and chooses the rest as without one.  As in HF
         max_length counts the prompt, the processors see it as history (min_new_tokens counts from its end) and an EOS inside it
-        does not finish the row.  Not with num_beams > 1, kv_cache=False, return_logprobs or best_of."""
+        does not finish the row.  Not with num_beams > 1, kv_cache=False, return_logprobs or best_of.
+        return_cross_attention=True (greedy and sampling on the K/V cache, with or without processors, best_of or a decoder
+        prompt): returns (sequences, info) with info["cross_attention"] fp32 [rows, n_dec_layers, L, Le] -- HF's
+        `cross_attentions` of output_attentions=True averaged over the heads: [r, i, p] is layer i's attention over the encoder
+        tokens that produced row r's token of position p (the query of position p - 1), written by the session itself
+        (klab_t5_decode_attn_map beside every cross-attention of the decoder; tokens and log-probabilities are bit-identical with
+        and without it).  The Le encoder tokens are the info["image_tokens"] Swin tokens, an info["image_grid"] = (g, g) raster,
+        followed by the source-text tokens (the reference's torch.cat order).  Column 0 (the start token) and everything after a
+        row's EOS are 0; with best_of the rows are those of the sequences.  With return_logprobs as well the same info carries
+        both.  Not with num_beams > 1 (beam search re-parents its rows every step) or kv_cache=False."""
+        if return_cross_attention:
+            if num_beams > 1:
+                raise ValueError("return_cross_attention needs num_beams == 1 (beam search re-parents its rows every step and keeps no maps)")
+            if not kv_cache:
+                raise ValueError("return_cross_attention runs on the K/V cache only: it needs kv_cache=True")
         prompt = None
         if decoder_input_ids is not None:
             for bad, why in ((num_beams > 1, "num_beams > 1 (beam search takes no forced tokens)"),
@@ -453,7 +468,7 @@ class MyModel(nn.Module):
                 raise ValueError(f"`num_return_sequences` has to be a positive integer, but is {num_return_sequences}")
             return self._generate_sample(pixels, src, max_length, num_return_sequences, float(temperature), int(top_k), float(top_p),
                                          procs, return_logprobs=return_logprobs, best_of=best_of, length_penalty=length_penalty,
-                                         prompt=prompt)
+                                         prompt=prompt, return_cross_attention=return_cross_attention)
         if num_return_sequences > num_beams:
             raise ValueError(f"`num_return_sequences` ({num_return_sequences}) has to be smaller or equal to `num_beams` ({num_beams}).")
         if num_beams > 1:
@@ -465,7 +480,7 @@ class MyModel(nn.Module):
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence scores)")
         if kv_cache:
             return self._generate_sample(pixels, src, max_length, 1, 1.0, 0, 1.0, procs, pick=True, return_logprobs=return_logprobs,
-                                         length_penalty=length_penalty, prompt=prompt)
+                                         length_penalty=length_penalty, prompt=prompt, return_cross_attention=return_cross_attention)
         if procs is not None:
             raise ValueError("logits processors run on the K/V cache only: repetition_penalty, no_repeat_ngram_size, bad_words_ids, "
                              "min_length and min_new_tokens need kv_cache=True")
@@ -515,7 +530,7 @@ class MyModel(nn.Module):
         return ids
 
     @torch.no_grad()
-    def score(self, pixels, src, candidates, length_penalty=1.0, top=None):
+    def score(self, pixels, src, candidates, length_penalty=1.0, top=None, return_cross_attention=False):
         """How likely each of N given captions is for each image: candidates int64 [B, N, L] as labels are (no start token, each
         row closed by EOS, whatever follows the first EOS ignored; a row without EOS counts all L tokens), 1 <= N <= 64, L >= 1.
         One prefill at B rows, then ONE force session of B*N rows against the shared cross K/V (Swin and both encoders run once per
@@ -523,7 +538,10 @@ class MyModel(nn.Module):
         log_softmax(logits)[token]; the L - 1 decoder steps are enqueued without a host read, then one klab_gen_finalize.
         Returns dict(token_logprobs [B, N, L] fp32, 0 after a row's EOS; lengths [B, N] int32, tokens through the first EOS;
         scores [B, N] = sum / lengths ** length_penalty, the convention of generate's info["scores"] (length_penalty=0: the
-        sequence log-likelihood); order [B, top or N] int64, each image's candidate indices best first, ranked on the device)."""
+        sequence log-likelihood); order [B, top or N] int64, each image's candidate indices best first, ranked on the device).
+        return_cross_attention=True adds cross_attention fp32 [B, N, n_dec_layers, L, Le]: [b, j, i, l] is layer i's head-mean
+        attention over the encoder tokens (image tokens first, see generate) that predicted label l of candidate j, 0 after the
+        row's first EOS; with it image_tokens and image_grid.  The other entries are bit-identical with and without it."""
         cfg = self.main_cfg
         cand = torch.as_tensor(candidates)
         if cand.dim() != 3 or cand.dtype != torch.int64:
@@ -557,6 +575,7 @@ class MyModel(nn.Module):
                 raise ValueError(f"scoring: unsupported candidates per image {N} / length {L} for this model")
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             eng.gen_set_forced(table, L)
+            att = self._attn_maps_for(eng, gen, B * N, L + 1) if return_cross_attention else None
             eng.gen_begin(gen, ws)
             for t in range(1, L):  # nothing is chosen: the host has nothing to wait for
                 eng.gen_step(t, ws)
@@ -564,10 +583,13 @@ class MyModel(nn.Module):
         finally:
             self.transformer.train(was_training)
         order = order.long().view(B, -1) - torch.arange(B, device=dev).view(B, 1) * N
-        return dict(token_logprobs=lp[:, 1:].reshape(B, N, L), lengths=lens.view(B, N), scores=scores.view(B, N), order=order)
+        out = dict(token_logprobs=lp[:, 1:].reshape(B, N, L), lengths=lens.view(B, N), scores=scores.view(B, N), order=order)
+        if return_cross_attention:  # label l is session column l + 1
+            out.update(self._attn_info(att[:, :, 1:].permute(1, 0, 2, 3).reshape(B, N, att.shape[0], L, -1)))
+        return out
 
     def _generate_on_device(self, pixels, src, max_length, mode, n, procs=None, num_return_sequences=None, temperature=1.0, top_k=0,
-                            top_p=1.0, length_penalty=1.0, early_stopping=False, logprobs=False, prompt=None):
+                            top_p=1.0, length_penalty=1.0, early_stopping=False, logprobs=False, prompt=None, maps=False):
         """One prefill at B rows (Swin, both encoders and the cross K/V run once per image, not per row), then a decoding session of
         B*n rows on the device (row b*n + j: beam / sample j of image b, HF's `_expand_inputs_for_generation`): every step is the
         decoder over B*n rows and the mode's choice of the next tokens (`klab_engine_gen_step`); the host reads one stop word per
@@ -581,7 +603,9 @@ class MyModel(nn.Module):
         info = dict(token_logprobs, scores, lengths) (see generate); with num_return_sequences < n the rows returned are each
         image's num_return_sequences best by score, best first, ranked and gathered on the device.
         prompt (sampling and pick): the decoder prompt [B, Lp] with its start token (_decoder_prompt); its Lp - 1 tokens after
-        the start token are forced at positions 1 .. Lp - 1 of each image's n rows."""
+        the start token are forced at positions 1 .. Lp - 1 of each image's n rows.
+        maps (sampling and pick): the session also writes its cross-attention maps (Engine.gen_set_attn) and info carries
+        cross_attention [rows, n_dec_layers, L, Le], image_tokens and image_grid (see generate), for the rows returned."""
         if mode == "beam" and early_stopping not in (False, True, "never"):
             raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
         if max_length < 2:
@@ -608,6 +632,7 @@ class MyModel(nn.Module):
             ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
             if prompt is not None and prompt.shape[1] > 1:
                 eng.gen_set_forced(prompt.to(src.device).repeat_interleave(n, 0).contiguous(), prompt.shape[1] - 1)
+            att = self._attn_maps_for(eng, gen, B * n, max_length) if maps else None
             eng.gen_begin(gen, ws)
             cur = 1
             while cur < max_length - 1 and eng.gen_going(ws, cur):
@@ -615,18 +640,39 @@ class MyModel(nn.Module):
                 cur += 1
             if mode != "beam":
                 seq = eng.gen_result(ws, n, cur + 1)[0]
-                if not logprobs:
+                if not logprobs and not maps:
                     return seq, None
-                n_out = num_return_sequences if num_return_sequences is not None and num_return_sequences < n else None
-                lp, scores, lens, order = eng.gen_scores(ws, cur + 1, n_out, length_penalty)
-                if order is not None:
-                    order = order.long()
-                    seq, lp, scores, lens = seq[order], lp[order], scores[order], lens[order]
-                return seq, dict(token_logprobs=lp, scores=scores, lengths=lens)
+                info, order = {}, None
+                if logprobs:
+                    n_out = num_return_sequences if num_return_sequences is not None and num_return_sequences < n else None
+                    lp, scores, lens, order = eng.gen_scores(ws, cur + 1, n_out, length_penalty)
+                    if order is not None:
+                        order = order.long()
+                        seq, lp, scores, lens = seq[order], lp[order], scores[order], lens[order]
+                    info.update(token_logprobs=lp, scores=scores, lengths=lens)
+                if maps:
+                    att = att[:, :, :cur + 1].permute(1, 0, 2, 3)  # [B*n, n_dec_layers, L, Le]
+                    info.update(self._attn_info(att[order] if order is not None else att.contiguous()))
+                return seq, info
             seq, scores, lens = eng.gen_result(ws, num_return_sequences, max_length)
         finally:
             self.transformer.train(was_training)
         return seq[:, :1 + int(lens.max())], scores
+
+    def _attn_maps_for(self, eng, gen, rows, max_length):
+        """arms the cross-attention maps of the next gen_begin: f32 [n_dec_layers, rows, max_length, Le], the session's to clear and fill"""
+        nbytes = eng.gen_attn_bytes(gen)
+        if nbytes == 0:
+            raise ValueError("cross-attention maps: these generation settings carry none")
+        att = torch.empty(nbytes // 4, dtype=torch.float32, device=eng.workspace.device)
+        eng.gen_set_attn(att)
+        return att.view(self.main_cfg.num_decoder_layers, rows, max_length, -1)
+
+    def _attn_info(self, att):
+        """the cross-attention entries of a result: the maps and where the image tokens lie in their last dimension"""
+        n_img = self._engine.n_img
+        g = math.isqrt(n_img)
+        return dict(cross_attention=att, image_tokens=n_img, image_grid=(g, g))
 
     def _generate_beam(self, pixels, src, max_length, num_beams, length_penalty, early_stopping, num_return_sequences, return_scores,
                        procs=None):
@@ -636,15 +682,18 @@ class MyModel(nn.Module):
         return (seq, scores) if return_scores else seq
 
     def _generate_sample(self, pixels, src, max_length, num_return_sequences, temperature, top_k, top_p, procs=None, pick=False,
-                         return_logprobs=False, best_of=None, length_penalty=1.0, prompt=None):
+                         return_logprobs=False, best_of=None, length_penalty=1.0, prompt=None, return_cross_attention=False):
         """HF's `_sample` as a decoding session (_generate_on_device); pick=True: greedy decoding, the processed arg-max.
-        return_logprobs: (sequences, info); best_of: that many rows per image, the num_return_sequences best returned"""
+        return_logprobs / return_cross_attention: (sequences, info); best_of: that many rows per image, the num_return_sequences
+        best returned"""
         n = num_return_sequences if best_of is None else best_of
         seq, info = self._generate_on_device(pixels, src, max_length, "pick" if pick else "sample", n, procs,
                                              num_return_sequences=num_return_sequences, temperature=temperature, top_k=top_k, top_p=top_p,
                                              length_penalty=length_penalty, logprobs=return_logprobs or best_of is not None,
-                                             prompt=prompt)
-        return (seq, info) if return_logprobs else seq
+                                             prompt=prompt, maps=return_cross_attention)
+        if return_cross_attention and not return_logprobs:  # (best_of ranks by the scores; they were not asked for)
+            info = {k: info[k] for k in ("cross_attention", "image_tokens", "image_grid")}
+        return (seq, info) if return_logprobs or return_cross_attention else seq
 
     def _join_pending_update(self):
         """an optimizer update still running on its own stream (optim.FusedAdam(step_in_backward=True)) writes the weights:

@@ -346,6 +346,20 @@ def dbias_reduce(ds_ws, dbias, *, nbatch, H, Lq, Lk):
             "klab_dbias_reduce")
 
 
+def decode_attn_map(q, k, out, *, R, H, Lk, dk, q_bstride, kv_bstride, ldk, out_bstride, q_div=1, kv_group=1, bias_row=None, bias_ld=0,
+                    done=None):
+    """out[r*out_bstride + j] (f32) = the head mean of softmax_j(q_h . k_{h,j} + bias_row[h, j]) for the one query row of each of
+    R decoding rows: row r's query at q + (r // q_div)*q_bstride, its keys in sample r // kv_group at k + s*kv_bstride + j*ldk,
+    head h at column h*dk (element strides; q and k bf16 or f32, the same).  bias_row f32 [H, bias_ld] or None; done int32 [R] or
+    None: rows with done[r] != 0 get zeros.  V is not read (klab_t5_decode_attn_map, csrc/attn_map.hip)."""
+    lib = L.load()
+    if k.dtype != q.dtype or out.dtype != torch.float32:
+        raise ValueError("decode_attn_map: q and k share a dtype and the map is float32")
+    L.check(lib.klab_t5_decode_attn_map(L.dtype_code(q.dtype), q.data_ptr(), q_bstride, q_div, k.data_ptr(), kv_bstride, ldk, kv_group,
+                                        L.ptr(bias_row), bias_ld, L.ptr(done), out.data_ptr(), out_bstride, R, H, Lk, dk, L.stream_ptr()),
+            "klab_t5_decode_attn_map")
+
+
 def _swin_args(qkv, ctx, bias, logit_scale, lse, B, R, w, shift, H, Cc, bias_table=None, v_bias=None, dv_bias=None):
     a = L.SwinAttnArgs()
     a.v_bias, a.dv_bias = L.ptr(v_bias), L.ptr(dv_bias)
