@@ -82,8 +82,9 @@ int klab_quant_fp8_rows(const void* x, long ldx, int M, int K, void* x8, long ld
  * quantised to arena_fp8 + off + r*K with its scale at scales[(off + r*K) / 8]                                         */
 int klab_quant_fp8_arena(const void* desc_dev, int ndesc, long total_rows, const void* arena_bf16, void* arena_fp8, float* scales,
                          void* stream);
-/* n independent GEMMs.  Split-K weight-gradient members (bf16, both operands m-major, f32 C with accumulate + atomic_ok, no
- * epilogue extras) are batched into single launches of up to 8; every other member is run through klab_gemm. */
+/* n independent GEMMs.  Weight-gradient members (bf16, both operands m-major, f32 C with atomic_ok, no epilogue extras) are
+ * batched into single launches of up to 8; every other member is run through klab_gemm.  Per member: accumulate = 1 adds to C
+ * (split along K, float atomics); accumulate = 0 stores the product (never split, plain stores, C is not read). */
 int klab_gemm_grouped(const klab_gemm_args* list, int n, void* stream);
 /* the same with the choice of tile: large_tiles = 0 is klab_gemm_grouped; large_tiles = 1 runs the WHOLE list (at most 32 members) in one
  * launch on 256 x 256 tiles without split-K or atomics when every member has that form (as above, and N >= 128, K % 64 == 0, K >= 1024,

@@ -26,10 +26,10 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 namespace klab {
 
 // On/off switch from the environment: unset or non-zero = on, "0" = off.  Callers cache the result in a function-local static,
-// so each is read once per process.  Exactly nine exist -- KLAB_ZERO_ON_SIDE, KLAB_EARLY_SMALL, KLAB_LMHEAD_AREG,
+// so each is read once per process.  Exactly ten exist -- KLAB_ZERO_ON_SIDE, KLAB_EARLY_SMALL, KLAB_LMHEAD_AREG,
 // KLAB_T5_ATTN_FUSED, KLAB_T5_ATTN_BWD_FUSED, KLAB_SWIN_FUSED_EMBED, KLAB_SWIN_FUSED_LIN_LN, KLAB_WGRAD_GROUP_TILES,
-// KLAB_GEMM_P8 -- because tests/test_switches_gpu.py and tests/test_attn_bwd_fused_switch_gpu.py run the bench with each one
-// off and assert the loss the default forms give.
+// KLAB_GEMM_P8, KLAB_WGRAD_STORE -- because tests/test_switches_gpu.py, tests/test_attn_bwd_fused_switch_gpu.py and
+// tests/test_wgrad_store_switch_gpu.py run the bench with each one off and assert the loss the default forms give.
 inline bool env_on(const char* name) {
   const char* v = getenv(name);
   return !v || atoi(v) != 0;
@@ -38,6 +38,10 @@ inline bool env_on(const char* name) {
 // raise a kernel's dynamic-LDS limit once per (kernel, size): hipFuncSetAttribute is not a stream operation and must
 // not be issued while the stream is being captured into a hipGraph (misc.hip)
 int ensure_dyn_lds(const void* kernel, size_t bytes);
+
+// clear n f32 ranges (ptrs[i], counts[i] floats; empty ones are skipped) with one launch per ZERO_RANGES_MAX of them (misc.hip)
+constexpr int ZERO_RANGES_MAX = 16;
+int zero_ranges(float* const* ptrs, const long* counts, int n, hipStream_t s);
 
 template <typename T> struct TypeTag;
 template <> struct TypeTag<float> { static constexpr int id = KLAB_F32; };

@@ -19,7 +19,9 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gemm_shared.h"  // klab::tl_launch_probe: a launch carries the probe's events as its own start / stop events
@@ -205,6 +207,16 @@ struct klab_engine {
   bool dec_embed_ready = false;   // ... and the decoder's input embedding
   bool inv_n_ready = false;       // ... and 1 / n_valid of the labels
   bool kv_wgrad_done = false;     // the cross k|v weight gradients went out with the decoder layers' groups
+  // Write plan of the main model's gradient buffer (wgrad_write_plan): the slices whose first writer STORES (the products of the
+  // multi-layer large-tile groups, the LM-head weight gradient) are neither cleared nor read back; everything else of segments 0
+  // and 1 is cleared, as coalesced ranges.  Offsets and lengths in floats from G[2].
+  struct WritePlan {
+    bool valid = false, graph = false, kv = false;           // built for this use_graph / cross k|v-in-the-groups setting
+    bool head_store = false, any_store = false;              // the LM-head weight gradient stores; anything stores at all
+    std::vector<char> store[2];                              // [encoder, decoder][layer]: the layer's products store
+    std::vector<std::pair<long, long>> stored;               // the slices store products may target (WgradQueue::push checks)
+    std::vector<std::pair<long, long>> clear[2];             // per segment: the ranges cleared at backward entry
+  } wplan;
   // stream capture is illegal on the legacy default stream (where PyTorch runs unless told otherwise): in graph mode
   // calls arriving on stream 0 are executed on this engine-owned stream, fenced in and out with events
   hipStream_t own = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
@@ -892,11 +904,77 @@ int main_after_side(const Ctx& c) {
 // backward segment, so they may run any time after the producer: they are queued here and released in batches with ONE
 // main->side event per layer (an event record costs the main queue ~6 us; one per weight gradient left ~40 us of
 // bubbles in every layer's critical path).
-struct PendingWgrad { const void* dy; long lddy; const void* x; long ldx; int M, N, K; float* dw; };
+static bool wgrad_store_on() {
+  static const bool on = klab::env_on("KLAB_WGRAD_STORE");
+  return on;
+}
+// Release plan of a stack's weight gradients (groups of >= GROUP_TILES = T tiles; switched off: one 128-wide grouped launch per
+// layer, round 2's form).  One T5-small layer's products are 48-64 tiles of 256 x 256 -- a fifth of the chip, and a large tile
+// takes ~100 us whatever the grid, which is why PER-LAYER large tiles lost (6.41 vs 6.18 ms).  So the layers of a stack except
+// its last are released in groups of >= T tiles (T5-small: decoder 3 + 2 layers, encoder 3 + 2; same box, three rounds, T = 0 / 90
+// / 110 (encoder 5 in one group) / 200: 5.990 / 5.855 / 5.880 / 5.982 ms per step), and the LAST layer alone on the
+// 128-wide kernel: its launch is the tail the segment's end waits for, and 70 us of tail hide behind the main chain's own last
+// kernels where a 180-us group does not.  A layer that reaches T on its own (T5-base / large) keeps the per-layer form.
+// store[i]: layer i's products leave in a list that spans layers -- the large-tile kernel, one workgroup per tile over the whole
+// contraction -- and each is its slice's only writer, so it STORES and the slice is not cleared (KLAB_WGRAD_STORE=0: never).
+// t5_stack_backward follows this plan and wgrad_write_plan derives the clears from it: the one place the rule lives.
+struct WgradRelease { std::vector<char> flush_at, store; bool kv_in_queue = false; };
+static WgradRelease wgrad_release_plan(const klab_engine* e, const klab_t5_cfg& cfg, int Ln, bool dec, bool have_dkv, const float* Gflat) {
+  const int d = cfg.d_model, inner = cfg.n_heads * cfg.d_kv, ff = cfg.d_ff;
+  WgradRelease r;
+  r.flush_at.assign(Ln, 1);
+  r.store.assign(Ln, 0);
+  constexpr int GROUP_TILES = 90;
+  static const bool group_on = klab::env_on("KLAB_WGRAD_GROUP_TILES");
+  const bool eager_main = Gflat == e->G[2] && !e->use_graph;
+  r.kv_in_queue = dec && have_dkv && eager_main && e->kvall_g_off >= 0;
+  if (group_on && Ln >= 3 && eager_main) {
+    auto T2 = [](int n, int k) { return (long)((n + 255) / 256) * ((k + 255) / 256); };
+    const long tl = T2(d, ff) + T2(cfg.ffn_gated ? 2 * ff : ff, d) + T2(d, inner) + T2(3 * inner, d) + (dec ? T2(d, inner) + T2(inner, d) + (r.kv_in_queue ? T2(2 * inner, d) : 0) : 0);
+    const int per_group = (int)((GROUP_TILES + tl - 1) / tl), per_layer = dec ? 7 : 4;
+    if (per_group >= 2) {
+      const int body = Ln - 1;
+      int ng = body / per_group;
+      if (ng < 1) ng = 1;
+      if (((body + ng - 1) / ng) * per_layer <= 32) {  // (a grouped launch takes 32 products)
+        std::fill(r.flush_at.begin(), r.flush_at.end(), 0);
+        int i = Ln - 1;
+        for (int gi = 0; gi < ng; ++gi) { i -= body / ng + (gi < body % ng ? 1 : 0); r.flush_at[i + 1] = 1; }
+        r.flush_at[0] = 1;
+      }
+    }
+  }
+  if (wgrad_store_on() && eager_main) {  // WgradQueue::flush, replayed: which layers leave in a list that spans two layers or more
+    const size_t per_layer = dec ? 6 + (r.kv_in_queue ? 1 : 0) : 4;
+    size_t queued = 0;
+    int first = Ln - 1;  // the list holds layers first .. i
+    for (int i = Ln - 1; i >= 0; --i) {
+      queued += per_layer;
+      if (!r.flush_at[i] && queued + 8 <= 32) continue;
+      if (first - i + 1 >= 2)
+        for (int k = i; k <= first; ++k) r.store[k] = 1;
+      queued = 0; first = i - 1;
+    }
+  }
+  return r;
+}
+
+struct PendingWgrad { const void* dy; long lddy; const void* x; long ldx; int M, N, K; float* dw; bool store; };
 struct WgradQueue {
   std::vector<PendingWgrad> q;
   int layers = 0;  // flush calls (= layers) the queue spans
-  void push(const void* dy, long lddy, const void* x, long ldx, int M, int N, int K, float* dw) { q.push_back({dy, lddy, x, ldx, M, N, K, dw}); }
+  const klab_engine::WritePlan* plan = nullptr; const float* Gbase = nullptr;  // store pushes are checked against the write plan
+  // store: this product is its slice's first and only writer and the slice was NOT cleared (the write plan): C = product, not C +=
+  int push(const void* dy, long lddy, const void* x, long ldx, int M, int N, int K, float* dw, bool store = false) {
+    if (store) {  // the slice must be one the write plan left uncleared for exactly this product
+      bool ok = false;
+      if (plan && plan->valid)
+        for (const auto& s : plan->stored) ok = ok || (s.first == dw - Gbase && s.second == (long)N * K);
+      if (!ok) return KLAB_ERR_BADARG;
+    }
+    q.push_back({dy, lddy, x, ldx, M, N, K, dw, store});
+    return 0;
+  }
   // Called once per layer.  now == false: keep the layer's products queued (the caller's plan releases them with a later layer's);
   // now == true: release everything queued in ONE grouped launch -- on 256 x 256 tiles (mm8p.hip: half the operand bytes of the
   // 128-wide grouping) when the list spans two layers or more, on the 128-wide kernel when it is one layer's.
@@ -914,7 +992,7 @@ struct WgradQueue {
     gs.reserve(q.size());
     for (const PendingWgrad& w : q) {
       klab_gemm_args g = G0(cs, w.N, w.K, w.M, w.dy, w.lddy, 0, w.x, w.ldx, 0, w.dw, w.K, KLAB_F32);  // as linear_wgrad
-      g.accumulate = 1; g.atomic_ok = 1;
+      g.accumulate = w.store ? 0 : 1; g.atomic_ok = 1;  // (a store member is right on either grouped kernel: never split along K)
       gs.push_back(g);
     }
     klab_engine::Probe& pr = c.e->probe[1];
@@ -990,46 +1068,28 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
   RC(rms_bwd(e->dxn, s.h[j], W[final_ln], s.rstd_f, nullptr, dh_cur, dy, final_ln, p, tag_of(stack_id, 0, SITE_FINAL), p,
              tag_of(stack_id, (int)L.size() - 1, SITE_FFN_OUT)));
   std::vector<int> pending_buckets;  // layers whose weight gradients are queued but not yet launched
-  // Release plan of the weight gradients (groups of >= GROUP_TILES = T tiles; switched off: one 128-wide grouped launch per layer,
-  // round 2's form).  One T5-small layer's products are 48-64 tiles of 256 x 256 -- a fifth of the chip, and a large tile
-  // takes ~100 us whatever the grid, which is why PER-LAYER large tiles lost (6.41 vs 6.18 ms).  So the layers of a stack except
-  // its last are released in groups of >= T tiles (T5-small: decoder 3 + 2 layers, encoder 3 + 2; same box, three rounds, T = 0 / 90
-  // / 110 (encoder 5 in one group) / 200: 5.990 / 5.855 / 5.880 / 5.982 ms per step), and the LAST layer alone on the
-  // 128-wide kernel: its launch is the tail the segment's end waits for, and 70 us of tail hide behind the main chain's own last
-  // kernels where a 180-us group does not.  A layer that reaches T on its own (T5-base / large) keeps the per-layer form.
-  const int Ln = (int)L.size();
-  std::vector<char> flush_at(Ln, 1);
-  constexpr int GROUP_TILES = 90;
-  static const bool group_on = klab::env_on("KLAB_WGRAD_GROUP_TILES");
-  const bool kv_in_queue = dec && dkv_all && Gflat == e->G[2] && !e->use_graph && e->kvall_g_off >= 0;
-  if (group_on && Ln >= 3 && Gflat == e->G[2] && !e->use_graph) {
-    auto T2 = [](int n, int k) { return (long)((n + 255) / 256) * ((k + 255) / 256); };
-    const long tl = T2(d, ff) + T2(cfg.ffn_gated ? 2 * ff : ff, d) + T2(d, inner) + T2(3 * inner, d) + (dec ? T2(d, inner) + T2(inner, d) + (kv_in_queue ? T2(2 * inner, d) : 0) : 0);
-    const int per_group = (int)((GROUP_TILES + tl - 1) / tl), per_layer = dec ? 7 : 4;
-    if (per_group >= 2) {
-      const int body = Ln - 1;
-      int ng = body / per_group;
-      if (ng < 1) ng = 1;
-      if (((body + ng - 1) / ng) * per_layer <= 32) {  // (a grouped launch takes 32 products)
-        std::fill(flush_at.begin(), flush_at.end(), 0);
-        int i = Ln - 1;
-        for (int gi = 0; gi < ng; ++gi) { i -= body / ng + (gi < body % ng ? 1 : 0); flush_at[i + 1] = 1; }
-        flush_at[0] = 1;
-      }
-    }
-  }
+  // the release plan of the weight gradients (wgrad_release_plan).  This backward's clears came from the write plan, which was
+  // built from the same call: a plan that says otherwise than this one means slices were left uncleared for nothing, or cleared
+  // under a product that stores -- an error, not something to run through.
+  const WgradRelease rel = wgrad_release_plan(e, cfg, (int)L.size(), dec, dkv_all != nullptr, Gflat);
+  const std::vector<char>& flush_at = rel.flush_at;
+  const bool kv_in_queue = rel.kv_in_queue;
+  const bool plan_live = Gflat == e->G[2];
+  if (plan_live && (!e->wplan.valid || e->wplan.store[stk] != rel.store)) return KLAB_ERR_BADARG;
+  wq.plan = &e->wplan; wq.Gbase = Gflat;
   for (int i = (int)L.size() - 1; i >= 0; --i) {
     const T5LayerIdx& l = L[i];
     T5LayerBufs& b = s.L[i];
     void* dhmid = e->dhmid_pool[i];
     void* dqkv = e->dqkv_pool[i];
+    const bool st = plan_live && rel.store[i];
     // ---------------- FFN ----------------
     --j;
-    wq.push(dy, d, b.hmid, ff, M, d, ff, G(l.wo));
+    RC(wq.push(dy, d, b.hmid, ff, M, d, ff, G(l.wo), st));
     if (cfg.ffn_gated) {  // wo dgrad -> gate backward (d(a) | d(b) side by side) -> ONE wgrad [2 d_ff, d] and ONE K = 2 d_ff dgrad
       RC(linear_dgrad(c, dy, d, M, d, P[l.wo].warena_off, ff, e->dh_ff, c.dt));
       RC(klab_geglu_bwd(e->dh_ff, ff, b.ab, 2 * ff, dhmid, 2 * ff, c.dt, M, ff, p, e->seed_dev, tag_of(stack_id, i, SITE_MID), c.ws()));
-      wq.push(dhmid, 2 * ff, b.xn3, d, M, 2 * ff, d, G(l.wi));  // wi_0 | wi_1 grads are adjacent
+      RC(wq.push(dhmid, 2 * ff, b.xn3, d, M, 2 * ff, d, G(l.wi), st));  // wi_0 | wi_1 grads are adjacent
       RC(linear_dgrad(c, dhmid, 2 * ff, M, 2 * ff, P[l.wi].warena_off, d, e->dxn, KLAB_F32));
     } else {
       {
@@ -1037,7 +1097,7 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
         g.aux = b.hmid; g.ldaux = ff; g.aux_mode = KLAB_AUX_NONZERO; g.aux_scale = inv_keep;
         RC(klab_gemm(&g, c.ws()));
       }
-      wq.push(dhmid, ff, b.xn3, d, M, ff, d, G(l.wi));
+      RC(wq.push(dhmid, ff, b.xn3, d, M, ff, d, G(l.wi), st));
       RC(linear_dgrad(c, dhmid, ff, M, ff, P[l.wi].warena_off, d, e->dxn, KLAB_F32));
     }
     {
@@ -1049,7 +1109,7 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
     if (dec) {  // ---------------- cross attention ----------------
       --j;
       void* dqc = e->dqc_pool[i];
-      wq.push(dy, d, b.ctx2, inner, M, d, inner, G(l.co));
+      RC(wq.push(dy, d, b.ctx2, inner, M, d, inner, G(l.co), st));
       dctx_ready = false;
       klab_attn_args a;
       memset(&a, 0, sizeof(a));
@@ -1063,10 +1123,10 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
       a.dv = eoff(c, dkv_all, (long)i * 2 * inner + inner); a.lddv = kv_ld;
       RC(attn_bwd(a, P[l.co].warena_off));
       if (kv_in_queue) {  // this layer's k | v projection: its slice of d(k|v) is final, the product joins the layer's group
-        wq.push(eoff(c, dkv_all, (long)i * 2 * inner), kv_ld, e->enc.out_t, d, B * Lkv, 2 * inner, d, Gflat + e->kvall_g_off + (long)i * 2 * inner * d);
+        RC(wq.push(eoff(c, dkv_all, (long)i * 2 * inner), kv_ld, e->enc.out_t, d, B * Lkv, 2 * inner, d, Gflat + e->kvall_g_off + (long)i * 2 * inner * d, st));
         e->kv_wgrad_done = true;
       }
-      wq.push(dqc, inner, b.xn2, d, M, inner, d, G(l.cq));
+      RC(wq.push(dqc, inner, b.xn2, d, M, inner, d, G(l.cq), st));
       RC(linear_dgrad(c, dqc, inner, M, inner, P[l.cq].warena_off, d, e->dxn, KLAB_F32));
       dy = next_dy();
       RC(rms_bwd(e->dxn, s.h[j], W[l.ln1], b.rstd2, dh_cur, dh_oth, dy, l.ln1, 0.f, 0, p, tag_of(stack_id, i, SITE_ATTN_OUT)));
@@ -1074,7 +1134,7 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
     }
     // ---------------- self attention ----------------
     --j;
-    wq.push(dy, d, b.ctx, inner, M, d, inner, G(l.o));
+    RC(wq.push(dy, d, b.ctx, inner, M, d, inner, G(l.o), st));
     dctx_ready = false;
     {
       klab_attn_args a;
@@ -1096,7 +1156,7 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
       if (arc == KLAB_ERR_UNSUPPORTED) { a.ds_defer = 0; a.ds_ws = nullptr; arc = attn_bwd(a, P[l.o].warena_off); }
       RC(arc);
     }
-    wq.push(dqkv, 3 * inner, b.xn1, d, M, 3 * inner, d, G(l.q));  // q|k|v grads are adjacent
+    RC(wq.push(dqkv, 3 * inner, b.xn1, d, M, 3 * inner, d, G(l.q), st));  // q|k|v grads are adjacent
     RC(linear_dgrad(c, dqkv, 3 * inner, M, 3 * inner, P[l.q].warena_off, d, e->dxn, KLAB_F32));
     {
       const bool first = (i == 0);
@@ -1461,6 +1521,7 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
   e->frozen_valid = false;
   e->seg1_zeroed = e->dbias_zeroed[0] = e->dbias_zeroed[1] = e->denc_in_dxn = false;  // (hand-offs between backward segments of the OLD binding)
   e->bias_ready[0] = e->bias_ready[1] = e->bias_ready[2] = e->dec_embed_ready = e->inv_n_ready = e->kv_wgrad_done = false;
+  e->wplan.valid = false;  // rebuilt at the next backward, for the new binding's buffers
   e->loss_out = nullptr;
   e->forced_armed = ForcedTable();
   e->attn_armed = AttnMaps();
@@ -2352,6 +2413,72 @@ extern "C" int klab_engine_gen_scores(klab_engine* e, void* ws, int length, int 
                                hipMemcpyDeviceToDevice, (hipStream_t)stream);
 }
 
+// The write plan of the main model's gradient buffer for the current use_graph / cross k|v setting: every slice whose first
+// writer stores -- the products of the layers wgrad_release_plan marks (the same call t5_stack_backward makes) and the LM-head
+// weight gradient, the first of the tied table's contributors (klab_embed_bwd then scatter-adds behind it on the side stream;
+// untied: lm_head's only writer, and `shared`, whose first writer scatter-adds, is cleared) -- is left alone, the rest of segments
+// 0 and 1 is cleared as coalesced ranges: the norm weights (klab_colpart_reduce and klab_rmsnorm_bwd ADD to them), the
+// relative-position tables, each stack's last layer (128-wide split-K, atomics), anything released per layer, any padding and
+// any parameter without a writer.  T5-small at the default plan: 7.3 M floats (29 MB) of 60.5 M (242 MB).
+static void wgrad_write_plan(klab_engine* e) {
+  klab_engine::WritePlan& w = e->wplan;
+  const klab_t5_cfg& cfg = e->cfg.main;
+  const auto& P = e->P[2];
+  const long d = cfg.d_model, inner = (long)cfg.n_heads * cfg.d_kv, ff = cfg.d_ff;
+  w = klab_engine::WritePlan();
+  w.graph = e->use_graph; w.kv = e->dkv_all != nullptr;
+  w.head_store = wgrad_store_on() && !e->use_graph && e->mi.head >= 0 && P[e->mi.head].grad_off >= 0;
+  if (w.head_store) w.stored.push_back({P[e->mi.head].grad_off, (long)cfg.vocab * d});
+  for (int stk = 0; stk < 2; ++stk) {
+    const bool dec = stk == 1;
+    const std::vector<T5LayerIdx>& L = dec ? e->mi.dec : e->mi.enc;
+    const WgradRelease rel = wgrad_release_plan(e, cfg, (int)L.size(), dec, dec && e->dkv_all != nullptr, e->G[2]);
+    w.store[stk] = rel.store;
+    for (size_t i = 0; i < L.size(); ++i) {
+      if (!rel.store[i]) continue;
+      const T5LayerIdx& l = L[i];  // the products t5_stack_backward queues for a layer (WgradQueue::push checks each against this list)
+      w.stored.push_back({P[l.wo].grad_off, d * ff});
+      w.stored.push_back({P[l.wi].grad_off, (cfg.ffn_gated ? 2 * ff : ff) * d});
+      w.stored.push_back({P[l.o].grad_off, d * inner});
+      w.stored.push_back({P[l.q].grad_off, 3 * inner * d});
+      if (dec) {
+        w.stored.push_back({P[l.co].grad_off, d * inner});
+        w.stored.push_back({P[l.cq].grad_off, inner * d});
+        if (rel.kv_in_queue) w.stored.push_back({e->kvall_g_off + (long)i * 2 * inner * d, 2 * inner * d});
+      }
+    }
+  }
+  std::sort(w.stored.begin(), w.stored.end());
+  w.any_store = !w.stored.empty();
+  for (int seg = 0; seg < 2; ++seg) {
+    const long end = e->seg_off[seg] + e->seg_len[seg];
+    long cur = e->seg_off[seg];
+    for (const auto& s : w.stored) {
+      if (s.first + s.second <= cur || s.first >= end) continue;
+      if (s.first > cur) w.clear[seg].push_back({cur, s.first - cur});
+      cur = s.first + s.second;
+    }
+    if (cur < end) w.clear[seg].push_back({cur, end - cur});
+  }
+  w.valid = true;
+}
+static bool wgrad_write_plan_current(const klab_engine* e) {
+  return e->wplan.valid && e->wplan.graph == e->use_graph && e->wplan.kv == (e->dkv_all != nullptr);
+}
+// clear the plan's ranges of the given segments (and, with_dbias, the two attention-bias accumulators) in one launch
+static int clear_planned(klab_engine* e, int seg_lo, int seg_hi, bool with_dbias, hipStream_t s) {
+  std::vector<float*> zp;
+  std::vector<long> zn;
+  for (int seg = seg_lo; seg <= seg_hi; ++seg)
+    for (const auto& r : e->wplan.clear[seg]) { zp.push_back(e->G[2] + r.first); zn.push_back(r.second); }
+  if (with_dbias) {
+    const long H = e->cfg.main.n_heads;
+    zp.push_back((float*)e->dec.dbias); zn.push_back(H * e->Lt * e->Lt);
+    zp.push_back((float*)e->enc.dbias); zn.push_back(H * e->Le * e->Le);
+  }
+  return klab::zero_ranges(zp.data(), zn.data(), (int)zp.size(), s);
+}
+
 // segment 0: LM head + decoder + shared embedding; 1: encoder; 2: Swin
 static int backward_segment(klab_engine* e, int segment, const float* dloss_dev, void* stream) {
   Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
@@ -2367,16 +2494,25 @@ static int backward_segment(klab_engine* e, int segment, const float* dloss_dev,
     Ctx cs{e, e->side, c.dt, c.es};
     // Clearing 242 MB of gradient slices and the bias accumulators took 36 + 12 us of the main chain (four fills in front of the
     // kernels that need none of them).  They now run on the side stream, beside the LM-head input gradient; off: the old order.
+    // What is cleared is the write plan's ranges (one launch) where some first writer stores; where none does (graph replay,
+    // KLAB_WGRAD_STORE=0) it is the whole segments, with the fills as before.
     static const bool zero_side = klab::env_on("KLAB_ZERO_ON_SIDE");
     const bool zside = zero_side && !e->use_graph;  // (host-side flags below: not for a captured sequence)
+    if (!wgrad_write_plan_current(e)) wgrad_write_plan(e);
+    const bool ranged = e->wplan.any_store;
     if (zside) {
       RC(side_after_main(c));  // behind every earlier reader of the gradient buffers on the caller's stream (optimizer, running sums)
-      RC((int)hipMemsetAsync(Gm + e->seg_off[0], 0, (size_t)e->seg_len[0] * 4, e->side));
-      RC((int)hipMemsetAsync(Gm + e->seg_off[1], 0, (size_t)e->seg_len[1] * 4, e->side));
-      RC((int)hipMemsetAsync(e->dec.dbias, 0, (size_t)cfg.main.n_heads * e->Lt * e->Lt * 4, e->side));
-      RC((int)hipMemsetAsync(e->enc.dbias, 0, (size_t)cfg.main.n_heads * e->Le * e->Le * 4, e->side));
+      if (ranged) RC(clear_planned(e, 0, 1, true, e->side));
+      else {
+        RC((int)hipMemsetAsync(Gm + e->seg_off[0], 0, (size_t)e->seg_len[0] * 4, e->side));
+        RC((int)hipMemsetAsync(Gm + e->seg_off[1], 0, (size_t)e->seg_len[1] * 4, e->side));
+        RC((int)hipMemsetAsync(e->dec.dbias, 0, (size_t)cfg.main.n_heads * e->Lt * e->Lt * 4, e->side));
+        RC((int)hipMemsetAsync(e->enc.dbias, 0, (size_t)cfg.main.n_heads * e->Le * e->Le * 4, e->side));
+      }
       RC((int)hipEventRecord(e->ev_zero, e->side));
       e->seg1_zeroed = e->dbias_zeroed[0] = e->dbias_zeroed[1] = true;
+    } else if (ranged) {
+      RC(clear_planned(e, 0, 0, false, c.s));
     } else {
       RC((int)hipMemsetAsync(Gm + e->seg_off[0], 0, (size_t)e->seg_len[0] * 4, c.s));
     }
@@ -2391,8 +2527,9 @@ static int backward_segment(klab_engine* e, int segment, const float* dloss_dev,
     // longer than one after the other); it then overlaps the decoder's first, latency-bound backward kernels
     RC(side_after_main(c));
     {  // d head [V,d] = dlogits^T @ dec_out  (tied: the first of shared.weight's three contributors; untied: lm_head.weight's only one)
+      // the write plan: it stores (its slice was not cleared, 66 MB not read back); the tile kernel is the same either way
       klab_gemm_args g = G0(cs, V, d, Md, e->logits, V, 0, e->dec.out_t, d, 0, Gm + e->P[2][e->mi.head].grad_off, d, KLAB_F32);
-      g.alpha = alpha; g.alpha_dev = dloss_dev; g.accumulate = 1; g.atomic_ok = 1;
+      g.alpha = alpha; g.alpha_dev = dloss_dev; g.accumulate = e->wplan.head_store ? 0 : 1; g.atomic_ok = 1;
       RC(klab_gemm(&g, cs.ws()));
     }
     float* dh0 = nullptr;
@@ -2414,7 +2551,9 @@ static int backward_segment(klab_engine* e, int segment, const float* dloss_dev,
   }
   if (segment == 1) {
     e->ev_next = 0;
+    if (!wgrad_write_plan_current(e)) { wgrad_write_plan(e); e->seg1_zeroed = false; }  // (whatever was cleared followed another plan)
     if (e->seg1_zeroed) e->seg1_zeroed = false;  // cleared at the entry of segment 0, beside the LM-head input gradient
+    else if (e->wplan.any_store) RC(clear_planned(e, 1, 1, false, c.s));
     else RC((int)hipMemsetAsync(Gm + e->seg_off[1], 0, (size_t)e->seg_len[1] * 4, c.s));
     // the stack consumes dxn as d(final-norm output)
     const int Me = B * e->Le;

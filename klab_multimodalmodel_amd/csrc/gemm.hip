@@ -286,8 +286,10 @@ struct GldsOperand {
   const int nt = kt1 - kt0;                                                             \
   if (nt <= 0) return;
 
-// 4 waves (2 x 2) on a BM x BN tile, any operand layout; ATOMIC: split-K partial sums added to C with float atomics
-template <int BM, int BN, bool AK, bool BKM, bool ATOMIC>
+// 4 waves (2 x 2) on a BM x BN tile, any operand layout; ATOMIC: split-K partial sums added to C with float atomics.
+// MAY_STORE (with ATOMIC; the grouped kernel's store members): p.accumulate == 0 writes the tile with plain stores from the same
+// accumulator layout instead; such a product must not be split along K (p.splits == 1), C is never read.
+template <int BM, int BN, bool AK, bool BKM, bool ATOMIC, bool MAY_STORE = false>
 __device__ __forceinline__ void gemm_glds_body(const GemmP& p, const int bid = blockIdx.x) {
   typedef bf16_t T;
   constexpr int WTM = BM / 2, WTN = BN / 2, MI = WTM / 16, NI = WTN / 16;
@@ -312,6 +314,8 @@ __device__ __forceinline__ void gemm_glds_body(const GemmP& p, const int bid = b
   if (p.alpha_dev) alpha *= p.alpha_dev[0];
   if constexpr (ATOMIC) {
     float* Cf = reinterpret_cast<float*>(p.C);
+    bool store = false;
+    if constexpr (MAY_STORE) store = !p.accumulate;  // workgroup-uniform
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -321,7 +325,9 @@ __device__ __forceinline__ void gemm_glds_body(const GemmP& p, const int bid = b
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int m = bm0 + wm + i * 16 + (lane >> 4) * 4 + r;
-          if (m < p.M) atomicAdd(Cf + (long)m * p.ldc + n, acc[i][j][r] * alpha);
+          if (m >= p.M) continue;
+          if (store) Cf[(long)m * p.ldc + n] = acc[i][j][r] * alpha;
+          else atomicAdd(Cf + (long)m * p.ldc + n, acc[i][j][r] * alpha);
         }
       }
   } else {
@@ -364,7 +370,10 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(GemmP p) { gemm_glds_bod
 // Grouped launch: up to 8 independent split-K weight-gradient GEMMs (both operands m-major, f32 atomic accumulation) in ONE
 // grid.  A layer's 4-7 weight gradients are 2-9 GFLOP each: launched one by one on the side stream each of them under-fills
 // the chip and pays its own launch; together they are one ~30 GFLOP kernel whose small members fill the big ones' tails.
-struct GroupEntry { const void* A; long lda; const void* B; long ldb; float* C; long ldc; int M, N, K, splits, start; float alpha; };
+// A member with accumulate == 0 (a store member) is never split along K (splits == 1) and writes its tiles with plain stores: C
+// needs no clearing first.  A computed -0.0 then stays -0.0 where 0 + -0.0 gave +0.0; nothing downstream tells them apart (Adam
+// squares or scales the value, torch.equal takes them as equal).
+struct GroupEntry { const void* A; long lda; const void* B; long ldb; float* C; long ldc; int M, N, K, splits, start; float alpha; int accumulate; };
 struct GroupP { GroupEntry e[8]; int n; };
 template <int BN>
 __global__ __launch_bounds__(256) void gemm_glds_grouped_tn_kernel(GroupP g) {
@@ -376,13 +385,13 @@ __global__ __launch_bounds__(256) void gemm_glds_grouped_tn_kernel(GroupP g) {
   GemmP p;
   p.M = e.M; p.N = e.N; p.K = e.K;
   p.A = e.A; p.lda = e.lda; p.a_kmajor = 0; p.B = e.B; p.ldb = e.ldb; p.b_kmajor = 0;
-  p.C = e.C; p.ldc = e.ldc; p.c_f32 = 1; p.accumulate = 1;
+  p.C = e.C; p.ldc = e.ldc; p.c_f32 = 1; p.accumulate = e.accumulate;
   p.alpha = e.alpha; p.alpha_dev = nullptr; p.bias = nullptr; p.act = 0;
   p.aux = nullptr; p.ldaux = 0; p.aux_mode = 0; p.aux_scale = 1.f; p.residual = nullptr; p.ldr = 0; p.r_f32 = 1;
-  p.drop_p = 0.f; p.seed = nullptr; p.tag = 0; p.splits = e.splits; p.epi = 0;
+  p.drop_p = 0.f; p.seed = nullptr; p.tag = 0; p.splits = e.accumulate ? e.splits : 1; p.epi = 0;
   // (measured: members whose K is not split adding their tile with staged, coalesced read-modify-writes instead of 16 K float
   // atomics per tile -- 0.082 vs 0.079 ms per launch, no change in the step: the atomics are not what bounds this kernel)
-  gemm_glds_body<128, BN, false, false, true>(p, (int)blockIdx.x - e.start);
+  gemm_glds_body<128, BN, false, false, true, true>(p, (int)blockIdx.x - e.start);
 }
 
 // One workgroup = 4 waves (2x2) computing a BM x BN tile over k-tiles [kt0, kt1).
@@ -877,7 +886,7 @@ extern "C" int klab_gemm_grouped_tiles(const klab_gemm_args* list, int n, int la
   g.n = 0;
   int blocks = 0;
   auto fits = [&](const klab_gemm_args* a) {
-    return a->dtype == KLAB_BF16 && !a->a_kmajor && !a->b_kmajor && a->c_dtype == KLAB_F32 && a->accumulate && a->atomic_ok &&
+    return a->dtype == KLAB_BF16 && !a->a_kmajor && !a->b_kmajor && a->c_dtype == KLAB_F32 && a->atomic_ok &&
            !a->bias && !a->act && !a->aux && !a->residual && a->drop_p == 0.f && !a->alpha_dev && a->name_tag == 0 && a->M >= 128 &&
            a->N >= 64 && (a->K % 32) == 0 && a->K >= 512 && !(a->M & 7) && !(a->N & 7) && !(a->lda & 7) && !(a->ldb & 7) &&
            !((uintptr_t)a->A & 15) && !((uintptr_t)a->B & 15) && !((uintptr_t)a->C & 15);
@@ -920,10 +929,10 @@ extern "C" int klab_gemm_grouped_tiles(const klab_gemm_args* list, int n, int la
     long sp = (nt + per_wg / 2) / per_wg;
     if (sp > nt / 16) sp = nt / 16;
     if (sp > 16) sp = 16;
-    if (sp < 1) sp = 1;
+    if (sp < 1 || !a->accumulate) sp = 1;  // a store member: one workgroup per tile over the whole contraction
     GroupEntry& e = g.e[g.n];
     e.A = a->A; e.lda = a->lda; e.B = a->B; e.ldb = a->ldb; e.C = (float*)a->C; e.ldc = a->ldc;
-    e.M = a->M; e.N = a->N; e.K = a->K; e.splits = (int)sp; e.start = blocks; e.alpha = a->alpha;
+    e.M = a->M; e.N = a->N; e.K = a->K; e.splits = (int)sp; e.start = blocks; e.alpha = a->alpha; e.accumulate = a->accumulate ? 1 : 0;
     blocks += (int)(t * sp);
     if (++g.n == 8) { const int rc = flush(); if (rc) return rc; }
   }

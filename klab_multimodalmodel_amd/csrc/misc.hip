@@ -513,6 +513,39 @@ static inline unsigned stream_grid(long work_items) {
   return (unsigned)g;
 }
 
+// Clear up to ZERO_RANGES_MAX f32 ranges in ONE launch (common.h: zero_ranges): blockIdx.y picks the range, the blocks of a row
+// stride over it with 16-byte stores; the elements in front of the first and behind the last aligned vector are stored singly.
+struct ZeroRangesP { float* p[ZERO_RANGES_MAX]; long n[ZERO_RANGES_MAX]; };
+__global__ __launch_bounds__(256) void zero_ranges_kernel(ZeroRangesP r) {
+  float* p = r.p[blockIdx.y];
+  const long n = r.n[blockIdx.y];
+  long head = (long)((16 - ((uintptr_t)p & 15)) & 15) / 4;  // (a float pointer: 4-byte aligned)
+  if (head > n) head = n;
+  const long n4 = (n - head) / 4;
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, step = (long)gridDim.x * blockDim.x;
+  f32x4* p4 = reinterpret_cast<f32x4*>(p + head);
+  for (long g = tid; g < n4; g += step) p4[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (tid < head) p[tid] = 0.f;
+  const long tail0 = head + n4 * 4;
+  if (tid < n - tail0) p[tail0 + tid] = 0.f;
+}
+int zero_ranges(float* const* ptrs, const long* counts, int n, hipStream_t s) {
+  for (int i0 = 0; i0 < n; i0 += ZERO_RANGES_MAX) {
+    ZeroRangesP r;
+    int m = 0;
+    long longest = 0;
+    for (int i = i0; i < n && m < ZERO_RANGES_MAX; ++i) {
+      if (!ptrs[i] || counts[i] <= 0) continue;
+      r.p[m] = ptrs[i]; r.n[m] = counts[i]; ++m;
+      if (counts[i] > longest) longest = counts[i];
+    }
+    if (!m) continue;
+    hipLaunchKernelGGL(zero_ranges_kernel, dim3(stream_grid(longest / 4 + 1), (unsigned)m), dim3(256), 0, s, r);
+    KLAB_LAUNCH_CHECK();
+  }
+  return KLAB_OK;
+}
+
 }  // namespace klab
 
 using namespace klab;

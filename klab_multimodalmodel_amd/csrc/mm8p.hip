@@ -448,7 +448,10 @@ __global__ __launch_bounds__(512) void mm8p_kernel(GemmP p) { mm8p_body<AK, BKM,
 // weight gradients of a T5 layer (HF/t5 autograd of :83-94, 206-209).  One 256 x 256 tile over the WHOLE contraction per
 // workgroup: no split-K, no atomics, half the operand traffic of the 128 x 128 split-K form (gemm.hip's grouped kernel), and a
 // layer's gradients occupy ~50 CUs instead of all 256 -- they run on a side stream beside the activation-gradient chain.
-struct Group8Entry { const void* A; long lda; const void* B; long ldb; float* C; long ldc; int M, N, K, start; float alpha; };
+// accumulate == 0 (a store member): the copy-out writes the product with the same coalesced 16-byte row stores and never reads C,
+// so C needs no clearing first and nothing outside [M, N] is touched.  A computed -0.0 then stays -0.0, where 0 + -0.0 gave +0.0:
+// nothing downstream tells them apart (Adam squares or scales the value, torch.equal takes them as equal).
+struct Group8Entry { const void* A; long lda; const void* B; long ldb; float* C; long ldc; int M, N, K, start; float alpha; int accumulate; };
 constexpr int GROUP_MAX = 32;  // (several layers' products in one grid: engine.cpp's grouped weight gradients)
 struct Group8P { Group8Entry e[GROUP_MAX]; int n; };
 __global__ __launch_bounds__(512) void mm8p_grouped_tn_kernel(Group8P g) {
@@ -461,7 +464,7 @@ __global__ __launch_bounds__(512) void mm8p_grouped_tn_kernel(Group8P g) {
   p.M = e.M; p.N = e.N; p.K = e.K;
   p.A = e.A; p.lda = e.lda; p.a_kmajor = 0;
   p.B = e.B; p.ldb = e.ldb; p.b_kmajor = 0;
-  p.C = e.C; p.ldc = e.ldc; p.c_f32 = 1; p.accumulate = 1;
+  p.C = e.C; p.ldc = e.ldc; p.c_f32 = 1; p.accumulate = e.accumulate;
   p.alpha = e.alpha; p.alpha_dev = nullptr; p.bias = nullptr; p.act = 0;
   p.aux = nullptr; p.ldaux = 0; p.aux_mode = 0; p.aux_scale = 1.f;
   p.residual = nullptr; p.ldr = 0; p.r_f32 = 1;
@@ -482,14 +485,14 @@ int mm8p_grouped_try(const klab_gemm_args* list, int n, bool large_tiles, hipStr
   int blocks = 0;
   for (int i = 0; i < n; ++i) {
     const klab_gemm_args* a = &list[i];
-    const bool ok = a->dtype == KLAB_BF16 && !a->a_kmajor && !a->b_kmajor && a->c_dtype == KLAB_F32 && a->accumulate && !a->bias && !a->act &&
+    const bool ok = a->dtype == KLAB_BF16 && !a->a_kmajor && !a->b_kmajor && a->c_dtype == KLAB_F32 && !a->bias && !a->act &&
                     !a->aux && !a->residual && a->drop_p == 0.f && !a->alpha_dev && a->M >= 128 && a->N >= 128 && (a->K % BK) == 0 &&
                     a->K >= 1024 && !(a->M & 7) && !(a->N & 7) && !(a->lda & 7) && !(a->ldb & 7) && !(a->ldc & 3) &&
                     !((uintptr_t)a->A & 15) && !((uintptr_t)a->B & 15) && !((uintptr_t)a->C & 15);
     if (!ok) return KLAB_ERR_UNSUPPORTED;
     Group8Entry& e = g.e[g.n++];
     e.A = a->A; e.lda = a->lda; e.B = a->B; e.ldb = a->ldb; e.C = (float*)a->C; e.ldc = a->ldc;
-    e.M = a->M; e.N = a->N; e.K = a->K; e.start = blocks; e.alpha = a->alpha;
+    e.M = a->M; e.N = a->N; e.K = a->K; e.start = blocks; e.alpha = a->alpha; e.accumulate = a->accumulate ? 1 : 0;
     blocks += ((a->M + BM - 1) / BM) * ((a->N + BN - 1) / BN);
   }
   const size_t epi_bytes = (size_t)128 * SLAB_PITCH;
