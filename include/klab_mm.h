@@ -502,6 +502,18 @@ int klab_adafactor_step(const void* desc_dev, int ndesc, long state_elems, long 
                         float* scalars, float* scratch, void* arena, int dtype, float beta2t, float one_minus_beta2t, float eps0, float eps1,
                         float rel_step, float clip_threshold, float beta1, float one_minus_beta1, float weight_decay, int scale_parameter,
                         void* stream);
+/* Gradient-norm clipping (torch.nn.utils.clip_grad_norm_) over ANY set of fp32 gradient tensors of one device.  table = device
+ * array of {float* ptr; long n}, one entry per tensor, n >= 1, ptr 4-byte aligned (16-byte aligned tensors are read and written
+ * in 16-byte vectors).  Tensor i owns ceil(n_i / chunk) consecutive fp64 partials of `parts`, chunk = klab_grad_norm_chunk().
+ * klab_grad_norm (kind 0: L2, squares and sums in fp64; kind 1: max |g|, NaN kept) is two launches: one partial per chunk, then
+ * one workgroup that writes norms[i] for i < nt and the total norms[nt] (nt = 0: a total of 0).  No floating-point atomics, a
+ * fixed order of summation: the same input gives the same bits on every run.  nparts < nt is a bad argument; the exact count
+ * is known to the device only, which never writes past parts[nparts - 1] and gives NaN for a tensor whose partials are cut off.
+ * klab_grad_clip is one launch: coef_dev[0] = min(max_norm / (*total_dev + 1e-6f), 1) with NaN kept (torch's clamp), and every
+ * element times coef in place -- unless coef >= 1, when nothing is read or written. */
+int klab_grad_norm_chunk(void);
+int klab_grad_norm(const void* table_dev, int nt, int kind, double* parts, long nparts, float* norms, void* stream);
+int klab_grad_clip(const void* table_dev, int nt, const float* total_dev, float max_norm, float* coef_dev, void* stream);
 /* decoding over a K/V cache: one query row per (row, head) of R rows against cached keys / values (element strides; bias_row
  * [H, bias_ld] or NULL; scores are unscaled, HF/t5:196-197).  Key j of query row r is read at row  s*kv_bstride + j*ldk  (element
  * offsets from k / v) where s = kv_slot[r*slot_ld + j] when kv_slot (int32 [R, slot_ld]) is given (beam search: the beams' key-slot

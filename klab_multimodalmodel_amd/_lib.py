@@ -115,6 +115,9 @@ SIGNATURES = {
     "klab_adam_step_range": [vp, i32, i64, i64, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, f32, vp],
     "klab_adafactor_plan": [i32, vp, vp, vp, vp, vp],
     "klab_adafactor_step": [vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, f32, f32, f32, i32, vp],
+    "klab_grad_norm_chunk": [],
+    "klab_grad_norm": [vp, i32, i32, vp, i64, vp, vp],
+    "klab_grad_clip": [vp, i32, vp, f32, vp, vp],
     "klab_layernorm_fwd": [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, f32, i32, i32, i32, f32, vp, u32, vp],
     "klab_layernorm_bwd": [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, u32, vp],
     "klab_rmsnorm_fwd_q8": [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, u32, vp],

@@ -350,6 +350,12 @@ class MyModel(nn.Module):
     def flat_grads(self, model="main"):
         return self._flat.get(model)
 
+    def grad_norms(self, norm_type=2.0):
+        """(names, norms) of the trainable parameters' gradients: HF state-dict names and the fp32 device tensor of their norms with
+        the total norm last, from one multi-tensor launch and without a host read (optim.grad_norms)"""
+        from ..optim import grad_norms
+        return grad_norms(self, norm_type)
+
     # ---- the reference surface -----------------------------------------------------------------
     def forward(self, images, source_encoding, target_encoding=None, return_loss=True):
         if self._pending_opt_stream is not None:  # an in-backward optimizer update nobody joined through step()

@@ -539,6 +539,58 @@ def adam_step(desc, total4, grads, m, v, arena, *, lr, beta1=0.9, beta2=0.999, e
                 "klab_adam_step_range")
 
 
+def grad_norm_chunk():
+    """elements per fp64 partial of grad_norm (a compile-time constant of the library; no GPU needed)"""
+    return int(L.load().klab_grad_norm_chunk())
+
+
+def grad_norm_plan(numels, chunk=None):
+    """host side of the gradient table: tensor i of `numels` owns partials [first[i], first[i] + ceil(numels[i] / chunk));
+    returns (first, nparts)"""
+    chunk = grad_norm_chunk() if chunk is None else int(chunk)
+    first, run = [], 0
+    for n in numels:
+        n = int(n)
+        if n < 1:
+            raise ValueError("klab: a gradient tensor of the table has no elements")
+        first.append(run)
+        run += (n + chunk - 1) // chunk
+    return first, run
+
+
+def grad_table(tensors):
+    """the device table of grad_norm / grad_clip for fp32 contiguous tensors of one device: desc int64 [n, 2] rows of
+    {pointer, numel}; returns (desc, nparts)"""
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda for t in tensors)
+    _first, nparts = grad_norm_plan([t.numel() for t in tensors])
+    rows = [[t.data_ptr(), t.numel()] for t in tensors]
+    dev = tensors[0].device if tensors else "cuda"
+    host = torch.tensor(rows, dtype=torch.int64).reshape(-1, 2).pin_memory()  # pinned: the upload does not synchronise
+    return host.to(dev, non_blocking=True), nparts
+
+
+def grad_norm(desc, parts, norms, kind=0, nparts=None):
+    """norms[i] = the L2 norm (kind 0) or max |g| (kind 1) of tensor i of the table, norms[n] = that of all of them (klab_grad_norm);
+    parts: float64 scratch of at least `nparts` elements (grad_table's count; checked when given), norms: float32 [>= n + 1]"""
+    lib = L.load()
+    assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 2 and desc.is_contiguous()
+    assert parts.dtype == torch.float64 and norms.dtype == torch.float32 and norms.numel() >= desc.shape[0] + 1
+    if nparts is not None and parts.numel() < nparts:
+        raise ValueError(f"klab: grad_norm needs {nparts} partials, the buffer holds {parts.numel()}")
+    L.check(lib.klab_grad_norm(desc.data_ptr(), desc.shape[0], int(kind), parts.data_ptr(), parts.numel(), norms.data_ptr(), L.stream_ptr()),
+            "klab_grad_norm")
+
+
+def grad_clip(desc, total, max_norm, coef):
+    """coef[0] = min(max_norm / (total[0] + 1e-6), 1) (NaN kept) and every tensor of the table times coef in place, or no store at
+    all when coef >= 1 (klab_grad_clip); total, coef: float32 device tensors of one element, e.g. views of grad_norm's `norms`"""
+    lib = L.load()
+    assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 2 and desc.is_contiguous()
+    assert total.dtype == coef.dtype == torch.float32
+    L.check(lib.klab_grad_clip(desc.data_ptr(), desc.shape[0], total.data_ptr(), float(max_norm), coef.data_ptr(), L.stream_ptr()),
+            "klab_grad_clip")
+
+
 def image_preprocess(src_u8, desc, n, max_h, max_w, pixel_values, *, mid=256, out=224, filter_a=3, filter_b=2,
                      rescale=1.0 / 255 / 255, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)):
     """klab_image_preprocess: src_u8 device uint8 bytes, desc device int64 [n, 2] rows of {offset, height | width << 32}

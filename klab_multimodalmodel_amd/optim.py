@@ -1,4 +1,5 @@
-"""Fused optimizers for the native MyModel: Adam and Adafactor (`FusedAdafactor`, at the end of the file).
+"""Fused optimizers for the native MyModel: Adam and Adafactor (`FusedAdafactor`), and on-device gradient-norm
+clipping (`clip_grad_norm_`, `grad_norms`, at the end of the file).
 
 Drop-in for the reference's `torch.optim.Adam(model.module.transformer.parameters(), lr=args.lr)` (ref/train.py:28): same
 constructor arguments, same update rule (no amsgrad, L2 weight decay), `param_groups` / LR schedulers / `zero_grad` /
@@ -479,3 +480,154 @@ class FusedAdafactor(Optimizer):
         super().load_state_dict(state_dict)
         self._flat_live = False
         self._steps = 0
+
+
+# ---- gradient-norm clipping (csrc/grad_clip.hip) ------------------------------------------------------------------------------------
+_CLIP_CACHE = {}  # (device, ((data_ptr, numel), ...)) -> _ClipState, for gradients no klab model owns
+_CLIP_CACHE_MAX = 8
+
+
+class _ClipState:
+    """the device table of one set of gradient tensors, its fp64 partials and the result words: norms[0 .. nt - 1], the total at
+    [nt], the clip coefficient at [nt + 1]"""
+
+    def __init__(self, grads):
+        from . import ops
+        self.nt = len(grads)
+        self.desc, self.nparts = ops.grad_table(grads)
+        dev = grads[0].device
+        self.parts = torch.empty(self.nparts, dtype=torch.float64, device=dev)
+        self.res = torch.zeros(self.nt + 2, dtype=torch.float32, device=dev)
+
+
+def _clip_owner(params):
+    """the one klab MyModel that owns some of `params` (its trainable T5 carries `_klab_owner`), else None"""
+    owner = None
+    for p in params:
+        ref = getattr(p, "_klab_owner", None)
+        m = ref() if ref is not None else None
+        if m is not None:
+            if owner is not None and m is not owner:
+                return None
+            owner = m
+    return owner
+
+
+def _clip_native(params, grads, norm_type):
+    """(state, owner) when the kernels apply to `grads` (the gradients of `params` that are not None), else (None, why)"""
+    if norm_type != 2.0 and norm_type != math.inf:
+        return None, "norm_type is neither 2 nor inf"
+    dev = grads[0].device
+    if dev.type != "cuda":
+        return None, "gradients are not on a GPU"
+    key = []
+    for g in grads:
+        if g.dtype != torch.float32 or g.device != dev or g.layout != torch.strided or not g.is_contiguous() or g.numel() == 0:
+            return None, "a gradient is not a contiguous fp32 tensor on the one device"
+        key.append((g.data_ptr(), g.numel()))
+    key = tuple(key)
+    if len({k[0] for k in key}) != len(key):
+        return None, "a gradient tensor is listed twice"
+    from . import _lib
+    try:
+        _lib.load()
+    except (_lib.KlabError, OSError, AttributeError):
+        return None, "the library does not load"
+    owner = _clip_owner(params)
+    if owner is not None:
+        # kept on the model until it is re-bound: `_views` is a new list after every rebind (`_apply`, `_engine_for`)
+        owner._grad_targets()
+        cache = getattr(owner, "_clip_cache", None)
+        if cache is None or cache[0] is not owner._views:
+            cache = owner._clip_cache = (owner._views, {})
+        states = cache[1]
+    else:
+        states = _CLIP_CACHE
+    st = states.get((dev, key))
+    if st is None:
+        if len(states) >= _CLIP_CACHE_MAX:
+            states.clear()
+        with torch.cuda.device(dev):
+            st = states[(dev, key)] = _ClipState(grads)
+    return st, owner
+
+
+def _clip_join(owner, dev):
+    """order the current stream behind everything that still writes `owner`'s gradients or weights"""
+    opt = owner._optimizer_in_backward() if owner._optimizer_in_backward is not None else None
+    if opt is not None and opt._bw_token is not None:
+        raise RuntimeError("clip_grad_norm_ needs the whole gradient before any update, but FusedAdam(step_in_backward=True) has "
+                           "already updated segment 0 underneath this backward(); construct the optimizer with step_in_backward=False")
+    red = owner._pending_reduce
+    if red is not None:  # klab DDP(overlap_optimizer=True): the last all-reduces are not joined yet
+        owner._pending_reduce = None
+        red.finish()
+    side = owner._pending_opt_stream
+    if side is not None:
+        torch.cuda.current_stream(dev).wait_stream(side)
+        owner._pending_opt_stream = None
+
+
+def _clip_norms(st, owner, norm_type):
+    from . import ops
+    dev = st.res.device
+    if owner is not None:
+        _clip_join(owner, dev)
+    with torch.cuda.device(dev):
+        ops.grad_norm(st.desc, st.parts, st.res, kind=0 if norm_type == 2.0 else 1, nparts=st.nparts)
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """`torch.nn.utils.clip_grad_norm_` with the same signature, return value and messages.  For contiguous fp32 gradients on one
+    GPU and `norm_type` 2 or inf it is three launches whatever the number of tensors (csrc/grad_clip.hip): the norm in one read of
+    the gradients, and a scale pass that stores nothing unless the gradients are really clipped.  No host read (unless
+    `error_if_nonfinite`), the gradients stay where they are (FusedAdam / FusedAdafactor keep their fused paths).  The total is
+    accumulated in fp64: finite where torch's fp32 squares overflow, and the same bits on every run.  In every other case
+    torch's function is called with the same arguments."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    else:
+        parameters = list(parameters)  # (may be a generator, and torch's function would need it again)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    max_norm, norm_type = float(max_norm), float(norm_type)
+    if len(grads) == 0:
+        return torch.tensor(0.0)
+    st, owner = _clip_native(parameters, grads, norm_type)
+    if st is None:
+        return torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type, error_if_nonfinite, foreach)
+    from . import ops
+    _clip_norms(st, owner, norm_type)
+    total = st.res[st.nt]
+    if error_if_nonfinite and not bool(torch.isfinite(total)):
+        raise RuntimeError(f"The total norm of order {norm_type} for gradients from `parameters` is non-finite, so it cannot be "
+                           "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                           "`error_if_nonfinite=False`")
+    with torch.cuda.device(st.res.device):
+        ops.grad_clip(st.desc, st.res[st.nt:st.nt + 1], max_norm, st.res[st.nt + 1:st.nt + 2])
+    return total.clone()  # the result words are written again by the next call
+
+
+@torch.no_grad()
+def grad_norms(parameters_or_model, norm_type=2.0):
+    """(names, norms): the norm of every gradient and, last, of all of them, as the fp32 device tensor [nt + 1] that ONE
+    klab_grad_norm call writes -- the per-parameter curve of a training log at the cost of the clipping's own norm pass, with no
+    host read.  `names` are the HF state-dict names (`transformer.…`, `image_model.…`) for a klab MyModel, else the indices into
+    the given parameters.  Parameters without a gradient are left out.  NotImplementedError where the kernels do not apply
+    (see clip_grad_norm_)."""
+    if isinstance(parameters_or_model, torch.nn.Module):
+        named = [(n, p) for n, p in parameters_or_model.named_parameters() if p.requires_grad]
+    elif isinstance(parameters_or_model, torch.Tensor):
+        named = [(0, parameters_or_model)]
+    else:
+        named = list(enumerate(parameters_or_model))
+    named = [(n, p) for n, p in named if p.grad is not None]
+    names, params = [n for n, _p in named], [p for _n, p in named]
+    norm_type = float(norm_type)
+    if not params:
+        raise NotImplementedError("grad_norms: no parameter has a gradient")
+    st, owner = _clip_native(params, [p.grad for p in params], norm_type)
+    if st is None:
+        raise NotImplementedError(f"grad_norms needs the native path: {owner}")
+    _clip_norms(st, owner, norm_type)
+    return names, st.res[:st.nt + 1].clone()
