@@ -471,6 +471,31 @@ int klab_engine_adam_step_segment(klab_engine* e, int segment, float* m, float* 
 int klab_adam_step_range(const void* desc_dev, int ndesc, long begin4, long end4, const float* grads, float* m, float* v, void* arena,
                          int dtype, float lr, float beta1, float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
                          void* stream);
+/* AdamW (torch.optim.AdamW's single-tensor rule, decoupled decay, no amsgrad / maximize) over the same descriptor table, with the
+ * hyper-parameters of up to KLAB_ADAMW_MAX_GROUPS parameter groups in ONE launch (csrc/adamw.hip).  group_of_dev: device array of
+ * ndesc ints in table order, the group (0 <= id < ngroups) of each tensor; it belongs to the caller.  groups: HOST array, read
+ * before the call returns and passed to the kernel by value -- no copy to the device, nothing read back.  bias_corr{1,2} =
+ * 1 - beta^step > 0.  Per element, in f32:
+ *   p' = p * decay;  m' = m + (1 - beta1) (g - m);  v' = beta2 v + (1 - beta2) g^2;
+ *   p'' = p' - step * (m' / (sqrt(v') * inv_sqrt_bc2 + eps));  arena copy = (dtype) p''
+ * with  decay = (float)(1.0 - (double)lr * (double)weight_decay)  and  step = (float)((double)lr / bias_corr1)  formed on the host
+ * from the f32 fields below, inv_sqrt_bc2 = 1.f / sqrtf(bias_corr2).  lr = 0 leaves p bit-identical.  [begin4, end4): vec4 range of
+ * the table's prefix space, as klab_adam_step_range.  ngroups < 1 or > KLAB_ADAMW_MAX_GROUPS: KLAB_ERR_UNSUPPORTED, nothing is
+ * launched. */
+#define KLAB_ADAMW_MAX_GROUPS 16
+typedef struct { float lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2; } klab_adamw_group;
+int klab_adamw_step_range(const void* desc_dev, int ndesc, const int* group_of_dev, const klab_adamw_group* groups /*host*/, int ngroups,
+                          long begin4, long end4, const float* grads, float* m, float* v, void* arena, int dtype, void* stream);
+/* table order of the fused optimizers (klab_engine_adam_step, klab_engine_adamw_step): param_ptrs[i] = the master tensor of table
+ * entry i, *n_segment0 = how many leading entries belong to backward segment 0.  Returns the number of entries (> 0), or
+ * KLAB_ERR_BADARG when max_n is smaller, KLAB_ERR_UNSUPPORTED when the table is unusable.  Host data only: no synchronisation. */
+int klab_engine_adam_layout(klab_engine* e, int max_n, long* param_ptrs, int* n_segment0);
+/* klab_adamw_step_range on the engine's table, gradients and weight arena: segment -1 = every tensor, 0 / 1 = the tensors of that
+ * backward segment (both = one full step).  Refreshes the compute-dtype copies like klab_engine_adam_step.  The group table is
+ * the caller's and survives a re-bind to another batch shape (same tensors, same order).  KLAB_ERR_UNSUPPORTED when the Adam
+ * table is unusable. */
+int klab_engine_adamw_step(klab_engine* e, int segment /* -1 both, 0, 1 */, float* m, float* v, const int* group_of_dev,
+                           const klab_adamw_group* groups, int ngroups, void* stream);
 /* Adafactor (the rule of transformers.optimization.Adafactor) for ALL parameters of the trainable T5 in four launches, whatever
  * the number of tensors: statistics (row / column sums of g^2 + eps0, sum p^2), their reduction (EMA into R / C, mean R, RMS(p)),
  * sum u^2, apply.  Tensors with >= 2 dims are factored (rows = product of all dims but the last), 1-D tensors keep a full second

@@ -91,6 +91,23 @@ class LogitsProcCfg(C.Structure):  # klab_logits_proc_cfg
                 ("n_bad", i32), ("bad_off", C.POINTER(i32)), ("bad_tok", C.POINTER(i32))]
 
 
+class AdamWGroup(C.Structure):  # klab_adamw_group
+    _fields_ = [("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("bias_corr1", f32), ("bias_corr2", f32)]
+
+
+ADAMW_MAX_GROUPS = 16  # KLAB_ADAMW_MAX_GROUPS
+
+
+def adamw_groups(groups):
+    """host array of klab_adamw_group from dicts / tuples of (lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2)"""
+    keys = [f for f, _t in AdamWGroup._fields_]
+    arr = (AdamWGroup * max(len(groups), 1))()
+    for i, g in enumerate(groups):
+        vals = [g[k] for k in keys] if isinstance(g, dict) else list(g)
+        arr[i] = AdamWGroup(*[float(x) for x in vals])
+    return arr
+
+
 GEN_PICK, GEN_SAMPLE, GEN_BEAM, GEN_FORCE = 0, 1, 2, 3
 
 
@@ -113,6 +130,7 @@ SIGNATURES = {
     "klab_colpart_reduce": [vp, i64, i32, i32, vp, i32, vp],
     "klab_adam_step": [vp, i32, i64, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, f32, vp],
     "klab_adam_step_range": [vp, i32, i64, i64, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, f32, vp],
+    "klab_adamw_step_range": [vp, i32, vp, C.POINTER(AdamWGroup), i32, i64, i64, vp, vp, vp, vp, i32, vp],
     "klab_adafactor_plan": [i32, vp, vp, vp, vp, vp],
     "klab_adafactor_step": [vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, f32, f32, f32, i32, vp],
     "klab_grad_norm_chunk": [],

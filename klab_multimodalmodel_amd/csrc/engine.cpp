@@ -155,6 +155,7 @@ struct klab_engine {
   const void* q8_src[2] = {nullptr, nullptr}; int q8_rows[2] = {0, 0}, q8_k[2] = {0, 0};
   void* cast_desc = nullptr; int n_cast = 0; long cast_total4 = 0;      // trainable GEMM weights (cast every forward)
   void* adam_desc = nullptr; int n_adam = 0; long adam_total4 = 0, adam_split4 = 0;
+  std::vector<long> adam_ptrs; int n_adam_seg0 = 0;  // host copy of the table's order (klab_engine_adam_layout)
   void* af_desc = nullptr; int n_af = 0; long af_totals[4] = {0, 0, 0, 0};  // Adafactor: state elems, tiles, scratch elems, scalar elems
   // RMS-norm weight gradients of a stack: per-workgroup partials of every norm, folded by one reduction per stack
   float* rms_part = nullptr; long rms_part_stride = 0; float** rms_dst_dev[2] = {nullptr, nullptr}; int rms_ncalls[2] = {0, 0};
@@ -1576,7 +1577,7 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
     // tensors of backward segment 0 first, then segment 1: a prefix range of the table = one segment (the optimizer may
     // update segment 0 while segment 1's gradient all-reduce is still in flight, klab_engine_adam_step_segment)
     for (int seg = 0; seg < 2 && ok; ++seg) {
-      if (seg == 1) e->adam_split4 = pre;
+      if (seg == 1) { e->adam_split4 = pre; e->n_adam_seg0 = n; }
       for (size_t i = 0; i < e->P[2].size(); ++i) {
         const ParamInfo& p = e->P[2][i];
         if (p.grad_off < 0 || (p.grad_off >= e->seg_off[1]) != (seg == 1)) continue;
@@ -1586,6 +1587,8 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
       }
     }
     e->n_adam = ok ? n : 0; e->adam_total4 = pre;
+    e->adam_ptrs.clear();
+    for (int k = 0; k < e->n_adam; ++k) e->adam_ptrs.push_back(d[(size_t)k * 4]);
     if (e->n_adam) {  // (the synchronise is shared with the Adafactor table below: adam_tab lives until then)
       hipError_t er = hipMemcpyAsync(e->adam_desc, d.data(), d.size() * sizeof(long), hipMemcpyHostToDevice, hs);
       if (er != hipSuccess) return (int)er;
@@ -1827,6 +1830,23 @@ extern "C" int klab_engine_adam_step_segment(klab_engine* e, int segment, float*
   const long b4 = segment == 0 ? 0 : e->adam_split4, e4 = segment == 0 ? e->adam_split4 : e->adam_total4;
   return klab_adam_step_range(e->adam_desc, e->n_adam, b4, e4, e->G[2], m, v, e->warena, e->cfg.dtype, lr, beta1, beta2, eps, weight_decay,
                               bias_corr1, bias_corr2, stream);
+}
+
+extern "C" int klab_engine_adam_layout(klab_engine* e, int max_n, long* param_ptrs, int* n_segment0) {
+  if (!e || !e->bound || !param_ptrs || !n_segment0) return KLAB_ERR_BADARG;
+  if (!e->n_adam) return KLAB_ERR_UNSUPPORTED;
+  if (max_n < e->n_adam) return KLAB_ERR_BADARG;
+  for (int k = 0; k < e->n_adam; ++k) param_ptrs[k] = e->adam_ptrs[k];
+  *n_segment0 = e->n_adam_seg0;
+  return e->n_adam;
+}
+
+extern "C" int klab_engine_adamw_step(klab_engine* e, int segment, float* m, float* v, const int* group_of_dev, const klab_adamw_group* groups,
+                                      int ngroups, void* stream) {
+  if (!e || !e->bound || !m || !v || !e->G[2] || segment < -1 || segment > 1) return KLAB_ERR_BADARG;
+  if (!e->n_adam) return KLAB_ERR_UNSUPPORTED;
+  const long b4 = segment == 1 ? e->adam_split4 : 0, e4 = segment == 0 ? e->adam_split4 : e->adam_total4;
+  return klab_adamw_step_range(e->adam_desc, e->n_adam, group_of_dev, groups, ngroups, b4, e4, e->G[2], m, v, e->warena, e->cfg.dtype, stream);
 }
 
 // Device-side dropout RNG of the binding: st[1] = base seed, st[2] = number of forwards since it was (re)seeded; every forward

@@ -137,6 +137,8 @@ ENGINE_SIGS = {
                                C.c_float, C.c_void_p], C.c_int),
     "klab_engine_adam_step_segment": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.c_float, C.c_float, C.c_void_p], C.c_int),
+    "klab_engine_adam_layout": ([C.c_void_p, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_int)], C.c_int),
+    "klab_engine_adamw_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(L.AdamWGroup), C.c_int, C.c_void_p], C.c_int),
     "klab_engine_adafactor_state_elems": ([C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)], C.c_int),
     "klab_engine_adafactor_layout": ([C.c_void_p, C.c_int, C.POINTER(C.c_long)], C.c_int),
     "klab_engine_adafactor_step": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_float] * 9 + [C.c_int, C.c_void_p],
@@ -523,6 +525,23 @@ class Engine:
             return
         L.check(self._lib.klab_engine_adam_step(self._h, m.data_ptr(), v.data_ptr(), lr, beta1, beta2, eps, weight_decay, bias_corr1,
                                                 bias_corr2, L.stream_ptr()), "klab_engine_adam_step")
+
+    def adam_layout(self):
+        """(param data_ptrs in the table order of the fused Adam / AdamW steps, how many of them belong to backward segment 0)"""
+        n = len(self.params["main"])
+        buf, n0 = (C.c_long * n)(), C.c_int(0)
+        rc = self._lib.klab_engine_adam_layout(self._h, n, buf, C.byref(n0))
+        if rc <= 0:
+            L.check(rc if rc < 0 else L.ERR_BADARG, "klab_engine_adam_layout")
+        return [int(buf[i]) for i in range(rc)], int(n0.value)
+
+    def adamw_step(self, m, v, group_of, groups, segment=None):
+        """torch.optim.AdamW's update for every parameter of the trainable T5 in one kernel, whatever the number of parameter groups
+        (+ refreshed bf16 copies).  group_of: int32 device tensor in adam_layout() order; groups: 1 .. 16 dicts of lr, beta1, beta2,
+        eps, weight_decay, bias_corr1, bias_corr2 (host values, passed by value); segment = 0 / 1: only that backward segment."""
+        L.check(self._lib.klab_engine_adamw_step(self._h, -1 if segment is None else int(segment), m.data_ptr(), v.data_ptr(),
+                                                 group_of.data_ptr(), L.adamw_groups(groups), len(groups), L.stream_ptr()),
+                "klab_engine_adamw_step")
 
     def adafactor_sizes(self):
         """(state, scalar, scratch) element counts of the f32 buffers klab_engine_adafactor_step works on"""

@@ -126,6 +126,11 @@ class _LossFn(torch.autograd.Function):
         model, eng = ctx.model, ctx.eng
         if ctx.token != model._fwd_token or eng is not model._engine:
             raise RuntimeError("klab MyModel: backward() must follow its own forward() (activations live in one workspace)")
+        opt = model._optimizer_in_backward() if model._optimizer_in_backward is not None else None
+        if opt is not None and opt._bw_token is not None:
+            # a second backward() before step() (gradient accumulation): segment 0 was already updated underneath the first one.
+            # The gradients are no longer "fresh" now, so _segment_ready below would never be asked: say it here.
+            raise opt._second_backward_error()
         g = gout.detach().to(torch.float32).contiguous().view(1)
         direct = model._direct_grads
         targets = model._grad_targets()

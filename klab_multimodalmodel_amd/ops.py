@@ -539,6 +539,20 @@ def adam_step(desc, total4, grads, m, v, arena, *, lr, beta1=0.9, beta2=0.999, e
                 "klab_adam_step_range")
 
 
+def adamw_step(desc, group_of, groups, grads, m, v, arena, *, begin4=0, end4=None, total4=None):
+    """one torch.optim.AdamW update (decoupled decay) of the vec4 range [begin4, end4) of the table's prefix space in ONE launch,
+    whatever the number of parameter groups (klab_adamw_step_range).  desc as for adam_step; group_of: int32 device tensor [n], the
+    group of each tensor in table order; groups: 1 .. 16 dicts (or tuples) of lr, beta1, beta2, eps, weight_decay, bias_corr1,
+    bias_corr2 -- host values, passed to the kernel by value.  end4 defaults to total4 (the whole table)."""
+    lib = L.load()
+    assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 4 and desc.is_contiguous()
+    assert group_of.dtype == torch.int32 and group_of.is_contiguous() and group_of.numel() == desc.shape[0] and group_of.device == desc.device
+    end4 = total4 if end4 is None else end4
+    L.check(lib.klab_adamw_step_range(desc.data_ptr(), desc.shape[0], group_of.data_ptr(), L.adamw_groups(groups), len(groups), int(begin4),
+                                      int(end4), grads.data_ptr(), m.data_ptr(), v.data_ptr(), arena.data_ptr(), L.dtype_code(arena.dtype),
+                                      L.stream_ptr()), "klab_adamw_step_range")
+
+
 def grad_norm_chunk():
     """elements per fp64 partial of grad_norm (a compile-time constant of the library; no GPU needed)"""
     return int(L.load().klab_grad_norm_chunk())

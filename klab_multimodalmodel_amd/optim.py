@@ -1,5 +1,6 @@
-"""Fused optimizers for the native MyModel: Adam and Adafactor (`FusedAdafactor`), and on-device gradient-norm
-clipping (`clip_grad_norm_`, `grad_norms`, at the end of the file).
+"""Fused optimizers for the native MyModel: Adam, AdamW with per-group hyper-parameters (`FusedAdamW`,
+`decay_param_groups`) and Adafactor (`FusedAdafactor`), and on-device gradient-norm clipping (`clip_grad_norm_`, `grad_norms`, at
+the end of the file).
 
 Drop-in for the reference's `torch.optim.Adam(model.module.transformer.parameters(), lr=args.lr)` (ref/train.py:28): same
 constructor arguments, same update rule (no amsgrad, L2 weight decay), `param_groups` / LR schedulers / `zero_grad` /
@@ -7,7 +8,8 @@ constructor arguments, same update rule (no amsgrad, L2 weight decay), `param_gr
 (the direct-gradient mode that `MyModel._direct_grads` / klab DDP use), `step()` is ONE kernel over all tensors that also
 rewrites the bf16 copies the next forward's GEMMs read -- the engine's separate fp32->bf16 cast pass is skipped.  In every
 other situation (foreign parameters, several param groups with different hyper-parameters, amsgrad, gradients that are not
-views of the flat buffer) it silently delegates to `torch.optim.Adam`, so it is always safe to use.
+views of the flat buffer) it silently delegates to `torch.optim.Adam`, so it is always safe to use.  Several groups stay on the
+one-kernel path with `FusedAdamW`.
 
 `step_in_backward=True` (opt-in; ONLY for loops in which every `backward()` is followed by `step()`, i.e. the reference's loop
 with its default `--accumulation_steps 1`, ref/train.py:61-67, ref/modules/config.py:16): the update of backward segment 0
@@ -22,10 +24,13 @@ import weakref
 
 import torch
 from torch.optim import Adam as _TorchAdam
+from torch.optim import AdamW as _TorchAdamW
 from torch.optim import Optimizer
 
 
 class FusedAdam(Optimizer):
+    _torch_cls = _TorchAdam  # the optimizer every other situation is delegated to
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, maximize=False,
                  step_in_backward=False):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
@@ -47,20 +52,34 @@ class FusedAdam(Optimizer):
         b1, b2 = g["betas"]
         return (float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), 1.0 - b1 ** steps, 1.0 - b2 ** steps)
 
+    def _launch(self, model, steps, segment=None):
+        """the update number `steps` of every tensor, or of backward segment 0 / 1, on the current stream"""
+        model._engine.adam_step(self._m, self._v, *self._hyper(steps), segment=segment)
+
+    def _in_backward_ok(self, model):
+        """may segment 0 be updated underneath this backward? (the groups' side of the question)"""
+        if len(self.param_groups) != 1:
+            return False
+        g = self.param_groups[0]
+        return not (g["amsgrad"] or g["maximize"])
+
+    def _second_backward_error(self):
+        return RuntimeError(f"{type(self).__name__}(step_in_backward=True) supports exactly one backward() per step(); with gradient "
+                            f"accumulation construct it with step_in_backward=False")
+
     @torch.no_grad()
     def _segment_ready(self, model, seg):
         """called by the model's backward when segment `seg`'s gradients are final on the current stream (and their all-reduce,
         if any, is enqueued): update segment 0 underneath the rest of the backward"""
-        if seg != 0 or self._fallback is not None or self._m is None or len(self.param_groups) != 1:
+        if seg != 0 or self._fallback is not None or self._m is None:
             return
         if self._bw_token is not None:
             # a second backward() before step(): gradient accumulation (ref/train.py --accumulation_steps > 1).  The first
             # micro-batch's gradients were already applied to segment 0 underneath its backward -- the update is not what Adam
             # would have done with the accumulated sum.  The contract is one backward per step: say so instead of training wrong.
-            raise RuntimeError("FusedAdam(step_in_backward=True) supports exactly one backward() per step(); with gradient "
-                               "accumulation construct it with step_in_backward=False")
-        g = self.param_groups[0]
-        if g["amsgrad"] or g["maximize"] or self._owner is None or self._owner() is not model:
+            # (_LossFn.backward raises the same error before it starts: this call is reached with fresh gradients only)
+            raise self._second_backward_error()
+        if self._owner is None or self._owner() is not model or not self._in_backward_ok(model):
             return
         flat = model._flat.get("main")
         if flat is None or self._m.shape != flat.shape or self._m.device != flat.device:
@@ -73,7 +92,7 @@ class FusedAdam(Optimizer):
             red = getattr(model, "_reducer", None)
             if red is not None:
                 red.finish_segment(0, flat.device)  # the current stream is the optimizer stream here
-            model._engine.adam_step(self._m, self._v, *self._hyper(self._steps + 1), segment=0)
+            self._launch(model, self._steps + 1, 0)
         self._bw_token = model._fwd_token
         self.in_backward_updates += 1
         model._pending_opt_stream = self._opt_stream
@@ -90,23 +109,31 @@ class FusedAdam(Optimizer):
                 owner = m
         return owner
 
-    def _fast_ok(self):
-        """(model, None) when the one-kernel path applies, else (None, reason)."""
+    def _groups_ok(self):
+        """None when the groups' settings allow the one-kernel path, else the reason"""
         if len(self.param_groups) != 1:
-            return None, "several param groups"
+            return "several param groups"
         g = self.param_groups[0]
         if g["amsgrad"] or g["maximize"]:
-            return None, "amsgrad / maximize"
+            return "amsgrad / maximize"
+        return None
+
+    def _fast_ok(self):
+        """(model, None) when the one-kernel path applies, else (None, reason)."""
+        why = self._groups_ok()
+        if why is not None:
+            return None, why
         model = self._find_owner()
         if model is None:
             return None, "parameters not owned by one klab MyModel"
         if model._flat.get("main") is None or model._engine.shape is None:
             return None, "engine not bound yet"
         views = {id(p): v for p, v, mn in (model._views or []) if mn == "main"}
-        mine = {id(p) for p in g["params"]}
+        params = [p for g in self.param_groups for p in g["params"]]  # (torch refuses a parameter in two groups)
+        mine = {id(p) for p in params}
         if mine != {id(p) for p in model.transformer.ordered() if p.requires_grad} or set(views) != mine:
             return None, "not exactly the trainable T5 parameters"
-        for p in g["params"]:
+        for p in params:
             v = views[id(p)]
             if p.grad is None or p.grad.data_ptr() != v.data_ptr():
                 return None, "gradients are not views of the flat buffer"
@@ -122,7 +149,7 @@ class FusedAdam(Optimizer):
         model, why = (None, "fallback already active") if self._fallback is not None else self._fast_ok()
         if model is None:
             if self._bw_token is not None:
-                raise RuntimeError(f"FusedAdam(step_in_backward=True): segment 0 was updated during backward() but step() cannot "
+                raise RuntimeError(f"{type(self).__name__}(step_in_backward=True): segment 0 was updated during backward() but step() cannot "
                                    f"take the fused path any more ({why})")
             for grp in self.param_groups:  # gradients may still be in flight (klab DDP overlap_optimizer): join before torch reads them
                 for p in grp["params"]:
@@ -132,17 +159,18 @@ class FusedAdam(Optimizer):
                     if red is not None:
                         owner._pending_reduce = None
                         red.finish()
-            self._fb_reason = why
+            if self._fallback is None or self._fb_reason is None:  # (later steps keep the reason of the first)
+                self._fb_reason = why
             self._step_fallback()
             return loss
         flat = model._flat["main"]
         if self._m is None or self._m.shape != flat.shape or self._m.device != flat.device:
             if self._bw_token is not None:
-                raise RuntimeError("FusedAdam(step_in_backward=True): the optimizer state changed between backward() and step()")
+                raise RuntimeError(f"{type(self).__name__}(step_in_backward=True): the optimizer state changed between backward() and step()")
             self._m = torch.zeros_like(flat)
             self._v = torch.zeros_like(flat)
         self._steps += 1
-        hyper = self._hyper(self._steps)
+        steps = self._steps
         seg0_done = self._bw_token is not None  # (reset by every step, set by every backward: one backward per step is the contract)
         self._bw_token = None
         if seg0_done:  # segment 0 was updated during the backward: the compute stream continues behind it
@@ -157,12 +185,12 @@ class FusedAdam(Optimizer):
                     if seg == 0 and seg0_done:
                         continue
                     red.finish_segment(seg)
-                    model._engine.adam_step(self._m, self._v, *hyper, segment=seg)
+                    self._launch(model, steps, seg)
                 red.finish()  # any further segment (Swin) and the bookkeeping
             elif seg0_done:
-                model._engine.adam_step(self._m, self._v, *hyper, segment=1)
+                self._launch(model, steps, 1)
             else:
-                model._engine.adam_step(self._m, self._v, *hyper)
+                self._launch(model, steps)
 
         launch()
         model._note_optimizer_step()
@@ -172,7 +200,7 @@ class FusedAdam(Optimizer):
 
     def _step_fallback(self):
         if self._fallback is None:
-            self._fallback = _TorchAdam(self.param_groups, fused=all(p.is_cuda for g in self.param_groups for p in g["params"]) or None)
+            self._fallback = self._torch_cls(self.param_groups, fused=all(p.is_cuda for g in self.param_groups for p in g["params"]) or None)
             self._fallback.param_groups = self.param_groups  # share the group dicts (LR schedulers act on ours)
             if self._m is not None:  # carry the fused state over (one-way)
                 model = self._owner() if self._owner is not None else None
@@ -209,6 +237,10 @@ class FusedAdam(Optimizer):
         steps = 0
         if model is not None and model._flat.get("main") is not None:
             model._grad_targets()  # builds the parameter -> flat-buffer views if no backward has run yet
+        why = self._loaded_state_refused()
+        if why is not None:
+            self._fb_reason = why
+            model = None
         if model is not None and model._views:
             flat = model._flat["main"]
             self._m, self._v = torch.zeros_like(flat), torch.zeros_like(flat)
@@ -224,9 +256,115 @@ class FusedAdam(Optimizer):
             self._steps = steps
             self._fallback = None
         else:  # no flat layout yet: continue with torch.optim.Adam on the loaded per-parameter state
-            self._fallback = _TorchAdam(self.param_groups)
+            self._fallback = self._torch_cls(self.param_groups)
             self._fallback.param_groups = self.param_groups
             self._fallback.state = self.state
+
+    def _loaded_state_refused(self):
+        """why a state that load_state_dict has just put into self.state cannot live in the flat buffers, or None"""
+        return None
+
+
+class FusedAdamW(FusedAdam):
+    """Drop-in for `torch.optim.AdamW` (decoupled weight decay, no amsgrad / maximize on the fused path): the same constructor, a
+    parameter iterable or a list of group dicts, `param_groups` / LR schedulers / `zero_grad` / `state_dict` as usual -- the
+    optimizer of the usual T5 fine-tuning recipe, with decay on the matrices and none on the norm weights and the position bias
+    (`decay_param_groups`).
+
+    When the union of the groups is exactly the trainable T5 of one bound klab MyModel (each parameter once), every `.grad` is a
+    view of the engine's flat gradient buffer (FusedAdam's ownership test), there are at most 16 groups, none of them asks for
+    amsgrad or maximize and all parameters share one step count, `step()` is ONE launch of csrc/adamw.hip whatever the number of
+    groups (one per backward segment under `step_in_backward` / klab DDP `overlap_optimizer`, exactly as FusedAdam).  The groups'
+    hyper-parameters are read from `param_groups` at every step and travel in the kernel's arguments, so a scheduler that moves
+    each group's `lr` simply works and nothing is copied to or read from the device.  The kernel also rewrites the compute-dtype
+    copies of the weights, so the next forward skips its cast.  Which group a tensor belongs to is a small device table in the
+    engine's table order (`Engine.adam_layout()`), built once and again only when the model's gradient views are replaced or the
+    groups' membership changes; a re-bind to another batch shape keeps it.
+
+    One common step count: the flat state holds ONE `step` (the bias corrections are host scalars per group).  A loaded state whose
+    parameters disagree about `step` continues in torch.  In every other situation too (CPU tensors, foreign parameters, amsgrad /
+    maximize, more than 16 groups, an unbound engine) the step is `torch.optim.AdamW` on the shared group dicts, after any
+    pending gradient reduction is joined and with the flat state carried over; `_fb_reason` says why."""
+    _torch_cls = _TorchAdamW
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 step_in_backward=False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                         step_in_backward=step_in_backward)
+        self._gid = None        # int32 device tensor: the group of each tensor, in Engine.adam_layout() order
+        self._gid_views = None  # the model's _views list and ...
+        self._gid_key = None    # ... the groups' membership it was built for
+
+    def _groups_ok(self):
+        from . import _lib
+        if not 1 <= len(self.param_groups) <= _lib.ADAMW_MAX_GROUPS:
+            return f"more than {_lib.ADAMW_MAX_GROUPS} param groups"
+        if any(g["amsgrad"] or g["maximize"] for g in self.param_groups):
+            return "amsgrad / maximize"
+        return None
+
+    def _in_backward_ok(self, model):
+        return self._groups_ok() is None and self._table_current(model)  # (the table is built at a step(), never inside a backward)
+
+    def _membership(self):
+        return tuple(tuple(id(p) for p in g["params"]) for g in self.param_groups)
+
+    def _table_current(self, model):
+        return self._gid is not None and self._gid_views is model._views and self._gid_key == self._membership()
+
+    def _group_hyper(self, steps):
+        out = []
+        for g in self.param_groups:
+            b1, b2 = g["betas"]
+            out.append((float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), 1.0 - b1 ** steps, 1.0 - b2 ** steps))
+        return out
+
+    def _group_table(self, model):
+        """the device table of group ids for `model`'s engine"""
+        if not self._table_current(model):
+            ptrs, _n0 = model._engine.adam_layout()
+            by_ptr = {p.data_ptr(): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
+            if len(ptrs) != len(by_ptr) or any(q not in by_ptr for q in ptrs):
+                raise RuntimeError("FusedAdamW: the engine's optimizer table does not list exactly this optimizer's parameters")
+            host = torch.tensor([by_ptr[q] for q in ptrs], dtype=torch.int32).pin_memory()  # pinned: the upload does not synchronise
+            self._gid = host.to(model._flat["main"].device, non_blocking=True)
+            self._gid_views, self._gid_key = model._views, self._membership()
+        return self._gid
+
+    def _launch(self, model, steps, segment=None):
+        model._engine.adamw_step(self._m, self._v, self._group_table(model), self._group_hyper(steps), segment=segment)
+
+    def _loaded_state_refused(self):
+        steps = {int(float(st["step"])) for st in self.state.values() if st and "step" in st}
+        return "parameters with different step counts" if len(steps) > 1 else None
+
+
+def decay_param_groups(tree_or_model, weight_decay, no_decay=("bias", "layer_norm")):
+    """The usual two AdamW parameter groups over the trainable T5 of a klab MyModel (or over any module whose parameters carry
+    HuggingFace state-dict names): `[{"params": [...], "weight_decay": weight_decay}, {"params": [...], "weight_decay": 0.0}]`.
+
+    The rule is this project's: a parameter goes into the second group when its state-dict name contains one of the `no_decay`
+    substrings.  For a T5 that is every `layer_norm.weight` / `final_layer_norm.weight` and `relative_attention_bias.weight` (T5
+    has no bias vectors); everything else -- the embedding, the attention and feed-forward matrices, an untied LM head -- decays.
+    Tied aliases (`encoder.embed_tokens.weight`, ...) are listed once, under the name that owns the tensor; parameters that do not
+    require a gradient are left out."""
+    tree = getattr(tree_or_model, "transformer", tree_or_model)
+    decay, rest = [], []
+    for name, p in tree.named_parameters():  # (named_parameters lists a shared tensor once)
+        if not p.requires_grad:
+            continue
+        (rest if any(s in name for s in no_decay) else decay).append(p)
+    return [{"params": decay, "weight_decay": float(weight_decay)}, {"params": rest, "weight_decay": 0.0}]
 
 
 class FusedAdafactor(Optimizer):
