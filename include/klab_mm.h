@@ -328,6 +328,16 @@ int klab_relbias_bwd(const float* dbias, const int* bucket, float* dtable, int h
 int klab_ce_count(const long long* labels, int rows, float* inv_n, void* stream);
 int klab_ce_fwd(void* logits, long ld, int dtype, const long long* labels, int rows, int V, float* inv_n, float* loss_row,
                 float* loss, int write_grad, void* stream);
+/* the same with options (csrc/ce_opts.hip): label smoothing eps in [0, 1), z-loss z >= 0 and per-row weights (f32 [rows], finite,
+ * >= 0, NULL = all ones):
+ *   l_i = lse - (1 - eps) x_y - (eps / V) sum_j x_j + z lse^2 (0 where the label is -100), loss = sum_i w_i l_i / W with
+ *   W = sum of w_i over the rows with a label (loss 0 when W == 0), d l / d x_j = (w_i / W) [p_j (1 + 2 z lse) - (1 - eps) [j == y] - eps / V].
+ * loss_row receives the UNWEIGHTED l_i; a row with w_i == 0 or without a label gets a gradient of exact zeros.
+ * klab_ce_wsum writes inv_w[0] = 1 / W (0 when W == 0) in a fixed order; write_grad as klab_ce_fwd (bit 1: inv_w is already filled).
+ * With eps = 0, z = 0 and weights NULL or all ones every output equals klab_ce_fwd's bit for bit. */
+int klab_ce_wsum(const long long* labels, const float* weights, int rows, float* inv_w, void* stream);
+int klab_ce_fwd_opts(void* logits, long ld, int dtype, const long long* labels, const float* weights, int rows, int V, float eps, float z,
+                     float* inv_w, float* loss_row, float* loss, int write_grad, void* stream);
 int klab_im2col_patch(const float* pixels, void* out, int dtype, int B, int Cin, int Himg, int P, void* stream);
 /* same, rows of `ldo` >= Cin*P*P elements with the tail columns zero-filled (lets the patch-embedding GEMM run with K
  * padded to a multiple of 32); P == 4 takes a one-thread-per-patch vector path */
@@ -796,6 +806,12 @@ const float* klab_engine_loss_ptr(const klab_engine* e);
  * slot -- a caller that hands out a fresh tensor per step (MyModel.forward, ref/models/model.py:26) then needs no copy launch behind
  * the cross-entropy.  Returns 1 if it will be honoured, 0 under graph replay (the loss stays at klab_engine_loss_ptr), < 0 on error. */
 int klab_engine_set_loss_out(klab_engine* e, float* out);
+/* Options of the training loss.  eps (label smoothing, 0 <= eps < 1) and z (z-loss, >= 0) persist until changed.  `weights` (device,
+ * B*Lt floats, or NULL) is one-shot like klab_engine_set_loss_out: the NEXT klab_engine_forward copies it into the workspace beside
+ * the labels and never reads the caller's tensor again; a caller whose forward failed early passes NULL to disarm it.  With
+ * eps == z == 0 and no weights the forward issues klab_ce_fwd as before (graph slots included); otherwise klab_ce_wsum and
+ * klab_ce_fwd_opts, eagerly -- never from a captured graph, which would replay the options of the capture. */
+int klab_engine_set_loss_options(klab_engine* e, float eps, float z, const float* weights);
 const int* klab_engine_err_ptr(const klab_engine* e);
 /* device words {seed of the current step, base seed, forwards since seeding} (for stream-ordered snapshots; see klab_engine_get_rng) */
 const uint32_t* klab_engine_rng_ptr(const klab_engine* e);

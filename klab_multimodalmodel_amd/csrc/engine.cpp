@@ -204,6 +204,11 @@ struct klab_engine {
   bool dbias_zeroed[2] = {false, false};  // [decoder stack, encoder stack]
   bool denc_in_dxn = false;      // segment 0 left d(encoder output) in dxn, where segment 1's stack reads it
   float* loss_out = nullptr;     // one-shot destination of the next forward's loss (klab_engine_set_loss_out)
+  // klab_engine_set_loss_options: the scalars persist, the weights pointer is one-shot (the next forward copies B*Lt floats into
+  // loss_w_buf and never reads the caller's tensor again)
+  float loss_eps = 0.f, loss_z = 0.f;
+  const float* loss_w_armed = nullptr;
+  float *loss_w_buf = nullptr, *inv_w = nullptr;
   bool bias_ready[3] = {false, false, false};  // [stack id]: the stack's position bias was computed ahead of it, on the side stream
   bool dec_embed_ready = false;   // ... and the decoder's input embedding
   bool inv_n_ready = false;       // ... and 1 / n_valid of the labels
@@ -517,9 +522,11 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
   e->inv_n = (float*)((char*)e->seed_dev + 128);
   e->loss = (float*)((char*)e->seed_dev + 192);
   e->dloss_buf = (float*)((char*)e->seed_dev + 256);
+  e->inv_w = (float*)((char*)e->seed_dev + 320);
   e->pixels_buf = (float*)b.take((size_t)B * c.swin.in_ch * c.swin.image_size * c.swin.image_size * 4);
   e->src_buf = (long long*)b.take((size_t)B * Ls * 8);
   e->tgt_buf = (long long*)b.take((size_t)B * Lt * 8);
+  e->loss_w_buf = (float*)b.take((size_t)B * Lt * 4);
   e->warena = b.take((size_t)e->warena_elems * es);
   e->farena = (float*)b.take((size_t)e->farena_elems * 4);
   if (e->fp8) {
@@ -1524,6 +1531,7 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
   e->bias_ready[0] = e->bias_ready[1] = e->bias_ready[2] = e->dec_embed_ready = e->inv_n_ready = e->kv_wgrad_done = false;
   e->wplan.valid = false;  // rebuilt at the next backward, for the new binding's buffers
   e->loss_out = nullptr;
+  e->loss_w_armed = nullptr;
   e->forced_armed = ForcedTable();
   e->attn_armed = AttnMaps();
   e->gen.maps = AttnMaps();  // (sized for the old binding's rows)
@@ -1899,6 +1907,13 @@ extern "C" int klab_engine_forward(klab_engine* e, const float* pixels, const lo
   }
   RC((int)hipMemcpyAsync(e->src_buf, src_ids, (size_t)B * e->Ls * 8, hipMemcpyDeviceToDevice, c.s));
   RC((int)hipMemcpyAsync(e->tgt_buf, tgt_ids, (size_t)B * e->Lt * 8, hipMemcpyDeviceToDevice, c.s));
+  const float* loss_w = nullptr;  // this forward's per-token loss weights (one-shot, staged like the labels)
+  if (e->loss_w_armed) {
+    const float* src_w = e->loss_w_armed;
+    e->loss_w_armed = nullptr;
+    RC((int)hipMemcpyAsync(e->loss_w_buf, src_w, (size_t)B * e->Lt * 4, hipMemcpyDeviceToDevice, c.s));
+    loss_w = e->loss_w_buf;
+  }
   if (!e->seed_set || seed != e->seed_base) {  // (re)seed the device-side counter RNG; each forward then advances it itself
     hipLaunchKernelGGL(seed_set_kernel, dim3(1), dim3(1), 0, c.s, e->seed_dev, seed);
     e->seed_base = seed; e->seed_set = true;
@@ -1935,9 +1950,17 @@ extern "C" int klab_engine_forward(klab_engine* e, const float* pixels, const lo
     e->inv_n_ready = false;
     float* loss_dst = e->loss_out && !e->use_graph ? e->loss_out : e->loss;  // (replayed graphs write the fixed address)
     e->loss_out = nullptr;
-    RC(run_graphed(e, want_grad ? 3 : 2, c.s, [&]() {
-      return klab_ce_fwd(e->logits, V, c.dt, e->tgt_buf, Md, V, e->inv_n, e->loss_row, loss_dst, (want_grad ? 1 : 0) | (counted ? 2 : 0), c.ws());
-    }));
+    if (!loss_w && e->loss_eps == 0.f && e->loss_z == 0.f) {
+      RC(run_graphed(e, want_grad ? 3 : 2, c.s, [&]() {
+        return klab_ce_fwd(e->logits, V, c.dt, e->tgt_buf, Md, V, e->inv_n, e->loss_row, loss_dst, (want_grad ? 1 : 0) | (counted ? 2 : 0), c.ws());
+      }));
+    } else {
+      // label smoothing, z-loss or weights: eager like the LM head beside it, never a graph slot -- the options change between
+      // steps and a replay would bake them in
+      RC(klab_ce_wsum(e->tgt_buf, loss_w, Md, e->inv_w, c.ws()));
+      RC(klab_ce_fwd_opts(e->logits, V, c.dt, e->tgt_buf, loss_w, Md, V, e->loss_eps, e->loss_z, e->inv_w, e->loss_row, loss_dst,
+                          (want_grad ? 1 : 0) | 2, c.ws()));
+    }
   }
   return leave_stream(e, (hipStream_t)stream, xs);
 }
@@ -1983,6 +2006,15 @@ extern "C" int klab_engine_set_loss_out(klab_engine* e, float* out) {
   e->loss_out = e->use_graph ? nullptr : out;
   return e->loss_out ? 1 : 0;
 }
+// Options of the training loss (klab_ce_fwd_opts): eps and z persist until changed; `weights` (device, B*Lt floats, or NULL) is
+// one-shot -- the next forward stages it beside the labels.  A caller whose forward fails early passes NULL again to disarm it.
+extern "C" int klab_engine_set_loss_options(klab_engine* e, float eps, float z, const float* weights) {
+  if (!e || !(eps >= 0.f && eps < 1.f) || !(z >= 0.f) || !isfinite(z)) return KLAB_ERR_BADARG;
+  if (weights && !e->bound) return KLAB_ERR_BADARG;
+  e->loss_eps = eps; e->loss_z = z;
+  e->loss_w_armed = weights;
+  return KLAB_OK;
+}
 extern "C" const int* klab_engine_err_ptr(const klab_engine* e) { return e ? e->err_dev : nullptr; }
 extern "C" const uint32_t* klab_engine_rng_ptr(const klab_engine* e) { return e ? e->seed_dev : nullptr; }
 
@@ -1994,6 +2026,7 @@ extern "C" const void* klab_engine_buffer(const klab_engine* e, const char* name
   if (!strcmp(name, "encoder_out")) { set((long)e->B * e->Le, d, e->cfg.dtype); return e->enc.out_t; }
   if (!strcmp(name, "decoder_out")) { set((long)e->B * e->Lt, d, e->cfg.dtype); return e->dec.out_t; }
   if (!strcmp(name, "logits")) { set((long)e->B * e->Lt, e->cfg.main.vocab, e->cfg.dtype); return e->logits; }
+  if (!strcmp(name, "loss_row")) { set((long)e->B * e->Lt, 1, KLAB_F32); return e->loss_row; }
   return nullptr;
 }
 

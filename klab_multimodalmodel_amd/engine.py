@@ -384,6 +384,12 @@ class Engine:
             L.check(rc, "klab_engine_set_loss_out")
         return rc == 1
 
+    def set_loss_options(self, eps=0.0, z=0.0, weights=None):
+        """label smoothing and z-loss of the forwards from now on; `weights` (fp32 [B, Lt] device tensor or None) for the next
+        forward only, which copies it (None disarms weights armed earlier)"""
+        L.check(self._lib.klab_engine_set_loss_options(self._h, float(eps), float(z), weights.data_ptr() if weights is not None else None),
+                "klab_engine_set_loss_options")
+
     # ---- decoding sessions (HF `_beam_search`, `_sample`, greedy decoding); the workspace is the caller's, the binding's is
     # untouched ----------------------------------------------------------------------------------------------------------------
     GEN_MODES = {"pick": L.GEN_PICK, "sample": L.GEN_SAMPLE, "beam": L.GEN_BEAM, "force": L.GEN_FORCE}

@@ -107,13 +107,18 @@ class _LossFn(torch.autograd.Function):
         # a fresh tensor per step, written by the cross-entropy kernel itself (no copy launch behind it)
         out = torch.empty(1, device=pixels.device, dtype=torch.float32)
         direct_loss = eng.set_loss_out(out)
+        weights, model._loss_weights_next = model._loss_weights_next, None
+        eps, z = model.loss_options["label_smoothing"], model.loss_options["z_loss"]
         # the engine keeps a device-side counter RNG: the base only (re)seeds it, every forward advances it
         try:
+            eng.set_loss_options(eps, z, weights)
             eng.forward(pixels, src, tgt, training=int(model.transformer.training) | (2 if model._frozen_unchanged() else 0) | (4 if model._trainable_current() else 0),
                         seed=model._seed_base, want_grad=want_grad)
         except Exception:
             eng.set_loss_out(None)  # a forward that failed before its cross-entropy must not leave the one-shot pointer armed
+            eng.set_loss_options(eps, z, None)  # ... nor the one-shot loss weights
             raise
+        model._token_losses_valid = True
         ctx.model = model
         ctx.eng = eng
         ctx.nparams = len(params)
@@ -246,6 +251,9 @@ class MyModel(nn.Module):
         self._frozen_fp = None
         self._train_fp = None  # version fingerprint of the trainable T5 right after a klab FusedAdam step (bf16 copies current)
         self._fwd_token = 0
+        self._loss_options = {"label_smoothing": 0.0, "z_loss": 0.0}
+        self._loss_weights_next = None  # this call's target_encoding["loss_weights"], taken by _LossFn.forward
+        self._token_losses_valid = False  # the engine's per-token losses are those of a loss forward of this binding
         import weakref
         for p in self.transformer.parameters():  # lets klab_multimodalmodel_amd.optim.FusedAdam find its engine
             p._klab_owner = weakref.ref(self)
@@ -312,6 +320,7 @@ class MyModel(nn.Module):
             self._bound_key = key
             self._frozen_fp = None
             self._train_fp = None
+            self._token_losses_valid = False
         return self._engine
 
     def _note_optimizer_step(self):
@@ -352,6 +361,39 @@ class MyModel(nn.Module):
             self._views = out
         return [(p, v) for p, v, _m in self._views if p.requires_grad]
 
+    # ---- loss options -------------------------------------------------------------------------
+    def set_loss_options(self, label_smoothing=0.0, z_loss=0.0):
+        """Options of the training loss, for every forward from now on (train and eval mode, with or without gradients; generate and
+        score are not touched).  For each scored token with logits x, label y and lse = logsumexp(x):
+            l = lse - (1 - label_smoothing) x_y - (label_smoothing / V) sum_j x_j + z_loss lse^2
+        label_smoothing is torch.nn.functional.cross_entropy's (0 <= label_smoothing < 1), z_loss the coefficient of mesh-tensorflow
+        T5's auxiliary z-loss (>= 0; T5, T5 v1.1 and Flan-T5 were pre-trained with 1e-4).  Per-token weights travel with the call
+        instead: target_encoding["loss_weights"], a float [B, Lt] tensor on the model's device (finite, >= 0), used for that
+        forward only; the loss is sum w l / sum w over the tokens whose label is not -100.  With both options 0 and no weights the
+        forward runs exactly the launches of the plain loss.
+        These are hyper-parameters of the training script, not model state: save, state_dict and checkpoint.py do not store them.
+        Under klab DDP every rank normalises by its own sum of weights, exactly as it normalises by its own count of scored tokens
+        without them."""
+        eps, z = float(label_smoothing), float(z_loss)
+        if not (math.isfinite(eps) and 0.0 <= eps < 1.0):
+            raise ValueError(f"`label_smoothing` has to be a finite float in [0, 1), but is {label_smoothing}")
+        if not (math.isfinite(z) and z >= 0.0):
+            raise ValueError(f"`z_loss` has to be a finite float >= 0, but is {z_loss}")
+        self._loss_options = {"label_smoothing": eps, "z_loss": z}
+
+    @property
+    def loss_options(self):
+        """dict(label_smoothing, z_loss) as set_loss_options left them"""
+        return dict(self._loss_options)
+
+    def token_losses(self):
+        """fp32 [B, Lt] device tensor: a copy of the per-token losses l of the last loss forward (unweighted, with the loss options
+        of that forward; 0 where the label is -100).  sum w l / sum w over the scored tokens is the loss that forward returned."""
+        if not self._token_losses_valid:
+            raise RuntimeError("token_losses(): no loss forward has run on this binding yet (generate and score keep none)")
+        B, _Ls, Lt = self._bound_key[:3]
+        return self._engine.buffer("loss_row").view(B, Lt).clone()
+
     def flat_grads(self, model="main"):
         return self._flat.get(model)
 
@@ -379,6 +421,15 @@ class MyModel(nn.Module):
         src = src.to(torch.int64).contiguous()
         if return_loss:
             tgt = target_encoding["input_ids"].to(torch.int64).contiguous()
+            weights = target_encoding["loss_weights"] if "loss_weights" in target_encoding else None
+            if weights is not None:
+                if not torch.is_tensor(weights) or not weights.is_floating_point() or tuple(weights.shape) != tuple(tgt.shape):
+                    raise ValueError(f"target_encoding['loss_weights'] has to be a float tensor {tuple(tgt.shape)}, got "
+                                     f"{getattr(weights, 'dtype', type(weights))} {tuple(getattr(weights, 'shape', ()))}")
+                if weights.device != tgt.device:
+                    raise ValueError(f"target_encoding['loss_weights'] is on {weights.device}, the labels on {tgt.device}")
+                weights = weights.detach().to(torch.float32).contiguous()
+            self._loss_weights_next = weights
             params = self._trainable()
             # (grad mode is off inside Function.forward, so decide here whether d logits must be produced)
             want_grad = torch.is_grad_enabled() and len(params) > 0
@@ -504,6 +555,8 @@ class MyModel(nn.Module):
         self.transformer.eval()
         try:
             eng = self._engine_for(pixels, src, tgt)
+            self._token_losses_valid = False  # (these forwards score a pad target ...
+            eng.set_loss_options()                # ... with the plain loss: the launches generate always issued)
             for t in range(steps):
                 eng.forward(pixels, src, tgt, training=(8 if t > 0 else 0) | (2 if t > 0 else 0), seed=self._seed_base, want_grad=False)
                 nxt = eng.buffer("logits").view(B, steps, -1)[:, t].float().argmax(-1)
@@ -579,6 +632,8 @@ class MyModel(nn.Module):
         self.transformer.eval()
         try:
             eng = self._engine_for(pixels, src, tgt)
+            self._token_losses_valid = False  # (this forward scores a pad target ...
+            eng.set_loss_options()                # ... with the plain loss: the launches generate and score always issued)
             eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
             gen = eng.gen_cfg("force", N, L + 1, cfg.eos_token_id, cfg.pad_token_id, want_logprobs=True)
             nbytes = eng.gen_workspace_bytes(gen)
@@ -632,6 +687,8 @@ class MyModel(nn.Module):
         self.transformer.eval()
         try:
             eng = self._engine_for(pixels, src, tgt)
+            self._token_losses_valid = False  # (this forward scores a pad target ...
+            eng.set_loss_options()                # ... with the plain loss: the launches generate and score always issued)
             eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
             gen = eng.gen_cfg(mode, n, max_length, cfg.eos_token_id, pad, temperature, top_k, top_p, seed, length_penalty, early_stopping,
                               procs, want_logprobs=logprobs)

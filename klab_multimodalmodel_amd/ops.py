@@ -436,6 +436,21 @@ def ce_count(labels, inv_n):
     L.check(lib.klab_ce_count(labels.data_ptr(), labels.numel(), inv_n.data_ptr(), L.stream_ptr()), "klab_ce_count")
 
 
+def ce_wsum(labels, weights, inv_w):
+    """inv_w[0] = 1 / (sum of weights[i] over the labels != -100), 0 when that sum is 0; weights None = all ones"""
+    lib = L.load()
+    L.check(lib.klab_ce_wsum(labels.data_ptr(), L.ptr(weights), labels.numel(), inv_w.data_ptr(), L.stream_ptr()), "klab_ce_wsum")
+
+
+def ce_fwd_opts(logits, labels, weights, inv_w, loss_row, loss, *, eps=0.0, z=0.0, write_grad=True):
+    """ce_fwd with label smoothing eps, z-loss z and per-row weights (f32 [rows] or None); loss_row gets the unweighted row losses"""
+    lib = L.load()
+    rows, V = logits.shape
+    L.check(lib.klab_ce_fwd_opts(logits.data_ptr(), logits.stride(0), L.dtype_code(logits.dtype), labels.data_ptr(), L.ptr(weights), rows, V,
+                                 float(eps), float(z), inv_w.data_ptr(), loss_row.data_ptr(), loss.data_ptr(), int(write_grad),
+                                 L.stream_ptr()), "klab_ce_fwd_opts")
+
+
 def embed_fwd(ids, table, out, *, shift_right=False, L_seq=1, start_id=0, pad_id=0, drop_p=0.0, seed=None, tag=0, err=None):
     lib = L.load()
     rows, d = out.shape
