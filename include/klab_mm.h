@@ -506,6 +506,25 @@ int klab_engine_adam_layout(klab_engine* e, int max_n, long* param_ptrs, int* n_
  * table is unusable. */
 int klab_engine_adamw_step(klab_engine* e, int segment /* -1 both, 0, 1 */, float* m, float* v, const int* group_of_dev,
                            const klab_adamw_group* groups, int ngroups, void* stream);
+/* Exponential moving average of the weights over the same descriptor table, one launch each whatever the number of tensors
+ * (csrc/ema.hip).  ema: caller-owned f32 buffer laid out like the "main" flat gradient buffer, indexed by grad_off exactly as m
+ * and v are.  [begin4, end4): vec4 range of the table's prefix space, as klab_adam_step_range; all tensor lengths are multiples
+ * of 4.  No floating-point atomics, nothing read back.
+ *   update  per element, in f32:  e' = e + w (p - e)  (may contract to an FMA).  w is a HOST scalar passed by value, 0 <= w <= 1
+ *           (the caller forms (float)(1.0 - decay) in double).  p is only read and no arena is touched: 12 bytes per parameter.
+ *   swap    p and e exchange their bits -- moved, not computed: NaN payloads, -0, infinities and denormals survive -- and, for
+ *           tensors with arena_off >= 0, arena copy = (dtype) new p (round-to-nearest-even bf16, or the f32 bits).  Two swaps
+ *           restore p and ema bit for bit.  16 bytes per parameter + 2 for a bf16 copy.
+ * KLAB_ERR_BADARG: w outside [0, 1] or NaN, a null pointer, ndesc <= 0, begin4 < 0, end4 < begin4, dtype neither KLAB_BF16 nor
+ * KLAB_F32; nothing is launched.  end4 == begin4: KLAB_OK without a launch. */
+int klab_ema_update_range(const void* desc_dev, int ndesc, long begin4, long end4, float* ema, float w, void* stream);
+int klab_ema_swap_range(const void* desc_dev, int ndesc, long begin4, long end4, float* ema, void* arena, int dtype, void* stream);
+/* the two on the engine's table, the whole range, its weight arena and compute dtype: after klab_engine_ema_swap the compute-dtype
+ * copies are those of the parameters now in place, as after klab_engine_adam_step.  The ema buffer is the caller's and survives a
+ * re-bind to another batch shape (same tensors, same layout).  KLAB_ERR_UNSUPPORTED when the Adam table is unusable,
+ * KLAB_ERR_BADARG when the engine is unbound. */
+int klab_engine_ema_update(klab_engine* e, float* ema, float w, void* stream);
+int klab_engine_ema_swap(klab_engine* e, float* ema, void* stream);
 /* Adafactor (the rule of transformers.optimization.Adafactor) for ALL parameters of the trainable T5 in four launches, whatever
  * the number of tensors: statistics (row / column sums of g^2 + eps0, sum p^2), their reduction (EMA into R / C, mean R, RMS(p)),
  * sum u^2, apply.  Tensors with >= 2 dims are factored (rows = product of all dims but the last), 1-D tensors keep a full second

@@ -131,6 +131,8 @@ SIGNATURES = {
     "klab_adam_step": [vp, i32, i64, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, f32, vp],
     "klab_adam_step_range": [vp, i32, i64, i64, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, f32, vp],
     "klab_adamw_step_range": [vp, i32, vp, C.POINTER(AdamWGroup), i32, i64, i64, vp, vp, vp, vp, i32, vp],
+    "klab_ema_update_range": [vp, i32, i64, i64, vp, f32, vp],
+    "klab_ema_swap_range": [vp, i32, i64, i64, vp, vp, i32, vp],
     "klab_adafactor_plan": [i32, vp, vp, vp, vp, vp],
     "klab_adafactor_step": [vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, f32, f32, f32, i32, vp],
     "klab_grad_norm_chunk": [],

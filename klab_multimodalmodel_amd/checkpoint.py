@@ -12,6 +12,8 @@ adds what a resume needs, without stalling the training loop:
   * sharded optimizer state: under data parallelism every rank holds identical Adam moments, so rank r writes only slice r of
     the flat exp_avg / exp_avg_sq buffers (`<name>.opt<r>of<w>`), 1/world of the bytes per rank; rank 0 writes the model.
     With an optimizer other than `optim.FusedAdam` on its flat buffers the whole `state_dict()` goes into rank 0's file.
+  * weight EMA: `save(..., ema=ema)` stores `optim.WeightEMA.state_dict()` under "ema" in rank 0's file (every rank holds the
+    same average), `load_checkpoint(..., ema=ema)` loads it back, before or after the model is bound.
 
     ck = AsyncCheckpointer(args.result_dir)
     ck.save(model, optimizer, scheduler, step=global_step, name="epoch_3.pth", rank=rank, world=world)   # returns at once
@@ -70,7 +72,8 @@ class AsyncCheckpointer:
             e, self._error = self._error, None
             raise e
 
-    def save(self, model, optimizer=None, scheduler=None, step=0, name="checkpoint.pth", rank=0, world=1, extra=None):
+    def save(self, model, optimizer=None, scheduler=None, step=0, name="checkpoint.pth", rank=0, world=1, extra=None, ema=None):
+        """`ema`: an optim.WeightEMA whose state_dict() goes into rank 0's file under "ema", through the same host copy"""
         self.wait()  # one save in flight: the pinned snapshot of the previous one is released first
         core = _core(model)
         dev = next(core.transformer.parameters()).device
@@ -82,6 +85,7 @@ class AsyncCheckpointer:
         t_sd = core.transformer.state_dict() if rank == 0 else None
         i_sd = core.image_model.state_dict() if rank == 0 and getattr(core.args, "image_model_train", False) else None
         o_sd = optimizer.state_dict() if rank == 0 and optimizer is not None and flat is None else None
+        e_sd = ema.state_dict() if rank == 0 and ema is not None else None
         eng = getattr(core, "_engine", None)
         rng_dev = eng.rng_view if rank == 0 and eng is not None and getattr(eng, "shape", None) is not None else None
         # 2. ... then the side stream waits for the current one: the snapshot sees every update and every temporary above
@@ -107,6 +111,8 @@ class AsyncCheckpointer:
                 payload["scheduler"] = scheduler.state_dict()
             if extra is not None:
                 payload["extra"] = extra
+            if e_sd is not None:
+                payload["ema"] = _to_host(e_sd, stream)
             if optimizer is not None:
                 if flat is None:
                     payload["optimizer"] = _to_host(o_sd, stream)
@@ -117,7 +123,7 @@ class AsyncCheckpointer:
             n = flat[0].numel()
             lo, hi = n * rank // world, n * (rank + 1) // world
             shard = {"lo": lo, "hi": hi, "exp_avg": _to_host(flat[0][lo:hi], stream), "exp_avg_sq": _to_host(flat[1][lo:hi], stream)}
-        keep = (t_sd, i_sd, o_sd, rng_dev)  # device temporaries stay referenced until the copy event has completed (write())
+        keep = (t_sd, i_sd, o_sd, e_sd, rng_dev)  # device temporaries stay referenced until the copy event has completed (write())
         ev = None
         if stream is not None:
             ev = torch.cuda.Event()
@@ -144,9 +150,10 @@ class AsyncCheckpointer:
         return path
 
 
-def load_checkpoint(path, model, optimizer=None, scheduler=None, restore_rng=False, map_location="cpu"):
+def load_checkpoint(path, model, optimizer=None, scheduler=None, restore_rng=False, map_location="cpu", ema=None):
     """inverse of AsyncCheckpointer.save; returns the saved step.  For the FusedAdam flat state the model must have run one
-    forward (its flat buffers exist then); every rank reads all shards (the moments are replicated under data parallelism)."""
+    forward (its flat buffers exist then); every rank reads all shards (the moments are replicated under data parallelism).
+    `ema`: an optim.WeightEMA that takes the saved average back, whether the model is bound already or not."""
     ck = torch.load(path, map_location=map_location, weights_only=False)
     core = _core(model)
     core.transformer.load_state_dict(ck["transformer"])          # ref/models/model.py:38
@@ -176,6 +183,10 @@ def load_checkpoint(path, model, optimizer=None, scheduler=None, restore_rng=Fal
                 g.update(saved)
     if scheduler is not None and "scheduler" in ck:
         scheduler.load_state_dict(ck["scheduler"])
+    if ema is not None:
+        if "ema" not in ck:
+            raise RuntimeError(f"{path} holds no weight EMA (it was saved without `ema=`)")
+        ema.load_state_dict(ck["ema"])
     er = ck.get("engine_rng")
     if er is not None and hasattr(core, "_seed_base"):  # continue the dropout mask stream (always: it is part of the training state)
         core._seed_base = int(er["seed_base"])

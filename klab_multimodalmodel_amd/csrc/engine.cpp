@@ -1857,6 +1857,18 @@ extern "C" int klab_engine_adamw_step(klab_engine* e, int segment, float* m, flo
   return klab_adamw_step_range(e->adam_desc, e->n_adam, group_of_dev, groups, ngroups, b4, e4, e->G[2], m, v, e->warena, e->cfg.dtype, stream);
 }
 
+extern "C" int klab_engine_ema_update(klab_engine* e, float* ema, float w, void* stream) {
+  if (!e || !e->bound || !ema) return KLAB_ERR_BADARG;
+  if (!e->n_adam) return KLAB_ERR_UNSUPPORTED;
+  return klab_ema_update_range(e->adam_desc, e->n_adam, 0, e->adam_total4, ema, w, stream);
+}
+
+extern "C" int klab_engine_ema_swap(klab_engine* e, float* ema, void* stream) {
+  if (!e || !e->bound || !ema) return KLAB_ERR_BADARG;
+  if (!e->n_adam) return KLAB_ERR_UNSUPPORTED;
+  return klab_ema_swap_range(e->adam_desc, e->n_adam, 0, e->adam_total4, ema, e->warena, e->cfg.dtype, stream);
+}
+
 // Device-side dropout RNG of the binding: st[1] = base seed, st[2] = number of forwards since it was (re)seeded; every forward
 // derives its masks from hash(base, counter).  A resumed run restores both so that it continues the mask stream instead of
 // replaying it from step 1 (checkpoint.py).

@@ -139,6 +139,8 @@ ENGINE_SIGS = {
                                        C.c_float, C.c_float, C.c_void_p], C.c_int),
     "klab_engine_adam_layout": ([C.c_void_p, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_int)], C.c_int),
     "klab_engine_adamw_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(L.AdamWGroup), C.c_int, C.c_void_p], C.c_int),
+    "klab_engine_ema_update": ([C.c_void_p, C.c_void_p, C.c_float, C.c_void_p], C.c_int),
+    "klab_engine_ema_swap": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_adafactor_state_elems": ([C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)], C.c_int),
     "klab_engine_adafactor_layout": ([C.c_void_p, C.c_int, C.POINTER(C.c_long)], C.c_int),
     "klab_engine_adafactor_step": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_float] * 9 + [C.c_int, C.c_void_p],
@@ -548,6 +550,20 @@ class Engine:
         L.check(self._lib.klab_engine_adamw_step(self._h, -1 if segment is None else int(segment), m.data_ptr(), v.data_ptr(),
                                                  group_of.data_ptr(), L.adamw_groups(groups), len(groups), L.stream_ptr()),
                 "klab_engine_adamw_step")
+
+    def ema_update(self, ema, w):
+        """ema += w (p - ema) for every parameter of the trainable T5 in one kernel; ema: fp32 device tensor laid out like the "main"
+        flat gradient buffer, w: host float in [0, 1] (passed by value).  The parameters are only read."""
+        if ema.dtype != torch.float32 or not ema.is_contiguous() or ema.numel() < self.grad_elems["main"]:
+            raise ValueError("the EMA buffer has to be a contiguous fp32 tensor of the flat gradient buffer's size")
+        L.check(self._lib.klab_engine_ema_update(self._h, ema.data_ptr(), float(w), L.stream_ptr()), "klab_engine_ema_update")
+
+    def ema_swap(self, ema):
+        """exchange the bits of every parameter of the trainable T5 with its slice of `ema` in one kernel (+ refreshed bf16 copies of
+        the parameters now in place); a second call restores both bit for bit."""
+        if ema.dtype != torch.float32 or not ema.is_contiguous() or ema.numel() < self.grad_elems["main"]:
+            raise ValueError("the EMA buffer has to be a contiguous fp32 tensor of the flat gradient buffer's size")
+        L.check(self._lib.klab_engine_ema_swap(self._h, ema.data_ptr(), L.stream_ptr()), "klab_engine_ema_swap")
 
     def adafactor_sizes(self):
         """(state, scalar, scratch) element counts of the f32 buffers klab_engine_adafactor_step works on"""

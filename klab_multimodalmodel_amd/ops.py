@@ -568,6 +568,30 @@ def adamw_step(desc, group_of, groups, grads, m, v, arena, *, begin4=0, end4=Non
                                       L.stream_ptr()), "klab_adamw_step_range")
 
 
+def ema_update(desc, ema, w, *, begin4=0, end4=None, total4=None):
+    """one EMA update e' = e + w (p - e) of the vec4 range [begin4, end4) of the table's prefix space in ONE launch
+    (klab_ema_update_range).  desc as for adam_step; ema: fp32 device tensor laid out like grads / m / v (indexed by goff); w: host
+    float in [0, 1], passed to the kernel by value.  The parameters are only read.  end4 defaults to total4 (the whole table)."""
+    lib = L.load()
+    assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 4 and desc.is_contiguous()
+    assert ema.dtype == torch.float32 and ema.is_contiguous()
+    end4 = total4 if end4 is None else end4
+    L.check(lib.klab_ema_update_range(desc.data_ptr(), desc.shape[0], int(begin4), int(end4), ema.data_ptr(), float(w), L.stream_ptr()),
+            "klab_ema_update_range")
+
+
+def ema_swap(desc, ema, arena, *, begin4=0, end4=None, total4=None):
+    """exchange the bits of every parameter of the vec4 range [begin4, end4) with its slice of `ema` and write the compute-dtype
+    copy of the new parameter into `arena` (bf16 or fp32; tensors with aoff < 0 have none) in ONE launch (klab_ema_swap_range).
+    Two calls restore both bit for bit.  end4 defaults to total4 (the whole table)."""
+    lib = L.load()
+    assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 4 and desc.is_contiguous()
+    assert ema.dtype == torch.float32 and ema.is_contiguous()
+    end4 = total4 if end4 is None else end4
+    L.check(lib.klab_ema_swap_range(desc.data_ptr(), desc.shape[0], int(begin4), int(end4), ema.data_ptr(), arena.data_ptr(),
+                                    L.dtype_code(arena.dtype), L.stream_ptr()), "klab_ema_swap_range")
+
+
 def grad_norm_chunk():
     """elements per fp64 partial of grad_norm (a compile-time constant of the library; no GPU needed)"""
     return int(L.load().klab_grad_norm_chunk())

@@ -1,6 +1,6 @@
 """Fused optimizers for the native MyModel: Adam, AdamW with per-group hyper-parameters (`FusedAdamW`,
-`decay_param_groups`) and Adafactor (`FusedAdafactor`), and on-device gradient-norm clipping (`clip_grad_norm_`, `grad_norms`, at
-the end of the file).
+`decay_param_groups`) and Adafactor (`FusedAdafactor`), a fused exponential moving average of the weights with an in-place swap
+for evaluation (`WeightEMA`), and on-device gradient-norm clipping (`clip_grad_norm_`, `grad_norms`, at the end of the file).
 
 Drop-in for the reference's `torch.optim.Adam(model.module.transformer.parameters(), lr=args.lr)` (ref/train.py:28): same
 constructor arguments, same update rule (no amsgrad, L2 weight decay), `param_groups` / LR schedulers / `zero_grad` /
@@ -19,7 +19,9 @@ latency-bound encoder backward; `step()` then updates segment 1 and joins.  Same
 every step after a change of circumstances (`_fast_ok`) run the ordinary way.  Measured on configs[1] (one MI355X): 6.67 ms/step
 against 6.63 without -- the co-running streaming kernel slows the chain by as much as it hides -- so nothing turns it on by default.
 """
+import contextlib
 import math
+import struct
 import weakref
 
 import torch
@@ -618,6 +620,254 @@ class FusedAdafactor(Optimizer):
         super().load_state_dict(state_dict)
         self._flat_live = False
         self._steps = 0
+
+
+# ---- exponential moving average of the weights (csrc/ema.hip) ---------------------------------------------------------------------
+def _as_f32(x):
+    """the double x rounded to the nearest f32, as a Python float: the scalar the kernel receives"""
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+class WeightEMA:
+    """Exponential moving average ("shadow") of the trainable weights, updated after every optimizer step; validation, `generate`,
+    `score` and `save()` then run on the averaged weights inside `average_parameters()`:
+
+        ema = WeightEMA(model, decay=0.999, warmup=True)
+        ...
+        opt.step(); ema.update()
+        with ema.average_parameters():     # the averaged weights are the model's weights inside
+            val_loss = model(...); caps = model.generate(...); model.save("ema.pth")
+
+    `model` is a klab MyModel (its `.transformer` is tracked; a DDP wrapper is looked through), any `nn.Module`, or an iterable of
+    parameters.  Parameters that do not require a gradient are left out, a tied tensor is tracked once.  The shadow is fp32 and
+    starts as a copy of the parameters at construction.  The rule of `update()`:
+
+        num_updates += 1
+        decay_t = min(decay, (1 + num_updates) / (10 + num_updates))   with warmup, else decay
+        w = float32(1.0 - decay_t)                                      formed in double
+        shadow = shadow + w * (param - shadow)                          per element, in fp32
+
+    `decay` has to lie in [0, 1).
+
+    Fused path.  When the tracked parameters are exactly the trainable T5 of one bound klab MyModel (`FusedAdam`'s ownership test
+    without its conditions on gradients: the average reads none), the shadow lives in ONE flat fp32 buffer shaped like the model's
+    flat gradient buffer, `update()` is ONE launch whatever the number of tensors, and so is `swap()` -- and with it entering and
+    leaving `average_parameters()`.  The swap exchanges the bits of parameters and shadow in place and rewrites the compute-dtype
+    copies the forward's GEMMs read, so neither the first forward on the averaged weights nor the first one back on the raw
+    weights pays the fp32 -> bf16 cast that `p.copy_()` would cause.  Both calls first order the current stream behind a pending
+    in-backward optimizer update.
+
+    In every other situation (the model is not bound yet, a foreign module, CPU tensors, parameters that are not exactly the
+    trainable T5) the same rule runs per parameter in plain torch on per-parameter shadows; `_fb_reason` says why.  The state
+    moves into the flat buffer at the first `update()` / `swap()` at which the fused path applies -- normally the first update,
+    since the average is built before the first forward binds the engine -- and back when it stops applying.  A re-bind to
+    another batch shape keeps the flat state (same tensors, same layout); a move of the model to another device moves the
+    shadow with it.
+
+    While the averaged weights are swapped in, the shadow holds the raw weights: `update()`, `state_dict()` and
+    `load_state_dict()` raise RuntimeError.  `average_parameters()` swaps back when its body raises and is not re-entrant.
+    Training inside the context is not supported.
+
+    `state_dict()` is {"decay", "warmup", "num_updates", "shadow": {state-dict name: fp32 copy}}; for a module the names are those
+    of its `state_dict()`, tied aliases included, so `model.transformer.load_state_dict(sd["shadow"])` works when every parameter
+    is tracked.  `load_state_dict` is the inverse, before or after the model is bound and across the two forms.
+
+    Data parallelism needs nothing: every rank holds the same weights and so computes the same average."""
+
+    def __init__(self, model, decay=0.999, warmup=True):
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:  # (NaN fails too)
+            raise ValueError(f"Invalid decay value: {decay}")
+        self.decay, self.warmup, self.num_updates = decay, bool(warmup), 0
+        if isinstance(model, torch.nn.Module):
+            core = getattr(model, "module", model)
+            tree = core.transformer if hasattr(core, "_engine") and hasattr(core, "transformer") else model
+            named = list(tree.named_parameters())  # (lists a shared tensor once)
+            every = list(tree.named_parameters(remove_duplicate=False))
+        else:
+            named, seen = [], set()
+            for p in ([model] if isinstance(model, torch.Tensor) else model):
+                if id(p) not in seen:
+                    seen.add(id(p))
+                    named.append((str(len(named)), p))
+            every = named
+        named = [(n, p) for n, p in named if p.requires_grad]
+        if not named:
+            raise ValueError("WeightEMA: no parameter requires a gradient")
+        self._params = [p for _n, p in named]
+        index = {id(p): i for i, p in enumerate(self._params)}
+        self._names = [(n, index[id(p)]) for n, p in every if id(p) in index]  # every state-dict name of every tracked tensor
+        with torch.no_grad():
+            self._shadow = [p.detach().to(torch.float32, copy=True) for p in self._params]  # torch form; None while the flat buffer is live
+        self._flat = None     # fused form: one fp32 buffer laid out like the owner's _flat["main"] ...
+        self._offs = None     # ... and each tracked tensor's offset into it
+        self._owner = None
+        self._checked = None  # the binding (and gradient views) whose optimizer table was compared with the tracked tensors
+        self._raw = None      # torch form, while swapped: the raw weights
+        self._swapped = False
+        self._fb_reason = None
+
+    # ---- which form applies ---------------------------------------------------------------------------------------------------
+    def _fast_ok(self):
+        """(model, None) when the one-launch path applies, else (None, reason)"""
+        owner = None
+        for p in self._params:
+            ref = getattr(p, "_klab_owner", None)
+            m = ref() if ref is not None else None
+            if m is None or (owner is not None and m is not owner):
+                return None, "parameters not owned by one klab MyModel"
+            owner = m
+        model = owner
+        flat = model._flat.get("main")
+        if flat is None or model._engine.shape is None or model._bound_key is None:
+            return None, "engine not bound yet"
+        if any(p.device != flat.device or p.dtype != torch.float32 for p in self._params):
+            return None, "parameters are not fp32 tensors on the engine's device"
+        model._grad_targets()  # builds the parameter -> flat-buffer views if no backward has run yet
+        views = {id(p) for p, _v, mn in model._views if mn == "main"}
+        mine = {id(p) for p in self._params}
+        if mine != {id(p) for p in model.transformer.ordered() if p.requires_grad} or views != mine:
+            return None, "not exactly the trainable T5 parameters"
+        key = (model._bound_key, model._views)
+        if self._checked is None or self._checked[0] != key[0] or self._checked[1] is not key[1]:
+            try:
+                ptrs, _n0 = model._engine.adam_layout()
+            except NotImplementedError:
+                return None, "the engine's optimizer table is unusable"
+            if sorted(ptrs) != sorted(p.data_ptr() for p in self._params):
+                return None, "the engine's optimizer table does not list exactly these tensors"
+            self._checked = key
+        return model, None
+
+    def _slices(self):
+        return [self._flat[off:off + p.numel()].view(p.shape) for p, off in zip(self._params, self._offs)]
+
+    def _attach(self, model):
+        """per-parameter shadows -> one flat buffer in the layout of the model's flat gradient buffer"""
+        offs = {id(p): v.storage_offset() for p, v, mn in model._views if mn == "main"}
+        self._flat = torch.zeros_like(model._flat["main"])
+        self._offs = [offs[id(p)] for p in self._params]
+        for dst, src in zip(self._slices(), self._shadow):
+            dst.copy_(src)
+        self._shadow = None
+        self._owner = weakref.ref(model)
+
+    def _detach(self):
+        """flat buffer -> per-parameter shadows, on the parameters' devices"""
+        self._shadow = [s.to(p.device, copy=True) for s, p in zip(self._slices(), self._params)]
+        self._flat = self._offs = self._owner = None
+
+    def _form(self):
+        """the model of the fused path, or None for the torch path; the state moves to that form unless the averaged weights are
+        swapped in (the way out of a swap is the way in)"""
+        model, why = self._fast_ok()
+        if self._swapped:
+            return model if self._flat is not None else None
+        if model is not None and self._flat is not None and (self._owner() is not model or self._flat.shape != model._flat["main"].shape
+                                                            or self._flat.device != model._flat["main"].device):
+            self._detach()
+        if model is not None and self._flat is None:
+            self._attach(model)
+        elif model is None and self._flat is not None:
+            self._detach()
+        self._fb_reason = why
+        return model
+
+    def _not_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError(f"WeightEMA.{what} while the averaged weights are swapped in (the shadow holds the raw weights): leave "
+                               f"average_parameters() / call swap() first")
+
+    # ---- the interface --------------------------------------------------------------------------------------------------------
+    def decay_at(self, num_updates):
+        """decay_t of update number `num_updates` (1-based)"""
+        return min(self.decay, (1.0 + num_updates) / (10.0 + num_updates)) if self.warmup else self.decay
+
+    @torch.no_grad()
+    def update(self):
+        """one step of the rule above; call it after every optimizer step"""
+        self._not_swapped("update()")
+        model = self._form()
+        self.num_updates += 1
+        w = _as_f32(1.0 - self.decay_at(self.num_updates))
+        if model is not None:
+            model._join_pending_update()
+            with torch.cuda.device(self._flat.device):
+                model._engine.ema_update(self._flat, w)
+            return
+        for i, p in enumerate(self._params):
+            s = self._shadow[i]
+            if s.device != p.device:
+                s = self._shadow[i] = s.to(p.device)
+            s.add_(p.detach().to(torch.float32) - s, alpha=w)
+
+    @torch.no_grad()
+    def swap(self):
+        """exchange parameters and shadow: the first call puts the averaged weights into the model, the second the raw ones back,
+        bit for bit"""
+        model = self._form()
+        if self._flat is not None and model is not None:
+            model._join_pending_update()
+            with torch.cuda.device(self._flat.device):
+                model._engine.ema_swap(self._flat)
+            model._note_optimizer_step()  # the compute-dtype copies are those of the weights now in place
+        elif self._flat is not None:  # swapped in by the kernel, and the fused path is gone: the same exchange tensor by tensor
+            for p, s in zip(self._params, self._slices()):
+                tmp = p.detach().to(s.device, copy=True)
+                p.copy_(s)
+                s.copy_(tmp)
+        elif not self._swapped:
+            self._raw = [p.detach().clone() for p in self._params]
+            for p, s in zip(self._params, self._shadow):
+                p.copy_(s)
+        else:
+            for p, r in zip(self._params, self._raw):
+                p.copy_(r)
+            self._raw = None
+        self._swapped = not self._swapped
+
+    @contextlib.contextmanager
+    def average_parameters(self):
+        """context in which the averaged weights are the model's weights; the raw ones come back bit for bit, on exceptions too"""
+        if self._swapped:
+            raise RuntimeError("WeightEMA.average_parameters() is not re-entrant: the averaged weights are already swapped in")
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    @torch.no_grad()
+    def state_dict(self):
+        self._not_swapped("state_dict()")
+        self._form()
+        vals = self._slices() if self._flat is not None else self._shadow
+        copies = [v.detach().clone() for v in vals]
+        return {"decay": self.decay, "warmup": self.warmup, "num_updates": self.num_updates,
+                "shadow": {name: copies[i] for name, i in self._names}}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        self._not_swapped("load_state_dict()")
+        shadow = state_dict["shadow"]
+        first = {}
+        for name, i in self._names:
+            if name in shadow:
+                first.setdefault(i, name)
+        missing = [name for name, i in self._names if i not in first]
+        if missing:
+            raise KeyError(f"WeightEMA.load_state_dict: missing shadow key(s) {missing[:5]}{'...' if len(missing) > 5 else ''}")
+        self._form()
+        vals = self._slices() if self._flat is not None else self._shadow
+        for i, v in enumerate(vals):
+            src = shadow[first[i]]
+            if tuple(src.shape) != tuple(v.shape):
+                raise RuntimeError(f"size mismatch for {first[i]}: saved {tuple(src.shape)} vs tracked {tuple(v.shape)}")
+            v.copy_(src)
+        decay = float(state_dict["decay"])
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"Invalid decay value: {decay}")
+        self.decay, self.warmup, self.num_updates = decay, bool(state_dict["warmup"]), int(state_dict["num_updates"])
 
 
 # ---- gradient-norm clipping (csrc/grad_clip.hip) ------------------------------------------------------------------------------------
