@@ -276,6 +276,21 @@ size_t klab_image_preprocess_ws_bytes(int n_images, int max_h, int mid);
 int klab_image_preprocess(const unsigned char* src, const klab_image_desc* desc_dev, int n_images, int max_h, int max_w, int mid,
                           int out_size, int filter_a, int filter_b, double rescale, const float* mean3, const float* std3,
                           float* pixel_values, void* ws, size_t ws_bytes, void* stream);
+/* The same pipeline on a sub-rectangle of every image, mirrored left-right where asked: train-time random-resized-crop + flip.
+ * Image i gives exactly `im.crop((left, top, left + w, top + h)).resize((mid, mid), filter_a)`, then
+ * `.transpose(FLIP_LEFT_RIGHT)` when bit 0 of `flags` is set, then the processor's part as above.  Crop, THEN resize: the filter
+ * taps are clamped at the crop's edges (Pillow's `resize(box=...)` reads outside the box and gives other bytes).  No pixel is
+ * copied for the crop and the launches are the three of `klab_image_preprocess`:
+ *   offset: byte offset in `src` of the crop's first pixel = image offset + (top * pitch + left) * 3;  height, width: the crop's;
+ *   pitch: pixels from one source row to the next (the image's width).  The caller keeps the crop inside its image.
+ *   max_crop_h / max_crop_w: the largest crop of the batch; they size the workspace (`klab_image_preprocess_ws_bytes(n,
+ *   max_crop_h, mid)`), the grid and the weight tables, so an image too wide for the un-cropped call is taken with a crop that
+ *   fits.  filter_a must be 2 or 3.                                                                                           */
+#define KLAB_IMAGE_FLIP_LR 1
+typedef struct klab_image_crop_desc { long long offset; int height, width, pitch, flags; } klab_image_crop_desc;
+int klab_image_preprocess_crop(const unsigned char* src, const klab_image_crop_desc* desc_dev, int n_images, int max_crop_h,
+                               int max_crop_w, int mid, int out_size, int filter_a, int filter_b, double rescale, const float* mean3,
+                               const float* std3, float* pixel_values, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- JPEG decoding (row f-1: `Image.open(path).convert('RGB')`, ref/modules/loader.py:15) -------------------------------
  * Hybrid decoder for baseline / extended-sequential / progressive 8-bit Huffman JPEG (SOF0 / SOF1 / SOF2; grey, or three

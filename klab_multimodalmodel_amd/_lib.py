@@ -207,6 +207,7 @@ SIGNATURES = {
     "klab_segv_trace_install": [i32],
     "klab_segv_set_context": [C.c_char_p],
     "klab_image_preprocess": [vp, vp, i32, i32, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, C.c_size_t, vp],
+    "klab_image_preprocess_crop": [vp, vp, i32, i32, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, C.c_size_t, vp],
     "klab_jpeg_read_info": [vp, C.c_size_t, vp],
     "klab_jpeg_entropy_decode": [vp, C.c_size_t, vp, vp, vp],
     "klab_jpeg_entropy_decode_batch": [vp, vp, i32, vp, vp, vp, vp, i32],

@@ -8,6 +8,8 @@
 // (round-half-away), and every pass (horizontal first, then vertical) accumulates from 1 << 21, shifts by 22 and clamps to
 // uint8.  The weights are recomputed here per workgroup with the same double-precision operations in the same order
 // (contraction off: no FMA), so every intermediate uint8 image equals Pillow's.  This is HBM-bound byte work: no MFMA.
+// [h, w] is the whole image (klab_image_preprocess) or a crop of it read in place through a row pitch, optionally mirrored
+// left-right by the horizontal pass's store (klab_image_preprocess_crop): crop().resize().transpose(FLIP_LEFT_RIGHT).
 //   resample_h_kernel : [h, w, 3] u8 -> [h, mid, 3] u8      one thread per output column, weights in an LDS column, 16 rows per block
 //   resample_v_kernel : [h, mid, 3] u8 -> [mid, mid, 3] u8  8 output rows per block, byte-coalesced over the row
 //   resize_norm_kernel: [mid, mid, 3] u8 -> pixel_values [3, out, out] f32: both passes of the second resize through an LDS
@@ -71,14 +73,25 @@ __device__ __forceinline__ unsigned char clip8(int v) {
 }
 
 struct ImgP {
-  const unsigned char* src; const klab_image_desc* desc; unsigned char* tmp; unsigned char* mid_img;
-  int n, max_h, mid, filter_a, kmax;
+  const unsigned char* src; const void* desc; unsigned char* tmp; unsigned char* mid_img;
+  int n, max_h, mid, filter_a, kmax;  // max_h: the tallest source rectangle of the batch (rows of `tmp` per image)
 };
 
+// The source rectangle of image i: the whole image (klab_image_desc: pitch = width, no flip) or a crop of it
+// (klab_image_crop_desc).  Both resizes see only this rectangle -- crop, then resize: the taps are clamped at ITS edges.
+template <bool CROP> __device__ __forceinline__ klab_image_crop_desc load_rect(const void* desc, int i) {
+  if constexpr (CROP) {
+    return static_cast<const klab_image_crop_desc*>(desc)[i];
+  } else {
+    const klab_image_desc d = static_cast<const klab_image_desc*>(desc)[i];
+    return klab_image_crop_desc{d.offset, d.height, d.width, d.width, 0};
+  }
+}
+
 constexpr int HROWS = 16;
-__global__ __launch_bounds__(256) void resample_h_kernel(ImgP p) {
+template <bool CROP> __global__ __launch_bounds__(256) void resample_h_kernel(ImgP p) {
   extern __shared__ int lds_h[];  // k[kmax][mid] | lo[mid] | n[mid]
-  const klab_image_desc d = p.desc[blockIdx.y];
+  const klab_image_crop_desc d = load_rect<CROP>(p.desc, blockIdx.y);
   const int y0 = blockIdx.x * HROWS;
   if (y0 >= d.height) return;
   const int mid = p.mid;
@@ -93,16 +106,20 @@ __global__ __launch_bounds__(256) void resample_h_kernel(ImgP p) {
   const unsigned char* src = p.src + d.offset;
   unsigned char* dst = p.tmp + (size_t)blockIdx.y * p.max_h * mid * 3;
   const int y1 = y0 + HROWS < d.height ? y0 + HROWS : d.height;
+  // the flip mirrors the STORE (= resize, then flip: the vertical pass is column-wise).  Mirroring the weight table instead
+  // would not be exact: Pillow's double-precision weights of xx and of mid - 1 - xx need not round to the same integers.
+  const bool flip = (d.flags & KLAB_IMAGE_FLIP_LR) != 0;
   for (int xx = threadIdx.x; xx < mid; xx += 256) {
     const int l = lo[xx], n = nn[xx];
+    const int xo = flip ? mid - 1 - xx : xx;
     for (int y = y0; y < y1; ++y) {
-      const unsigned char* row = src + ((size_t)y * d.width + l) * 3;
+      const unsigned char* row = src + ((size_t)y * d.pitch + l) * 3;
       int s0 = 1 << (PBITS - 1), s1 = s0, s2 = s0;
       for (int t = 0; t < n; ++t) {
         const int k = kk[t * mid + xx];
         s0 += row[t * 3] * k; s1 += row[t * 3 + 1] * k; s2 += row[t * 3 + 2] * k;
       }
-      unsigned char* o = dst + ((size_t)y * mid + xx) * 3;
+      unsigned char* o = dst + ((size_t)y * mid + xo) * 3;
       o[0] = clip8(s0); o[1] = clip8(s1); o[2] = clip8(s2);
     }
   }
@@ -110,9 +127,9 @@ __global__ __launch_bounds__(256) void resample_h_kernel(ImgP p) {
 
 // vertical pass: 8 output rows per block; a thread owns 4 consecutive bytes of the row (one 32-bit load per source row)
 constexpr int VROWS = 8;
-__global__ __launch_bounds__(256) void resample_v_kernel(ImgP p) {
+template <bool CROP> __global__ __launch_bounds__(256) void resample_v_kernel(ImgP p) {
   extern __shared__ __attribute__((aligned(16))) int lds_v[];  // k[VROWS][kmax] | lo[VROWS] | n[VROWS]
-  const klab_image_desc d = p.desc[blockIdx.y];
+  const klab_image_crop_desc d = load_rect<CROP>(p.desc, blockIdx.y);
   const int mid = p.mid, y0 = blockIdx.x * VROWS;
   int* kk = lds_v;
   int* lo = kk + VROWS * p.kmax;
@@ -228,9 +245,12 @@ extern "C" size_t klab_image_preprocess_ws_bytes(int n_images, int max_h, int mi
   return al256((size_t)n_images * max_h * mid * 3) + al256((size_t)n_images * mid * mid * 3);
 }
 
-extern "C" int klab_image_preprocess(const unsigned char* src, const klab_image_desc* desc_dev, int n_images, int max_h, int max_w, int mid,
-                                     int out_size, int filter_a, int filter_b, double rescale, const float* mean3, const float* std3,
-                                     float* pixel_values, void* ws, size_t ws_bytes, void* stream) {
+// max_h / max_w bound the source rectangles of the batch (whole images, or crops): they size the workspace, the grid and the
+// two tap counts, so an image too wide for the weight table is still taken with a crop that fits
+template <bool CROP>
+static int image_preprocess(const unsigned char* src, const void* desc_dev, int n_images, int max_h, int max_w, int mid, int out_size,
+                            int filter_a, int filter_b, double rescale, const float* mean3, const float* std3, float* pixel_values,
+                            void* ws, size_t ws_bytes, void* stream) {
   if (!src || !pixel_values || !mean3 || !std3 || n_images <= 0 || mid <= 0 || out_size <= 0) return KLAB_ERR_BADARG;
   if ((filter_a != 0 && filter_a != 2 && filter_a != 3) || (filter_b != 2 && filter_b != 3)) return KLAB_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
@@ -239,19 +259,19 @@ extern "C" int klab_image_preprocess(const unsigned char* src, const klab_image_
     if (!desc_dev || !ws || max_h <= 0 || max_w <= 0) return KLAB_ERR_BADARG;
     if (ws_bytes < klab_image_preprocess_ws_bytes(n_images, max_h, mid)) return KLAB_ERR_BADARG;
     ImgP p{src, desc_dev, (unsigned char*)ws, (unsigned char*)ws + al256((size_t)n_images * max_h * mid * 3), n_images, max_h, mid, filter_a, 0};
-    // the widest / tallest image bounds every image's tap count
+    // the widest / tallest source rectangle bounds every image's tap count
     const int kh = pil_ksize(max_w, mid, filter_a), kv = pil_ksize(max_h, mid, filter_a);
     p.kmax = kh;
     const size_t lds_h = ((size_t)kh * mid + 2 * (size_t)mid) * 4;
     if (lds_h > 128 * 1024) return KLAB_ERR_UNSUPPORTED;  // > ~30x reduction of the width
-    int rc = ensure_dyn_lds(reinterpret_cast<const void*>(resample_h_kernel), lds_h);
+    int rc = ensure_dyn_lds(reinterpret_cast<const void*>(resample_h_kernel<CROP>), lds_h);
     if (rc) return rc;
-    hipLaunchKernelGGL(resample_h_kernel, dim3((max_h + HROWS - 1) / HROWS, n_images), dim3(256), lds_h, s, p);
+    hipLaunchKernelGGL(resample_h_kernel<CROP>, dim3((max_h + HROWS - 1) / HROWS, n_images), dim3(256), lds_h, s, p);
     KLAB_LAUNCH_CHECK();
     p.kmax = kv;
     const size_t lds_v = ((size_t)VROWS * kv + 2 * VROWS) * 4;
     if (lds_v > 64 * 1024) return KLAB_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(resample_v_kernel, dim3((mid + VROWS - 1) / VROWS, n_images), dim3(256), lds_v, s, p);
+    hipLaunchKernelGGL(resample_v_kernel<CROP>, dim3((mid + VROWS - 1) / VROWS, n_images), dim3(256), lds_v, s, p);
     KLAB_LAUNCH_CHECK();
     mid_img = p.mid_img;
   }
@@ -269,4 +289,20 @@ extern "C" int klab_image_preprocess(const unsigned char* src, const klab_image_
   hipLaunchKernelGGL(resize_norm_kernel, dim3((out_size + q.tr - 1) / q.tr, n_images), dim3(256), lds_n, s, q);
   KLAB_LAUNCH_CHECK();
   return KLAB_OK;
+}
+
+extern "C" int klab_image_preprocess(const unsigned char* src, const klab_image_desc* desc_dev, int n_images, int max_h, int max_w, int mid,
+                                     int out_size, int filter_a, int filter_b, double rescale, const float* mean3, const float* std3,
+                                     float* pixel_values, void* ws, size_t ws_bytes, void* stream) {
+  return image_preprocess<false>(src, desc_dev, n_images, max_h, max_w, mid, out_size, filter_a, filter_b, rescale, mean3, std3,
+                                 pixel_values, ws, ws_bytes, stream);
+}
+
+extern "C" int klab_image_preprocess_crop(const unsigned char* src, const klab_image_crop_desc* desc_dev, int n_images, int max_crop_h,
+                                          int max_crop_w, int mid, int out_size, int filter_a, int filter_b, double rescale,
+                                          const float* mean3, const float* std3, float* pixel_values, void* ws, size_t ws_bytes,
+                                          void* stream) {
+  if (filter_a == 0) return KLAB_ERR_BADARG;  // a crop belongs to the first resize: without it there is nothing to crop
+  return image_preprocess<true>(src, desc_dev, n_images, max_crop_h, max_crop_w, mid, out_size, filter_a, filter_b, rescale, mean3,
+                                std3, pixel_values, ws, ws_bytes, stream);
 }

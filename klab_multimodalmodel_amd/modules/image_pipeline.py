@@ -19,7 +19,13 @@ reference effectively does) and normalisation (`csrc/image_pre.hip`).  Entry poi
 
 Both return {"pixel_values": cuda float32 [B, 3, 224, 224]} -- what `MyModel.forward` takes.  No CPU fallback: without the HIP
 library the call raises.
+
+Train-time augmentation (`from_decoded` / `from_jpeg` only): `boxes=` ([n, 4] of top, left, h, w), `flips=` ([n] bool) or
+`augment=RandomResizedCropFlip(...)` put a random resized crop and a horizontal flip where the reference loader resizes --
+`im.crop(box).resize((256, 256))`, then `im.transpose(FLIP_LEFT_RIGHT)` -- inside the same three launches, bit for bit.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -39,6 +45,94 @@ class BatchFeature(dict):
             return self[k]
         except KeyError as e:
             raise AttributeError(k) from e
+
+
+class RandomResizedCropFlip:
+    """`torchvision.transforms.RandomResizedCrop.get_params` followed by `RandomHorizontalFlip`'s coin, draw for draw, as boxes and
+    flags for `GpuImageProcessor.from_decoded / from_jpeg(augment=...)`.  All draws come from `generator` (torch's global CPU
+    generator when None), image by image: the box of image 0, its flip, the box of image 1, ... so a seed fixes the batch."""
+
+    def __init__(self, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5, generator=None):
+        for name, v in (("scale", scale), ("ratio", ratio)):
+            if len(v) != 2 or not all(math.isfinite(x) for x in v) or not 0 < v[0] <= v[1]:
+                raise ValueError(f"{name} must be (min, max) with 0 < min <= max, got {v!r}")
+        if not 0 <= flip_p <= 1:
+            raise ValueError(f"flip_p must lie in [0, 1], got {flip_p!r}")
+        self.scale, self.ratio = (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1]))
+        self.flip_p, self.generator = float(flip_p), generator
+
+    def _box(self, height, width):
+        g = self.generator
+        area = height * width
+        log_ratio = torch.log(torch.tensor(self.ratio))
+        for _ in range(10):
+            target_area = area * torch.empty(1).uniform_(self.scale[0], self.scale[1], generator=g).item()
+            aspect = torch.exp(torch.empty(1).uniform_(log_ratio[0], log_ratio[1], generator=g)).item()
+            w = int(round(math.sqrt(target_area * aspect)))
+            h = int(round(math.sqrt(target_area / aspect)))
+            if 0 < w <= width and 0 < h <= height:
+                top = torch.randint(0, height - h + 1, size=(1,), generator=g).item()
+                left = torch.randint(0, width - w + 1, size=(1,), generator=g).item()
+                return top, left, h, w
+        in_ratio = float(width) / float(height)  # no try fitted: the central crop
+        if in_ratio < min(self.ratio):
+            w = width
+            h = int(round(w / min(self.ratio)))
+        elif in_ratio > max(self.ratio):
+            h = height
+            w = int(round(h * max(self.ratio)))
+        else:
+            w, h = width, height
+        return (height - h) // 2, (width - w) // 2, h, w
+
+    def sample(self, sizes):
+        """sizes: list of (height, width) -> (boxes int64 [n, 4] of top, left, h, w; flips bool [n]), CPU tensors"""
+        boxes = torch.zeros(len(sizes), 4, dtype=torch.int64)
+        flips = torch.zeros(len(sizes), dtype=torch.bool)
+        for i, (height, width) in enumerate(sizes):
+            boxes[i] = torch.tensor(self._box(int(height), int(width)))
+            flips[i] = bool(torch.rand(1, generator=self.generator) < self.flip_p)
+        return boxes, flips
+
+
+def resolve_augment(sizes, boxes=None, flips=None, augment=None):
+    """Host-side check of the augmentation arguments against the batch's `sizes` (list of (height, width)), before anything is
+    enqueued.  Returns (None, None) when none is given -- the un-augmented call -- else (boxes int64 numpy [n, 4], flips bool numpy
+    [n]), a missing one filled with the whole image / no flip.  A violation raises ValueError naming the image."""
+    if augment is not None:
+        if boxes is not None or flips is not None:
+            raise ValueError("augment= draws the boxes and flips itself: pass either augment or boxes / flips")
+        boxes, flips = augment.sample([(int(h), int(w)) for h, w in sizes])
+    if boxes is None and flips is None:
+        return None, None
+    n = len(sizes)
+    if boxes is None:
+        b = np.array([(0, 0, h, w) for h, w in sizes], np.int64).reshape(n, 4)
+    else:
+        b = boxes.detach().cpu().numpy() if isinstance(boxes, torch.Tensor) else np.asarray(boxes)
+        if b.shape != (n, 4):
+            raise ValueError(f"boxes must be [{n}, 4] rows of (top, left, h, w), got shape {tuple(b.shape)}")
+        if b.dtype.kind not in "iu":
+            raise ValueError(f"boxes must be integers, got {b.dtype}")
+        b = b.astype(np.int64)
+    if flips is None:
+        f = np.zeros(n, bool)
+    else:
+        f = flips.detach().cpu().numpy() if isinstance(flips, torch.Tensor) else np.asarray(flips)
+        if f.shape != (n,):
+            raise ValueError(f"flips must be [{n}] booleans, got shape {tuple(f.shape)}")
+        if f.dtype != bool:
+            raise ValueError(f"flips must be booleans, got {f.dtype}")
+    sz = np.asarray([(int(h), int(w)) for h, w in sizes], np.int64).reshape(n, 2)
+    empty = (b[:, 2] < 1) | (b[:, 3] < 1)
+    outside = (b[:, 0] < 0) | (b[:, 1] < 0) | (b[:, 0] + b[:, 2] > sz[:, 0]) | (b[:, 1] + b[:, 3] > sz[:, 1])
+    if (empty | outside).any():
+        i = int(np.flatnonzero(empty | outside)[0])
+        box = tuple(int(v) for v in b[i])
+        if empty[i]:
+            raise ValueError(f"image {i}: empty crop box (top, left, h, w) = {box}")
+        raise ValueError(f"image {i}: crop box (top, left, h, w) = {box} leaves the {sz[i, 0]} x {sz[i, 1]} image")
+    return b, f
 
 
 class GpuImageProcessor:
@@ -112,13 +206,22 @@ class GpuImageProcessor:
                              mean=self.mean, std=self.std)
         return BatchFeature(pixel_values=pv)
 
-    def from_decoded(self, images):
-        """list of decoded RGB images (HWC uint8 numpy arrays, PIL images or tensors) of any size"""
+    def _augmented(self, pv, boxes, flips, sampled):
+        out = BatchFeature(pixel_values=pv)
+        if sampled:  # what was drawn, for logging and replay through boxes= / flips=
+            out["crop_boxes"], out["flips"] = torch.from_numpy(boxes.copy()), torch.from_numpy(flips.copy())
+        return out
+
+    def from_decoded(self, images, boxes=None, flips=None, augment=None):
+        """list of decoded RGB images (HWC uint8 numpy arrays, PIL images or tensors) of any size.  boxes ([n, 4] ints: top, left,
+        h, w) / flips ([n] bools), or augment (a RandomResizedCropFlip that draws both; the result then also carries `crop_boxes`
+        and `flips`): image i is cropped to its box before the loader's resize and mirrored left-right after it."""
         arrs = [np.asarray(im.convert("RGB") if hasattr(im, "convert") else im, dtype=np.uint8) for im in images]
         for a in arrs:
             if a.ndim != 3 or a.shape[2] != 3:
                 raise ValueError("expected HWC RGB uint8 images")
         n = len(arrs)
+        boxes, flips = resolve_augment([a.shape[:2] for a in arrs], boxes, flips, augment)
         sizes = [a.shape[0] * a.shape[1] * 3 for a in arrs]
         offs = np.concatenate([[0], np.cumsum([(s + 15) // 16 * 16 for s in sizes])]).astype(np.int64)
         total = int(offs[-1])
@@ -143,18 +246,24 @@ class GpuImageProcessor:
         ev[self._flip] = torch.cuda.Event()
         ev[self._flip].record()
         self._stage_ev = ev
-        dd = torch.from_numpy(desc).to(self.device)
         pv = self._out(n)
-        ops.image_preprocess(src, dd, n, max(a.shape[0] for a in arrs), max(a.shape[1] for a in arrs), pv, mid=self.loader_size,
-                             out=self.size, filter_a=self.loader_resample, filter_b=self.resample, rescale=self.rescale, mean=self.mean,
-                             std=self.std)
+        kw = dict(mid=self.loader_size, out=self.size, filter_a=self.loader_resample, filter_b=self.resample, rescale=self.rescale,
+                  mean=self.mean, std=self.std)
+        if boxes is not None:  # the crops are read in place: the whole images are staged as above, the descriptor points into them
+            cd = ops.image_crop_desc(offs[:n], [a.shape[:2] for a in arrs], boxes, flips)
+            ops.image_preprocess_crop(src, torch.from_numpy(cd).to(self.device), n, int(boxes[:, 2].max()), int(boxes[:, 3].max()), pv, **kw)
+            return self._augmented(pv, boxes, flips, augment is not None)
+        dd = torch.from_numpy(desc).to(self.device)
+        ops.image_preprocess(src, dd, n, max(a.shape[0] for a in arrs), max(a.shape[1] for a in arrs), pv, **kw)
         return BatchFeature(pixel_values=pv)
 
-    def from_jpeg(self, files, n_threads=None, other_formats="raise"):
+    def from_jpeg(self, files, n_threads=None, other_formats="raise", boxes=None, flips=None, augment=None):
         """list of image files (paths, bytes or binary file objects) -> pixel_values; `Image.open(f).convert('RGB')` + from_decoded.
         Files the device decoder does not take (CMYK / 12-bit / arithmetic-coded JPEG, PNG, ...): other_formats="raise" (default)
         raises NotImplementedError naming them; other_formats="host" -- an explicit request, never a silent fallback -- decodes
-        exactly those files with PIL on the host and sends them through the same device resize (`from_decoded`)."""
+        exactly those files with PIL on the host and sends them through the same device resize (`from_decoded`).
+        boxes / flips / augment: as in `from_decoded`, against the sizes in the files' headers; the whole image is decoded on the
+        device and the crop is read out of it in place."""
         if other_formats not in ("raise", "host"):
             raise ValueError("other_formats must be 'raise' or 'host'")
         datas = []
@@ -170,28 +279,57 @@ class GpuImageProcessor:
             import os
             n_threads = min(16, os.cpu_count() or 1)
         n = len(datas)
+        aug = boxes is not None or flips is not None or augment is not None
         dev_idx, host_idx = list(range(n)), []
+        sizes = [None] * n  # (height, width) from the headers: read for the host route, and to check the boxes before any launch
         if other_formats == "host":
             dev_idx = []
             for i, d in enumerate(datas):
                 try:
-                    ok = bool(ops.jpeg_read_info(d).supported)
+                    info = ops.jpeg_read_info(d)
+                    ok, sizes[i] = bool(info.supported), (info.height, info.width)
                 except ValueError:  # not a JPEG stream at all
                     ok = False
                 (dev_idx if ok else host_idx).append(i)
-        pv = self._out(n)
-        if dev_idx:
-            sub = [datas[i] for i in dev_idx]
-            rgb, desc, items = ops.jpeg_decode_pipelined(sub, self.device, n_threads)
-            out = pv if not host_idx else self._out(len(sub))
-            ops.image_preprocess(rgb, desc, len(sub), max(it.info.height for it in items), max(it.info.width for it in items), out,
-                                 mid=self.loader_size, out=self.size, filter_a=self.loader_resample, filter_b=self.resample,
-                                 rescale=self.rescale, mean=self.mean, std=self.std)
-            if host_idx:
-                pv[torch.tensor(dev_idx, device=self.device)] = out
+        host_imgs = []
         if host_idx:
             import io
             from PIL import Image
-            dec = self.from_decoded([Image.open(io.BytesIO(datas[i])).convert("RGB") for i in host_idx])["pixel_values"]
-            pv[torch.tensor(host_idx, device=self.device)] = dec
+            host_imgs = [Image.open(io.BytesIO(datas[i])) for i in host_idx]
+            for i, im in zip(host_idx, host_imgs):
+                sizes[i] = (im.height, im.width)
+
+        def check(dev_sizes=()):  # every size is known: check the boxes (or draw them), before anything is enqueued
+            nonlocal boxes, flips
+            for i, hw in zip(dev_idx, dev_sizes):
+                sizes[i] = hw
+            boxes, flips = resolve_augment(sizes, boxes, flips, augment)
+
+        # other_formats="host" has read every header above; otherwise the decoder reads them, and hands the sizes over before it
+        # allocates or enqueues anything
+        hook = check if aug and dev_idx and other_formats == "raise" else None
+        if aug and hook is None:
+            check()
+        pv = self._out(n)
+        if dev_idx:
+            sub = [datas[i] for i in dev_idx]
+            rgb, desc, items = ops.jpeg_decode_pipelined(sub, self.device, n_threads, on_headers=hook)
+            out = pv if not host_idx else self._out(len(sub))
+            kw = dict(mid=self.loader_size, out=self.size, filter_a=self.loader_resample, filter_b=self.resample, rescale=self.rescale,
+                      mean=self.mean, std=self.std)
+            if aug:
+                cd = ops.image_crop_desc([it.rgb_off for it in items], [(it.info.height, it.info.width) for it in items], boxes[dev_idx],
+                                         flips[dev_idx])
+                ops.image_preprocess_crop(rgb, torch.from_numpy(cd).to(self.device), len(sub), int(boxes[dev_idx, 2].max()),
+                                          int(boxes[dev_idx, 3].max()), out, **kw)
+            else:
+                ops.image_preprocess(rgb, desc, len(sub), max(it.info.height for it in items), max(it.info.width for it in items), out, **kw)
+            if host_idx:
+                pv[torch.tensor(dev_idx, device=self.device)] = out
+        if host_idx:
+            host_imgs = [im.convert("RGB") for im in host_imgs]
+            dec = (self.from_decoded(host_imgs, boxes=boxes[host_idx], flips=flips[host_idx]) if aug else self.from_decoded(host_imgs))
+            pv[torch.tensor(host_idx, device=self.device)] = dec["pixel_values"]
+        if aug:
+            return self._augmented(pv, boxes, flips, augment is not None)
         return BatchFeature(pixel_values=pv)

@@ -661,6 +661,40 @@ def image_preprocess(src_u8, desc, n, max_h, max_w, pixel_values, *, mid=256, ou
                                       L.stream_ptr()), "klab_image_preprocess")
 
 
+IMAGE_FLIP_LR = 1  # KLAB_IMAGE_FLIP_LR
+
+
+def image_crop_desc(offsets, sizes, boxes, flips):
+    """host side of klab_image_crop_desc: int64 numpy [n, 3] rows of {offset, height | width << 32, pitch | flags << 32} for images
+    of `sizes` (height, width) at byte `offsets`, cropped to `boxes` (top, left, h, w) and mirrored where `flips`.  `top` and `left`
+    are folded into the offset; the boxes must have been checked against the sizes."""
+    import numpy as np
+    sz = np.asarray(sizes, np.int64).reshape(-1, 2)
+    b = np.asarray(boxes, np.int64).reshape(-1, 4)
+    fl = np.asarray(flips, bool).astype(np.int64) * IMAGE_FLIP_LR
+    desc = np.empty((len(sz), 3), np.int64)
+    desc[:, 0] = np.asarray(offsets, np.int64) + (b[:, 0] * sz[:, 1] + b[:, 1]) * 3
+    desc[:, 1] = b[:, 2] | (b[:, 3] << 32)
+    desc[:, 2] = sz[:, 1] | (fl << 32)
+    return desc
+
+
+def image_preprocess_crop(src_u8, desc, n, max_crop_h, max_crop_w, pixel_values, *, mid=256, out=224, filter_a=3, filter_b=2,
+                          rescale=1.0 / 255 / 255, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)):
+    """klab_image_preprocess_crop: image_preprocess on one sub-rectangle per image, mirrored where its flip bit is set.  desc:
+    device int64 [n, 3] from image_crop_desc; max_crop_h / max_crop_w: the largest crop of the batch."""
+    import torch
+    lib = L.load()
+    assert desc.dtype == torch.int64 and tuple(desc.shape) == (n, 3) and desc.is_contiguous()
+    m3 = (C.c_float * 3)(*mean)
+    s3 = (C.c_float * 3)(*std)
+    nbytes = lib.klab_image_preprocess_ws_bytes(n, max_crop_h, mid)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=src_u8.device)
+    L.check(lib.klab_image_preprocess_crop(src_u8.data_ptr(), desc.data_ptr(), n, max_crop_h, max_crop_w, mid, out, filter_a, filter_b,
+                                           rescale, C.cast(m3, C.c_void_p), C.cast(s3, C.c_void_p), pixel_values.data_ptr(),
+                                           ws.data_ptr(), nbytes, L.stream_ptr()), "klab_image_preprocess_crop")
+
+
 # ---- JPEG (row f-1): host entropy decoding + device reconstruction ---------------------------------------------------------
 def jpeg_read_info(data: bytes):
     """header of one JPEG file (host only): a _lib.JpegInfo"""
@@ -750,10 +784,11 @@ def jpeg_decode(datas, device="cuda", n_threads=8, pipelined=False):
     return out
 
 
-def jpeg_decode_pipelined(datas, device="cuda", n_threads=8, n_chunks=4):
+def jpeg_decode_pipelined(datas, device="cuda", n_threads=8, n_chunks=4, on_headers=None):
     """file bytes -> (rgb device buffer, desc device tensor [n, 2] in the klab_image_desc layout, items).  The batch is cut into
     chunks: while the host threads Huffman-decode chunk i+1, chunk i's coefficients cross PCIe and are reconstructed on the GPU
-    (the copies and kernels are asynchronous on the current stream; the host never waits for the device)."""
+    (the copies and kernels are asynchronous on the current stream; the host never waits for the device).  on_headers: called with
+    the list of (height, width) once every header is read and before anything is allocated or enqueued (a caller's own checks)."""
     import numpy as np
     import torch
     lib = L.load()
@@ -771,6 +806,8 @@ def jpeg_decode_pipelined(datas, device="cuda", n_threads=8, n_chunks=4):
         items[i].coef_block0, items[i].rgb_off = blocks, rgb_bytes
         blocks += f.coef_blocks
         rgb_bytes += (f.width * f.height * 3 + 15) // 16 * 16
+    if on_headers is not None:
+        on_headers([(it.info.height, it.info.width) for it in items])
     coefs_t = torch.empty((max(blocks, 1), 64), dtype=torch.int16, pin_memory=True)
     qt_t = torch.zeros((n, 192), dtype=torch.int16, pin_memory=True)
     coefs, qt = coefs_t.numpy(), qt_t.numpy()
