@@ -1,4 +1,4 @@
-"""Fixtures and fp64 references for tests/test_gemm_exact_gpu.py and tests/test_attn_exact_gpu.py (plain torch on the CPU;
+"""Fixtures and fp64 references for tests/test_gemm_exact_gpu.py, tests/test_attn_exact_gpu.py and tests/test_attn_fused_exact_gpu.py (plain torch on the CPU;
 tests/test_exact_fixtures_cpu.py proves what the GPU tests take for granted about them).
 
 GEMM: operands are integers in [-3, 3].  Every partial sum of a dot product is then an integer of magnitude <= 9 K < 2^24, so
@@ -13,6 +13,13 @@ the chosen keys and 0 elsewhere, and every output of forward and backward is a s
 representable in bf16 (checked in fp64 by the CPU test), so whatever a bf16 kernel stores must equal the reference bit for bit.
 A second one-hot fixture needs no bias at all (the streaming kernels' BIAS = 0 instantiations): keys are distinct +-2 sign
 codes and a query is 8 x its key, which puts every other score at least 128 below the chosen one.
+
+Attention dropout: attn_drop_mult states the mask of the probabilities on its own (element (seed, tag, slab = b H + h, q Lk + key));
+at p = 0.5 the multiplier is 0 or 2 and the dyadic fixtures stay dyadic (AttnFixture's `drop`).
+
+The fused attention sub-layer kernels (tests/test_attn_fused_exact_gpu.py) reuse AttnFixture at head dim 64 for the backward, which is
+handed dy and a signed-permutation o weight with dy @ W == rows(dO) (signed_perm, dy_for), and FusedFwdFixture for the forward: rows
+sign * 2^k and one +-1 per k-tile in every projection row make the norm, the projection and the attention exact stage by stage.
 
 Random operands: bounds are per element, the reference expression re-evaluated on absolute values times the unit roundoff of
 the format (gemm_bound, attn_fwd_bound, attn_bwd_bounds; the derivation is in DESIGN.md section 1)."""
@@ -133,6 +140,8 @@ def chosen_keys(H, Lq, Lk, n, causal):
                 start = 0
             if q == Lq - 1:
                 start = avail - 1
+            if Lq == 1:  # a single row cannot take both ends: the heads share them out
+                start = 0 if h == 0 else avail - 1 if h == H - 1 else (11 * h) % avail
             step = avail // nq
             rows.append(sorted((start + i * step) % avail for i in range(nq)))
         keys.append(rows)
@@ -157,7 +166,7 @@ class AttnFixture:
     all fp64 and exactly representable in bf16; references P, dS [B, H, Lq, Lk], ctx, lse [B, H, Lq], dq, dk, dv and
     dbias [H, Lq, Lk], exact in fp64 by construction: P is written down (1 / n on the chosen keys), not computed through exp."""
 
-    def __init__(self, kind, B, H, Lq, Lk, dk, causal=False, n=None, seed=0):
+    def __init__(self, kind, B, H, Lq, Lk, dk, causal=False, n=None, seed=0, drop=None):
         assert kind in ("onehot", "q0", "k0", "onehot_nobias")
         n = n or (1 if kind.startswith("onehot") else 2)
         assert (n == 1) == kind.startswith("onehot") and n in (1, 2, 4)
@@ -190,13 +199,18 @@ class AttnFixture:
         # the score every chosen key of a row shares (asserted by the CPU test), and with it the log-sum-exp
         chosen_score = torch.where(mask[None], self.S, -math.inf).amax(-1)
         self.lse = chosen_score + cnt[None, ..., 0].log()
-        self.ctx = self.P @ self.v
+        # drop = (seed, tag, p): the attention dropout mask M (0 or 1 / (1 - p)) on the probabilities, where the data path has it:
+        # Pm = P M feeds the context and dV, dP is masked before delta is taken off (dS = P (dP M - delta), delta from the masked ctx)
+        self.drop = drop
+        self.M = torch.ones(B, H, Lq, Lk, dtype=torch.float64) if drop is None else attn_drop_mask(*drop, B, H, Lq, Lk)
+        self.Pm = self.P * self.M
+        self.ctx = self.Pm @ self.v
         dP = self.do @ self.v.transpose(-1, -2)
         delta = (self.do * self.ctx).sum(-1, keepdim=True)
-        self.dS = self.P * (dP - delta)
+        self.dS = self.P * (dP * self.M - delta)
         self.dq = self.dS @ self.k
         self.dk_ = self.dS.transpose(-1, -2) @ self.q
-        self.dv = self.P.transpose(-1, -2) @ self.do
+        self.dv = self.Pm.transpose(-1, -2) @ self.do
         self.dbias = self.dS.sum(0)
 
     def softmax_fp64(self):
@@ -205,8 +219,8 @@ class AttnFixture:
 
 
 @functools.lru_cache(maxsize=None)
-def attn_fixture(kind, B, H, Lq, Lk, dk, causal=False, n=None, seed=0):
-    return AttnFixture(kind, B, H, Lq, Lk, dk, causal, n, seed)
+def attn_fixture(kind, B, H, Lq, Lk, dk, causal=False, n=None, seed=0, drop=None):
+    return AttnFixture(kind, B, H, Lq, Lk, dk, causal, n, seed, drop)
 
 
 # ---- T5 attention: plain fp64 reference and per-element bounds -----------------------------------------------------------------
@@ -223,10 +237,12 @@ def attn_reference(q, k, v, bias, causal):
     return P @ v, lse, P
 
 
-def attn_backward_reference(q, k, v, bias, causal, ctx, lse, do):
+def attn_backward_reference(q, k, v, bias, causal, ctx, lse, do, M=None):
     """The backward as the function of what the kernel is handed: P = exp(S - lse) from the SAVED log-sum-exp and
     delta = rowsum(dO * ctx) from the SAVED context (both the forward kernel's outputs, as f32 / bf16 holds them), in fp64.
-    Returns dq, dk, dv, dbias and the companions P, D (D >= |dS| element-wise: P (|dO| |V|^T + sum_d |dO ctx|))."""
+    Returns dq, dk, dv, dbias and the companions P, D (D >= |dS| element-wise: P (|dO| |V|^T + sum_d |dO ctx|)).
+    M [B, H, Lq, Lk]: the dropout multipliers of the probabilities (attn_drop_mask): dV takes P M, dP is masked (dS = P (dP M - delta));
+    the companions P and D then carry M where the data path does."""
     S = q @ k.transpose(-1, -2)
     if bias is not None:
         S = S + bias[None]
@@ -236,9 +252,19 @@ def attn_backward_reference(q, k, v, bias, causal, ctx, lse, do):
         P = P.masked_fill(torch.arange(Lk)[None, :] > torch.arange(Lq)[:, None], 0.0)
     dP = do @ v.transpose(-1, -2)
     delta = (do * ctx).sum(-1, keepdim=True)
-    dS = P * (dP - delta)
-    D = P * (do.abs() @ v.abs().transpose(-1, -2) + (do * ctx).abs().sum(-1, keepdim=True))
-    return dict(dq=dS @ k, dk=dS.transpose(-1, -2) @ q, dv=P.transpose(-1, -2) @ do, dbias=dS.sum(0), P=P, D=D, dS=dS)
+    if M is None:
+        dS = P * (dP - delta)
+        D = P * (do.abs() @ v.abs().transpose(-1, -2) + (do * ctx).abs().sum(-1, keepdim=True))
+        return dict(dq=dS @ k, dk=dS.transpose(-1, -2) @ q, dv=P.transpose(-1, -2) @ do, dbias=dS.sum(0), P=P, D=D, dS=dS, P0=P)
+    dS = P * (dP * M - delta)
+    D = attn_ds_companion(P, M, v, ctx, do.abs())
+    Pm = P * M
+    return dict(dq=dS @ k, dk=dS.transpose(-1, -2) @ q, dv=Pm.transpose(-1, -2) @ do, dbias=dS.sum(0), P=Pm, D=D, dS=dS, P0=P)
+
+
+def attn_ds_companion(P, M, v, ctx, e):
+    """P (M (e |V|^T) + sum_d e |ctx|): what an element-wise magnitude (or error) e >= 0 of dO becomes in dS = P (dP M - delta)"""
+    return P * (M * (e @ v.abs().transpose(-1, -2)) + (e * ctx.abs()).sum(-1, keepdim=True))
 
 
 def attn_fwd_bound(P, v):
@@ -361,6 +387,8 @@ ATTN_FLASH = [(200, 300, 32, False), (200, 300, 64, False)]
 # (33, 153, 64) in f32 needs 1184 bytes of LDS per key + 8.4 KiB against a budget of 150 KiB: chunks of kc = 112 < Lk keys
 ATTN_GENERIC = [("f32", 21, 37, 16, False), ("f32", 37, 37, 32, True), ("bf16", 33, 58, 24, False), ("f32", 33, 153, 64, False)]
 ATTN_B, ATTN_H = 3, 2
+# the one-workgroup MFMA kernels once more under dropout (p = 0.5, FUSED_DROP below): the mask of exact_ref.attn_drop_mult
+ATTN_DROP = [(33, 58, 64, False), (58, 58, 64, True)]
 
 
 
@@ -387,3 +415,196 @@ def attn_fixture_cases():
         out += [(kind, n, Lq, Lk, dk, causal) for kind, n in fixtures_for(dk)]
     out += [("onehot_nobias", 1, Lq, Lk, dk, causal) for Lq, Lk, dk, causal in ATTN_FLASH]
     return out
+
+
+# ---- attention dropout ---------------------------------------------------------------------------------------------------------
+def attn_drop_mult(seed, tag, p, slab, off):
+    """The multiplier of probability `off` = q * Lk + key of slab b * H + h, stated on its own (csrc/common.h): the key of
+    make_drop(seed, tag), folded with the slab by drop_slab, then one hash round on the 32-bit offset (drop_mult32):
+    mix32(off * 0x9E3779B1 + key) < trunc(p 2^32) ? 0 : 1 / (1 - p), f32.  slab and off are integer arrays that broadcast."""
+    import numpy as np
+    from tests.rowops_ref import mix32  # (rowops_ref imports this module at its top)
+    m = np.uint64(0xFFFFFFFF)
+    key = mix32(np.uint64((int(seed) * 0x9E3779B1 + int(tag) * 0x7FEB352D + 0x165667B1) & 0xFFFFFFFF))
+    slab = np.asarray(slab).astype(np.uint64) & m
+    key = mix32(key ^ ((slab * np.uint64(0x85EBCA77) + np.uint64(0x27D4EB2F)) & m))
+    off = np.asarray(off).astype(np.uint64) & m
+    h = mix32((off * np.uint64(0x9E3779B1) + key) & m)
+    pf = np.float32(p)
+    thresh = min(int(float(pf) * 4294967296.0), 0xFFFFFFFF)
+    scale = np.float32(1.0) / (np.float32(1.0) - pf)
+    return np.where(h < np.uint64(thresh), np.float32(0.0), scale).astype(np.float32)
+
+
+def attn_drop_mask(seed, tag, p, B, H, Lq, Lk):
+    """M [B, H, Lq, Lk] (fp64 holding the f32 multipliers) of one attention call"""
+    import numpy as np
+    slab = (np.arange(B)[:, None] * H + np.arange(H)[None, :])[:, :, None, None]
+    off = (np.arange(Lq)[:, None] * Lk + np.arange(Lk)[None, :])[None, None]
+    return torch.from_numpy(attn_drop_mult(seed, tag, p, slab, off)).double()
+
+
+# ---- fused T5 attention sub-layer kernels (klab_t5_attn_fused_fwd, klab_t5_attn_bwd_fused) --------------------------------------
+# d_model = 512, head dim 64, at most 64 queries / keys.  (cross, B, H, Lq, Lk, causal): the smallest shapes that reach every branch --
+# 64 (full tiles), 58 (ragged last wave), 33 (NS / NQS = 2 by one row), 17 (one wave + one row, NS = NQS = 1), 5 (three waves
+# without a query), 1; cross with Lq != Lk on either side of 32; B = 3 (the plain workgroup -> (sample, head) map) and B = 16 (the
+# (B & 7) == 0 map, two groups of eight samples).
+FUSED_D, FUSED_DK = 512, 64
+FUSED_SELF = [(64, True), (58, False), (33, True), (17, False), (5, True), (1, False)]
+FUSED_CROSS = [(64, 58), (40, 64), (9, 33), (33, 9), (1, 64), (64, 1)]
+FUSED_SHAPES = ([(False, 3, 8, L, L, c) for L, c in FUSED_SELF] + [(True, 3, 8, Lq, Lk, False) for Lq, Lk in FUSED_CROSS]
+                + [(False, 16, 8, 58, 58, False), (True, 16, 8, 64, 58, False)])
+# the forward's envelope fixes d_model and the head dim only: Flan-T5-small has 6 heads (inner = 384)
+FUSED_FWD_SHAPES = FUSED_SHAPES + [(False, 3, 6, 33, 33, True), (True, 3, 6, 40, 64, False)]
+FUSED_RANDOM = [(cross, B, 8, Lq, Lk, c) for B in (3, 16) for cross, Lq, Lk, c in
+                ((False, 64, 64, True), (False, 58, 58, False), (True, 64, 58, False), (True, 9, 33, False))]
+FUSED_DROP = (31, 11, 0.5)         # (seed, tag, p) of the exact dropout cases: the multiplier is 0 or 2, dyadic stays dyadic
+FUSED_RANDOM_DROP = (31, 11, 0.1)
+FUSED_FWD_KINDS = (("onehot", 1), ("q0", 4), ("k0", 2))  # (the CPU test is the judge of n, as for fixtures_for)
+FUSED_NEG = -65536.0  # bias of a key that is not chosen: |S| <= 64 * 16 * 16 = 2^14, so S + NEG is an integer f32 holds and
+                      # NEG + max S - min S <= -2^15: exp of it is 0 in f32 (and in fp64)
+
+
+def heads(x, L, H):
+    """[B * L, H * dk] -> [B, H, L, dk]"""
+    n, hd = x.shape
+    return x.reshape(n // L, L, H, hd // H).permute(0, 2, 1, 3)
+
+
+def unheads(x):
+    """[B, H, L, dk] -> [B * L, H * dk]: head h at column h * dk"""
+    b, h, L, dk = x.shape
+    return x.permute(0, 2, 1, 3).reshape(b * L, h * dk)
+
+
+@functools.lru_cache(maxsize=None)
+def signed_perm(d=FUSED_D, tile=64, seed=0):
+    """The o / co projection weight of the exact backward cases: W [d, d] (nn.Linear layout [d_model, inner]) with one +-1 per row
+    and per column, W[n, pi[n]] = sign[n].  Of the 64 rows of every k-tile of the dgrad (rows 64 t .. + 63) eight go to each head's
+    64-column slice, at random places of the tile and of the slice.  -> (W, pi, sign)"""
+    g = gen(6000 + seed)
+    nt = d // tile
+    per = tile // nt
+    slots = [torch.randperm(tile, generator=g) for _ in range(nt)]
+    pi = torch.empty(d, dtype=torch.int64)
+    for t in range(nt):
+        r = torch.randperm(tile, generator=g) + t * tile
+        for h in range(nt):
+            pi[r[h * per:(h + 1) * per]] = h * tile + slots[h][t * per:(t + 1) * per]
+    sign = 2.0 * torch.randint(0, 2, (d,), generator=g).double() - 1.0
+    W = torch.zeros(d, d, dtype=torch.float64)
+    W[torch.arange(d), pi] = sign
+    return W, pi, sign
+
+
+def dy_for(do):
+    """dy [B * Lq, 512] with dy @ W == rows(dO) exactly for W = signed_perm(): dy = rows(dO) W^T (a signed shuffle of the columns)"""
+    return unheads(do) @ signed_perm()[0].T
+
+
+@functools.lru_cache(maxsize=None)
+def fused_bwd_fixture(kind, n, cross, B, H, Lq, Lk, causal, drop=None):
+    """AttnFixture at head dim 64 (cached: callers must not write into it)"""
+    return AttnFixture(kind, B, H, Lq, Lk, FUSED_DK, causal, n, 0, drop)
+
+
+class FusedFwdFixture:
+    """klab_t5_attn_fused_fwd on operands that make every stage exact.
+    x[r, c] = sign[r, c] s_r with s_r in {1, 2, 4}: mean(x^2) = s_r^2 and x * rstd is within a few 1e-7 of +-1; gamma in {1, 2}:
+    bf16(gamma (x rstd)) = sign gamma for every rstd the rstd bound admits (the CPU test shows it).  Every projection row has one
+    +-1 in each of the eight k-tiles of 64 columns, so q | k | v are integers of magnitude <= 16, exact in f32 in any order and in
+    bf16.  The attention is AttnFixture's: bias 0 on the chosen keys and FUSED_NEG elsewhere; n = 1 for any q, k ('onehot'), n > 1
+    with the q block ('q0') or the k block ('k0': cross attention zeroes the given K) of the weight zero.  In the cross form K and
+    V are inputs, drawn as AttnFixture draws them.  References (fp64): xn [B Lq, 512], rstd [B Lq], proj [B Lq, 3 inner | inner],
+    P, M, Pm [B, H, Lq, Lk], ctx [B, H, Lq, 64], lse [B, H, Lq]."""
+
+    def __init__(self, kind, n, cross, B, H, Lq, Lk, causal, drop=None, eps=1e-6):
+        assert kind in ("onehot", "q0", "k0") and (n == 1) == (kind == "onehot") and (cross or Lq == Lk)
+        d, dk = FUSED_D, FUSED_DK
+        inner = H * dk
+        self.kind, self.n, self.cross, self.B, self.H, self.Lq, self.Lk, self.causal, self.inner = kind, n, cross, B, H, Lq, Lk, causal, inner
+        g = gen(8000 + 7 * Lq + Lk + 1000 * H)
+        nrows = B * Lq
+        sign = 2.0 * torch.randint(0, 2, (nrows, d), generator=g).double() - 1.0
+        self.s = 2.0 ** torch.randint(0, 3, (nrows,), generator=g).double()
+        self.x = sign * self.s[:, None]
+        self.gamma = 1.0 + torch.randint(0, 2, (d,), generator=g).double()
+        self.eps = eps
+        self.rstd = (self.x.pow(2).mean(-1) + eps).rsqrt()
+        self.xn = sign * self.gamma[None, :]
+        nproj = inner if cross else 3 * inner
+        W = torch.zeros(nproj, d, dtype=torch.float64)
+        for t in range(d // 64):
+            col = t * 64 + torch.randint(0, 64, (nproj,), generator=g)
+            W[torch.arange(nproj), col] = 2.0 * torch.randint(0, 2, (nproj,), generator=g).double() - 1.0
+        if kind == "q0":
+            W[:inner] = 0.0
+        elif kind == "k0" and not cross:
+            W[inner:2 * inner] = 0.0
+        self.w = W
+        self.proj = self.xn @ W.T
+        self.q = heads(self.proj[:, :inner], Lq, H)
+        if cross:
+            self.k = ints(g, -2, 2, B, H, Lk, dk)
+            self.v = ints(g, -1, 1, B, H, Lk, dk)
+            if kind == "k0":
+                self.k.zero_()
+        else:
+            self.k = heads(self.proj[:, inner:2 * inner], Lk, H)
+            self.v = heads(self.proj[:, 2 * inner:], Lk, H)
+        self.keys = chosen_keys(H, Lq, Lk, n, causal)
+        mask = torch.zeros(H, Lq, Lk, dtype=torch.bool)
+        for h in range(H):
+            for q in range(Lq):
+                mask[h, q, self.keys[h][q]] = True
+        self.mask = mask
+        cnt = mask.sum(-1, keepdim=True).double()
+        self.P = (mask.double() / cnt)[None].expand(B, H, Lq, Lk).contiguous()
+        self.bias = torch.where(mask, 0.0, FUSED_NEG).double()
+        self.S = self.q @ self.k.transpose(-1, -2)
+        self.lse = torch.where(mask[None], self.S, -math.inf).amax(-1) + cnt[None, ..., 0].log()
+        self.M = torch.ones(B, H, Lq, Lk, dtype=torch.float64) if drop is None else attn_drop_mask(*drop, B, H, Lq, Lk)
+        self.Pm = self.P * self.M
+        self.ctx = self.Pm @ self.v
+
+    def softmax_fp64(self):
+        return attn_reference(self.q, self.k, self.v, self.bias, self.causal)[2]
+
+
+@functools.lru_cache(maxsize=None)
+def fused_fwd_fixture(kind, n, cross, B, H, Lq, Lk, causal, drop=None):
+    return FusedFwdFixture(kind, n, cross, B, H, Lq, Lk, causal, drop)
+
+
+def rstd_bound(ref, d=FUSED_D):
+    """(adds(d) + 8) 2^-24 |ref|: the longest chain of f32 additions of a 64-lane row sum (rowops_ref.adds) plus the division, eps,
+    the reciprocal square root and slack for their ulps -- the bound tests/test_norm_exact_gpu.py holds klab_rmsnorm_fwd to"""
+    from tests.rowops_ref import adds
+    return (adds(d) + 8) * U24 * ref.abs()
+
+
+@functools.lru_cache(maxsize=None)
+def fused_randn(cross, B, H, Lq, Lk):
+    """random operands of both fused kernels (bf16 / f32 values held in fp64): x, gamma, the projection weight, the given K | V of
+    the cross form, the position bias; q | k | v, dy and the o weight of the backward"""
+    g = gen(9000 + 100 * Lq + Lk + B)
+    d, inner = FUSED_D, H * FUSED_DK
+    r16 = lambda *s: torch.randn(*s, generator=g).to(torch.bfloat16).double()
+    r32 = lambda *s: torch.randn(*s, generator=g).float().double()
+    return dict(x=2.0 * r32(B * Lq, d), gamma=(1.0 + 0.1 * torch.randn(d, generator=g)).float().double(),
+                w=(torch.randn((1 if cross else 3) * inner, d, generator=g) * d ** -0.5).to(torch.bfloat16).double(),
+                k=0.5 * r16(B, H, Lk, FUSED_DK), v=r16(B, H, Lk, FUSED_DK), bias=(2.0 * torch.randn(H, Lq, Lk, generator=g)).float().double(),
+                q=0.5 * r16(B, H, Lq, FUSED_DK), dy=r16(B * Lq, d), wo=(torch.randn(d, inner, generator=g) * d ** -0.5).to(torch.bfloat16).double())
+
+
+def attn_bwd_fused_bounds(r, M, q, k, v, ctx, do, absdo, Lq, Lk, dk, B, stored_ds):
+    """klab_t5_attn_bwd_fused: attn_bwd_bounds (with P M where the data path has it: r from attn_backward_reference(..., M)) plus
+    the error of the kernel's own dO = bf16(dy W_h) against the fp64 product the reference is given:
+        e = 2^-8 |dO| + gemm_bound(|dy| |W_h|, 512)        (one rounding to bf16, 512 f32 additions of exact products)
+    pushed once through every expression that contains dO: (P M)^T e for dV; for dS = P (dP M - delta) both dP = dO V^T and
+    delta = rowsum(dO ctx) carry it, E = P (M (e |V|^T) + sum_d e |ctx|), hence E |K| for dQ, E^T |Q| for dK, sum_b E for dbias."""
+    b = attn_bwd_bounds(r, q, k, v, do, Lq, Lk, dk, B, stored_ds)
+    e = U8 * do.abs() + gemm_bound(absdo, FUSED_D)
+    E = attn_ds_companion(r["P0"], M, v, ctx, e)
+    return dict(dv=b["dv"] + r["P"].transpose(-1, -2) @ e, dq=b["dq"] + E @ k.abs(), dk=b["dk"] + E.transpose(-1, -2) @ q.abs(),
+                dbias=b["dbias"] + E.sum(0))

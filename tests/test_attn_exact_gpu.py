@@ -13,6 +13,9 @@ numbers that bf16 holds exactly (tests/test_exact_fixtures_cpu.py proves it in f
 A wrong last query row of a ragged tile, a key block skipped or added twice, a wrong head or key index in one workgroup or a
 mis-masked edge fragment changes some element by at least its last bit and fails; the message names the first such element.
 
+The one-workgroup kernels run once more under dropout at p = 0.5 against exact_ref.attn_drop_mult, the mask stated on its own.  The
+harness (sentinel buffers, the comparisons) lives in tests/attn_harness.py, shared with tests/test_attn_fused_exact_gpu.py.
+
 The last section runs each kernel family once on randn operands under per-element bounds counted from the roundings on each
 output's data path (exact_ref.attn_fwd_bound, attn_bwd_bounds, attn_f32_bounds; DESIGN.md section 1 has the derivation and the
 measured worst ratios)."""
@@ -20,119 +23,18 @@ import pytest
 import torch
 
 from tests import exact_ref as R
+from tests.attn_harness import (GUARD, FlatOut, MatOut, assert_bf16_equal, assert_f32_close, first_bad, fused_input, ratio)
 
 pytestmark = pytest.mark.gpu
 
 DT = {"f32": torch.float32, "bf16": torch.bfloat16}
 B, H = R.ATTN_B, R.ATTN_H
-GUARD = 16      # elements before and after the flat f32 / bf16 outputs (lse, dbias, the dS slab)
-REL = 2.0 ** -20
-PAD_VALUE = 7.0
 
 
 @pytest.fixture(scope="module")
 def ops():
     from klab_multimodalmodel_amd import ops as K
     return K
-
-
-def rows(x):
-    """[B, H, L, dk] -> [B * L, H * dk]: head h at column h * dk"""
-    b, h, L, dk = x.shape
-    return x.permute(0, 2, 1, 3).reshape(b * L, h * dk)
-
-
-def unrows(x, L):
-    n, hd = x.shape
-    return x.reshape(n // L, L, H, hd // H).permute(0, 2, 1, 3)
-
-
-def bits(t):
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def sentinel(shape, dtype):
-    buf = torch.empty(shape, dtype=dtype)
-    if dtype == torch.float32:
-        buf.view(torch.int32).fill_(0x5A5B5C5D)
-    else:
-        buf.view(torch.int16).fill_(0x5A5B)
-    return buf
-
-
-def fused_input(parts, dtype):
-    """column blocks side by side in one [rows, sum of widths + 8] buffer -> (device buffer, ld, views at each block's first column)"""
-    mats = [rows(p) for p in parts]
-    w = mats[0].shape[1]
-    buf = torch.full((mats[0].shape[0], w * len(mats) + 8), PAD_VALUE, dtype=dtype)
-    for i, m in enumerate(mats):
-        buf[:, i * w:(i + 1) * w] = m.to(dtype)
-    d = buf.cuda()
-    return d, buf.shape[1], [d[:, i * w:] for i in range(len(mats))]
-
-
-class MatOut:
-    """`nblk` output matrices [n, H dk] side by side in a sentinel-filled [n + 2, nblk H dk + 8] buffer, written from row 1 on"""
-
-    def __init__(self, n, width, nblk, dtype):
-        self.n, self.w, self.nblk = n, width, nblk
-        self.ld = width * nblk + 8
-        self.before = sentinel((n + 2, self.ld), dtype)
-        self.buf = self.before.cuda()
-        self.views = [self.buf[1:, i * width:] for i in range(nblk)]
-
-    def fetch(self, L):
-        """-> the blocks as [B, H, L, dk]; asserts that nothing outside them changed"""
-        after = self.buf.cpu()
-        got = [unrows(after[1:1 + self.n, i * self.w:(i + 1) * self.w].clone(), L) for i in range(self.nblk)]
-        after[1:1 + self.n, :self.w * self.nblk] = self.before[1:1 + self.n, :self.w * self.nblk]
-        touched = bits(after) != bits(self.before)
-        assert not bool(touched.any()), f"wrote outside the output matrix at (buffer row, column) {touched.nonzero()[:8].tolist()}"
-        return got
-
-
-class FlatOut:
-    """a flat output of n elements between two guards of sentinel; fill: what the n elements start from (None: sentinel too)"""
-
-    def __init__(self, n, dtype, fill=None):
-        self.n = n
-        self.before = sentinel((n + 2 * GUARD,), dtype)
-        if fill is not None:
-            self.before[GUARD:GUARD + n] = fill
-        self.buf = self.before.cuda()
-        self.view = self.buf[GUARD:GUARD + n]
-
-    def fetch(self):
-        after = self.buf.cpu()
-        got = after[GUARD:GUARD + self.n].clone()
-        assert torch.equal(bits(after[:GUARD]), bits(self.before[:GUARD])) and torch.equal(bits(after[GUARD + self.n:]), bits(self.before[GUARD + self.n:])), \
-            "wrote into the guard of a flat output"
-        return got
-
-
-def first_bad(bad):
-    return tuple(int(v) for v in bad.nonzero()[0])
-
-
-def assert_bf16_equal(got, ref, what):
-    want = R.to_bf16_via_f32(ref)
-    bad = got != want
-    if bool(bad.any()):
-        i = first_bad(bad)
-        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements wrong, first at (b, h, row, col) = {i}: got {float(got[i])}, "
-                             f"want {float(want[i])}")
-    assert torch.equal(got, want)
-
-
-def assert_f32_close(got, ref, what, mag=None):
-    """|got - ref| <= 2^-20 mag (mag = |ref| unless the output is a sum: then the sum of its terms' magnitudes), 0 where mag is 0"""
-    mag = ref.abs() if mag is None else mag
-    err = (got.double() - ref).abs()
-    bad = err > REL * mag
-    if bool(bad.any()):
-        i = first_bad(bad)
-        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements off, first at {i}: got {float(got[i])!r}, want {float(ref[i])!r}, "
-                             f"allowed {REL * float(mag[i]):.3e}")
 
 
 def assert_out(got, ref, what, mag=None):
@@ -145,7 +47,7 @@ def assert_out(got, ref, what, mag=None):
 class Problem:
     """device operands of one attention problem in the engine's buffer layout: q alone, k | v fused, ctx | dO fused"""
 
-    def __init__(self, q, k, v, do, bias, dtype, Lq, Lk, dk, causal):
+    def __init__(self, q, k, v, do, bias, dtype, Lq, Lk, dk, causal, drop=None):
         self.Lq, self.Lk, self.dk, self.causal, self.dtype = Lq, Lk, dk, causal, dtype
         self.nb = q.shape[0]
         self.qbuf, self.ldq, (self.q,) = fused_input([q], dtype)
@@ -153,9 +55,12 @@ class Problem:
         self.do = do
         self.bias = None if bias is None else bias.float().cuda()
         self.kw = dict(B=self.nb, H=H, Lq=Lq, Lk=Lk, dk=dk, bias=self.bias, causal=causal, ldq=self.ldq, ldk=self.ldkv, ldv=self.ldkv)
+        if drop is not None:  # (seed, tag, p): attention dropout on the probabilities
+            self.seed = torch.tensor([drop[0]], dtype=torch.int32).cuda()
+            self.kw.update(seed=self.seed, tag=drop[1], drop_p=drop[2])
 
     def forward(self, ops):
-        ctx = MatOut(self.nb * self.Lq, H * self.dk, 1, self.dtype)
+        ctx = MatOut(self.nb * self.Lq, H * self.dk, 1, self.dtype, H)
         lse = FlatOut(self.nb * H * self.Lq, torch.float32)
         ops.t5_attn_fwd(self.q, self.k, self.v, ctx.views[0], lse.view, ldo=ctx.ld, **self.kw)
         torch.cuda.synchronize()
@@ -168,8 +73,8 @@ class Problem:
         Lq, Lk, dk = self.Lq, self.Lk, self.dk
         Lkp = (Lk + 31) // 32 * 32
         cbuf, ldc, (cv, dov) = fused_input([ctx, self.do], self.dtype)
-        dq = MatOut(self.nb * Lq, H * dk, 1, self.dtype)
-        dkv = MatOut(self.nb * Lk, H * dk, 2, self.dtype)
+        dq = MatOut(self.nb * Lq, H * dk, 1, self.dtype, H)
+        dkv = MatOut(self.nb * Lk, H * dk, 2, self.dtype, H)
         dbias = FlatOut(H * Lq * Lk, torch.float32, fill=0.0) if mode != "none" else None
         ds = FlatOut(self.nb * H * Lq * Lkp, torch.bfloat16) if mode in ("ds_ws", "ds_defer") else None
         lse_d = lse.float().cuda()
@@ -200,15 +105,15 @@ def path_of(dtype, Lq, Lk, dk, causal):
     return "generic"
 
 
-def run_fixture(ops, dtype, kind, n, Lq, Lk, dk, causal, modes):
-    f = R.attn_fixture(kind, B, H, Lq, Lk, dk, causal, n)
-    tag = f"{kind} n={n} (Lq, Lk, dk) = ({Lq}, {Lk}, {dk}) causal={causal} {dtype}"
-    pr = Problem(f.q, f.k, f.v, f.do, f.bias, DT[dtype], Lq, Lk, dk, causal)
+def run_fixture(ops, dtype, kind, n, Lq, Lk, dk, causal, modes, drop=None):
+    f = R.attn_fixture(kind, B, H, Lq, Lk, dk, causal, n, 0, drop)
+    tag = f"{kind} n={n} (Lq, Lk, dk) = ({Lq}, {Lk}, {dk}) causal={causal} {dtype}" + (f" dropout (seed, tag, p) = {drop}" if drop else "")
+    pr = Problem(f.q, f.k, f.v, f.do, f.bias, DT[dtype], Lq, Lk, dk, causal, drop)
     ctx, lse = pr.forward(ops)
     assert_out(ctx, f.ctx, f"forward ctx, {tag}")
     assert_f32_close(lse, f.lse, f"forward lse, {tag}")
     absds = f.dS.abs()
-    mags = dict(dq=absds @ f.k.abs(), dk=absds.transpose(-1, -2) @ f.q.abs(), dv=f.P.transpose(-1, -2) @ f.do.abs())
+    mags = dict(dq=absds @ f.k.abs(), dk=absds.transpose(-1, -2) @ f.q.abs(), dv=f.Pm.transpose(-1, -2) @ f.do.abs())
     for mode in modes:
         got = pr.backward(ops, f.ctx, f.lse, mode)
         for name, ref in (("dq", f.dq), ("dk", f.dk_), ("dv", f.dv)):
@@ -241,6 +146,18 @@ def test_mfma_one_workgroup_kernels(ops, kind, n, Lq, Lk, dk, causal):
     run_fixture(ops, "bf16", kind, n, Lq, Lk, dk, causal, modes)
 
 
+# the dropout mask, stated on its own (exact_ref.attn_drop_mult: element (seed, tag, slab = b H + h, q Lk + key)): at p = 0.5 the
+# multiplier is 0 or 2 and the dyadic fixtures stay dyadic (ctx = (P M) V, dV = (P M)^T dO, dS = P (dP M - delta)).  These are the
+# kernels the fused attention kernels are compared with elsewhere.
+DROP_CASES = [(kind, n, *c) for c in R.ATTN_DROP for kind, n in R.fixtures_for(c[2])]
+
+
+@pytest.mark.parametrize("kind,n,Lq,Lk,dk,causal", DROP_CASES, ids=[case_id(c) for c in DROP_CASES])
+def test_mfma_one_workgroup_kernels_dropout_mask(ops, kind, n, Lq, Lk, dk, causal):
+    assert path_of("bf16", Lq, Lk, dk, causal) == "mfma"
+    run_fixture(ops, "bf16", kind, n, Lq, Lk, dk, causal, ("atomics", "ds_ws", "ds_defer"), drop=R.FUSED_DROP)
+
+
 # ------------------------------------------------------------------------------------------------ streaming kernels
 # flash_fwd_kernel (Lk padded to 320 > 256), flash_bwd_dq_kernel + flash_bwd_dkv_kernel (the one-workgroup images of 224 queries
 # and 320 keys exceed 160 KiB at both head dims).  Four query blocks and five key blocks of 64, the last of each ragged.  The bias
@@ -269,14 +186,6 @@ def test_generic_kernels(ops, dtype, kind, n, Lq, Lk, dk, causal):
 
 
 # ------------------------------------------------------------------------------------------------ random operands, per element
-def ratio(got, ref, bound, what):
-    err = (got.double() - ref).abs()
-    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, float("inf"), 0.0).double())
-    i = first_bad(r == r.max())
-    print(f"  {what}: max err / bound {float(r.max()):.3e} at {i}")
-    return float(r.max()), f"{what}: worst element {i}: got {float(got[i])}, want {float(ref[i])}, bound {float(bound[i]):.3e}"
-
-
 RANDOM = [
     # (dtype, Lq, Lk, dk, causal, with_bias, modes)
     ("bf16", 70, 153, 64, False, True, ("ds_ws", "atomics")),   # t5_attn_fwd_mfma<64, 16>, t5_attn_bwd_mfma<64>
