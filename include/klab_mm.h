@@ -459,7 +459,16 @@ int klab_engine_bucket_wait(klab_engine* e, int segment, int i, void* stream);
  * off by default: a single-GPU step pays nothing for them                                                            */
 int klab_engine_set_bucket_events(klab_engine* e, int on);
 int klab_engine_segment(const klab_engine* e, int seg, int* model, long* off, long* len);
+/* Captions per image, n >= 1, of the NEXT klab_engine_bind: one-shot, the bind takes it and puts 1 back, so a caller that never
+ * sets it binds as before.  klab_engine_workspace_bytes sizes the binding that klab_engine_bind would make now (it reads the value
+ * and leaves it); klab_engine_workspace_bytes_n is the plain query for a given n and touches nothing.  The Swin tower, both encoders and the cross K/V of that binding run B rows of images; the decoder, the
+ * LM head and the loss run B*n target sequences in image-major order: tgt_ids [B,n,Lt], loss weights [B,n,Lt], loss_row /
+ * logits / decoder_out rows ((b*n + j)*Lt + t).  Cross-attention of an image's n sequences is issued as ONE batch element with
+ * n*Lt queries over the image's K/V (no position bias, no mask: HF/t5:404-432), so d(encoder output) needs no reduction over n.
+ * The loss is the mean over all scored tokens of all sequences.  Decoding sessions (klab_engine_gen_*) need a binding with n = 1. */
+int klab_engine_set_captions(klab_engine* e, int n);
 size_t klab_engine_workspace_bytes(klab_engine* e, int B, int Ls, int Lt);
+size_t klab_engine_workspace_bytes_n(klab_engine* e, int B, int Ls, int Lt, int n);
 /* *_params: host arrays of device pointers in klab_engine_param_info order.  *_bucket: int32 device
  * arrays [L*L] of T5 relative-position buckets (HF/t5:216-262, computed by the host exactly as the
  * reference does).  swin_coords[s] / swin_index[s]: per-stage CPB tables (HF/swinv2:457-492).      */
@@ -467,7 +476,7 @@ int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* workspace, siz
                      const void* const* lang_params, const void* const* main_params, float* main_grads, float* swin_grads,
                      const int* lang_bucket, const int* enc_bucket, const int* dec_bucket, const void* const* swin_coords,
                      const void* const* swin_index, void* stream);
-/* pixels [B,3,H,W] f32, src_ids [B,Ls] / tgt_ids [B,Lt] int64 (device).  training: T5 dropout on
+/* pixels [B,3,H,W] f32, src_ids [B,Ls] / tgt_ids [B,n,Lt] int64 (device).  training: T5 dropout on
  * (model.module.transformer.train(), ref/train.py:52).  `seed` (re)bases the device-side counter RNG whenever
  * it changes; every forward advances the counter itself.  The loss lands in *klab_engine_loss_ptr.      */
 int klab_engine_forward(klab_engine* e, const float* pixels, const long long* src_ids, const long long* tgt_ids, int training,
@@ -841,7 +850,7 @@ const float* klab_engine_loss_ptr(const klab_engine* e);
  * the cross-entropy.  Returns 1 if it will be honoured, 0 under graph replay (the loss stays at klab_engine_loss_ptr), < 0 on error. */
 int klab_engine_set_loss_out(klab_engine* e, float* out);
 /* Options of the training loss.  eps (label smoothing, 0 <= eps < 1) and z (z-loss, >= 0) persist until changed.  `weights` (device,
- * B*Lt floats, or NULL) is one-shot like klab_engine_set_loss_out: the NEXT klab_engine_forward copies it into the workspace beside
+ * B*n*Lt floats, or NULL) is one-shot like klab_engine_set_loss_out: the NEXT klab_engine_forward copies it into the workspace beside
  * the labels and never reads the caller's tensor again; a caller whose forward failed early passes NULL to disarm it.  With
  * eps == z == 0 and no weights the forward issues klab_ce_fwd as before (graph slots included); otherwise klab_ce_wsum and
  * klab_ce_fwd_opts, eagerly -- never from a captured graph, which would replay the options of the capture. */

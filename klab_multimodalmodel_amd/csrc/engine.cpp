@@ -140,6 +140,9 @@ struct klab_engine {
   // ---- bound state ----
   bool bound = false;
   int B = 0, Ls = 0, Lt = 0, Le = 0, Nimg = 0;
+  // captions per image (klab_engine_set_captions, read by the next bind): the encoder side runs B rows of images, the decoder side
+  // Bd = B*ncap sequences in image-major order (row ((b*ncap + j)*Lt + t)); their cross-attention is batch B with ncap*Lt queries
+  int ncap_next = 1, ncap = 1, Bd = 0;
   size_t es = 4;
   std::vector<const float*> W[3];
   float* G[3] = {nullptr, nullptr, nullptr};
@@ -204,7 +207,7 @@ struct klab_engine {
   bool dbias_zeroed[2] = {false, false};  // [decoder stack, encoder stack]
   bool denc_in_dxn = false;      // segment 0 left d(encoder output) in dxn, where segment 1's stack reads it
   float* loss_out = nullptr;     // one-shot destination of the next forward's loss (klab_engine_set_loss_out)
-  // klab_engine_set_loss_options: the scalars persist, the weights pointer is one-shot (the next forward copies B*Lt floats into
+  // klab_engine_set_loss_options: the scalars persist, the weights pointer is one-shot (the next forward copies Bd*Lt floats into
   // loss_w_buf and never reads the caller's tensor again)
   float loss_eps = 0.f, loss_z = 0.f;
   const float* loss_w_armed = nullptr;
@@ -514,7 +517,10 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
   const int Nimg = Rl * Rl, Le = Nimg + Ls;
   e->B = B; e->Ls = Ls; e->Lt = Lt; e->Le = Le; e->Nimg = Nimg;
   const long d = c.main.d_model, inner = (long)c.main.n_heads * c.main.d_kv, ff = c.main.d_ff;
-  const long Me = (long)B * Le, Md = (long)B * Lt;
+  const int ncap = e->ncap_next, Bd = B * ncap;
+  e->ncap = ncap; e->Bd = Bd;
+  const long Me = (long)B * Le, Md = (long)Bd * Lt;
+  const long Mx = Me > Md ? Me : Md;  // rows of the larger side
   const int nld = c.main.n_dec_layers;
 
   e->seed_dev = (uint32_t*)b.take(512);   // [0] seed of the current step, [1] base, [2] step counter
@@ -525,8 +531,8 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
   e->inv_w = (float*)((char*)e->seed_dev + 320);
   e->pixels_buf = (float*)b.take((size_t)B * c.swin.in_ch * c.swin.image_size * c.swin.image_size * 4);
   e->src_buf = (long long*)b.take((size_t)B * Ls * 8);
-  e->tgt_buf = (long long*)b.take((size_t)B * Lt * 8);
-  e->loss_w_buf = (float*)b.take((size_t)B * Lt * 4);
+  e->tgt_buf = (long long*)b.take((size_t)Md * 8);
+  e->loss_w_buf = (float*)b.take((size_t)Md * 4);
   e->warena = b.take((size_t)e->warena_elems * es);
   e->farena = (float*)b.take((size_t)e->farena_elems * 4);
   if (e->fp8) {
@@ -535,8 +541,8 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
     e->qdesc = b.take(sizeof(long) * 4 * (e->P[0].size() + e->P[1].size() + e->P[2].size() + 1));
     // activation staging: the widest A operand of any forward Linear (rows x K bytes) and its row scales
     const long R0q = c.swin.image_size / c.swin.patch;
-    long mk = (long)B * (Le > Lt ? Le : Lt) * (c.main.d_ff > c.main.d_model ? c.main.d_ff : c.main.d_model);
-    long rows = (long)B * (Le > Lt ? Le : Lt);
+    long mk = Mx * (c.main.d_ff > c.main.d_model ? c.main.d_ff : c.main.d_model);
+    long rows = Mx;
     for (int st = 0; st < c.swin.n_stages; ++st) {
       const long M = (long)B * (R0q >> st) * (R0q >> st), C = (long)c.swin.embed_dim << st;
       if (M * C * c.swin.mlp_ratio > mk) mk = M * C * c.swin.mlp_ratio;
@@ -557,7 +563,7 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
   {
     const int nle = c.main.n_layers, nldx = c.main.n_dec_layers;
     const int ncmax = (2 * nle + 1) > (3 * nldx + 1) ? (2 * nle + 1) : (3 * nldx + 1);
-    const long Mmax = (long)B * (Le > Lt ? Le : Lt);
+    const long Mmax = Mx;
     e->rms_part_stride = (long)klab_rmsnorm_part_rows((int)Mmax) * c.main.d_model;
     e->rms_part = (float*)b.take((size_t)ncmax * e->rms_part_stride * 4);
     e->rms_dst_dev[0] = (float**)b.take(sizeof(float*) * (2 * nle + 1));
@@ -566,12 +572,11 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
 
   plan_t5_stack(b, c.lang, c.lang.n_layers, false, false, B * Ls, B, Ls, es, e->lang, 0);
   plan_t5_stack(b, c.main, c.main.n_layers, false, true, (int)Me, B, Le, es, e->enc, 0);
-  plan_t5_stack(b, c.main, nld, true, true, (int)Md, B, Lt, es, e->dec, Le);
+  plan_t5_stack(b, c.main, nld, true, true, (int)Md, Bd, Lt, es, e->dec, Le);
   e->kv_all = b.take((size_t)Me * nld * 2 * inner * es);
   e->dkv_all = b.take((size_t)Me * nld * 2 * inner * es);
   e->logits = b.take((size_t)Md * c.main.vocab * es);
   e->loss_row = (float*)b.take((size_t)Md * 4);
-  const long Mx = Me > Md ? Me : Md;
   e->dh_a = (float*)b.take((size_t)Mx * d * 4);
   e->dh_b = (float*)b.take((size_t)Mx * d * 4);
   e->dxn = (float*)b.take((size_t)Mx * d * 4);
@@ -588,9 +593,9 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
   }
   e->dctx = b.take((size_t)Mx * inner * es);
   {
-    const long Lmax = Le > Lt ? Le : Lt;
+    const long se = (long)B * Le * ((Le + 31) & ~31L), sd = (long)Bd * Lt * ((Lt + 31) & ~31L);  // self-attention dS of a layer, per head
     const int nlmax = c.main.n_layers > c.main.n_dec_layers ? c.main.n_layers : c.main.n_dec_layers;
-    e->ds_ws = b.take((size_t)nlmax * B * c.main.n_heads * Lmax * ((Lmax + 31) & ~31L) * es);  // one slab per layer
+    e->ds_ws = b.take((size_t)nlmax * c.main.n_heads * (se > sd ? se : sd) * es);  // one slab per layer
   }
 
   // ---- Swin ----
@@ -808,10 +813,13 @@ static bool attn_bwd_fused_on() {
 
 // ------------------------------------------------------------------------------------------------
 // T5 stack forward (HF/t5:663-750); `h[0]` must already hold dropout(inputs_embeds)
+// qgrp (decoder only): sequences per image.  The B sequences are image-major, so the qgrp sequences of an image are qgrp*Lq
+// contiguous rows: their cross-attention (no position bias, no mask) over the image's K/V is ONE cross-attention of batch B / qgrp
+// with qgrp*Lq queries -- the unfused kernels, whose launch is per (batch element, head) at any query count.
 // ------------------------------------------------------------------------------------------------
 int t5_stack_forward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<ParamInfo>& P, const std::vector<const float*>& W,
                      const std::vector<T5LayerIdx>& L, int final_ln, T5StackBufs& s, bool dec, int stack_id, float p, int B,
-                     const void* kv_all, int Lkv, long kv_ld, float* out_f32, int grp, int grp_stride, int off, float p_final) {
+                     const void* kv_all, int Lkv, long kv_ld, float* out_f32, int grp, int grp_stride, int off, float p_final, int qgrp = 1) {
   const int d = cfg.d_model, H = cfg.n_heads, dk = cfg.d_kv, inner = H * dk, ff = cfg.d_ff;
   const int M = s.M, Lq = s.Lseq;
   const int relb = L[0].relb;
@@ -855,10 +863,10 @@ int t5_stack_forward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Par
       a.k = eoff(c, (void*)kv_all, (long)i * 2 * inner); a.ldk = kv_ld;
       a.v = eoff(c, (void*)kv_all, (long)i * 2 * inner + inner); a.ldv = kv_ld;
       a.bias = nullptr; a.causal = 0; a.ctx = b.ctx2; a.ldo = inner; a.lse = b.lse2;
-      a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lkv; a.dk = dk;
+      a.B = B / qgrp; a.H = H; a.Lq = qgrp * Lq; a.Lk = Lkv; a.dk = dk;
       a.drop_p = p; a.seed_dev = c.e->seed_dev; a.drop_tag = tag_of(stack_id, (int)i, SITE_XPROB);
       int frc = KLAB_ERR_UNSUPPORTED;
-      if (attn_fused_on() && c.dt == KLAB_BF16 && !c.e->fp8 && Lq >= 32) {  // norm -> q projection -> attention over the projected encoder output
+      if (attn_fused_on() && c.dt == KLAB_BF16 && !c.e->fp8 && Lq >= 32 && qgrp == 1) {  // norm -> q projection -> attention over the projected encoder output
         klab_attn_fused_args fa;
         memset(&fa, 0, sizeof(fa));
         fa.x = s.h[j]; fa.gamma = W[l.ln1]; fa.eps = cfg.ln_eps; fa.d_model = d; fa.w = woff(c, P[l.cq].warena_off);
@@ -1029,7 +1037,7 @@ struct WgradQueue {
 // ------------------------------------------------------------------------------------------------
 int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<ParamInfo>& P, const std::vector<const float*>& W,
                       float* Gflat, const std::vector<T5LayerIdx>& L, int final_ln, T5StackBufs& s, bool dec, int stack_id, float p,
-                      int B, const void* kv_all, void* dkv_all, int Lkv, long kv_ld, float** dh_out) {
+                      int B, const void* kv_all, void* dkv_all, int Lkv, long kv_ld, float** dh_out, int qgrp = 1) {
   klab_engine* e = c.e;
   const int d = cfg.d_model, H = cfg.n_heads, dk = cfg.d_kv, inner = H * dk, ff = cfg.d_ff;
   const int M = s.M, Lq = s.Lseq;
@@ -1062,8 +1070,8 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
   // fused kernel's envelope allows (bf16, d_model 512, head dim 64, <= 64 tokens per sample); otherwise the dgrad GEMM (once) +
   // klab_t5_attn_bwd.  KLAB_ERR_UNSUPPORTED of the attention kernel is returned for the caller's retry (ds_defer).
   bool dctx_ready = false;
-  auto attn_bwd = [&](klab_attn_args& a, long wo_off) -> int {
-    if (attn_bwd_fused_on() && c.dt == KLAB_BF16) {
+  auto attn_bwd = [&](klab_attn_args& a, long wo_off, bool fused_ok = true) -> int {
+    if (attn_bwd_fused_on() && c.dt == KLAB_BF16 && fused_ok) {
       klab_attn_bwd_fused_args fb;
       memset(&fb, 0, sizeof(fb));
       fb.dy = dy; fb.lddy = d; fb.w = woff(c, wo_off); fb.d_model = d; fb.attn = a;
@@ -1124,14 +1132,16 @@ int t5_stack_backward(const Ctx& c, const klab_t5_cfg& cfg, const std::vector<Pa
       a.dtype = c.dt; a.q = b.qc; a.ldq = inner;
       a.k = eoff(c, (void*)kv_all, (long)i * 2 * inner); a.ldk = kv_ld;
       a.v = eoff(c, (void*)kv_all, (long)i * 2 * inner + inner); a.ldv = kv_ld;
-      a.ctx = b.ctx2; a.ldo = inner; a.lse = b.lse2; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lkv; a.dk = dk;
+      // (qgrp sequences per image: batch B / qgrp with qgrp*Lq queries, as the forward; d k / d v of an image come out summed over
+      // its sequences, in the kernel's own fixed order)
+      a.ctx = b.ctx2; a.ldo = inner; a.lse = b.lse2; a.B = B / qgrp; a.H = H; a.Lq = qgrp * Lq; a.Lk = Lkv; a.dk = dk;
       a.drop_p = p; a.seed_dev = e->seed_dev; a.drop_tag = tag_of(stack_id, i, SITE_XPROB);
       a.dctx = e->dctx; a.lddo = inner; a.dq = dqc; a.lddq = inner;
       a.dk_out = eoff(c, dkv_all, (long)i * 2 * inner); a.lddk = kv_ld;
       a.dv = eoff(c, dkv_all, (long)i * 2 * inner + inner); a.lddv = kv_ld;
-      RC(attn_bwd(a, P[l.co].warena_off));
+      RC(attn_bwd(a, P[l.co].warena_off, qgrp == 1));
       if (kv_in_queue) {  // this layer's k | v projection: its slice of d(k|v) is final, the product joins the layer's group
-        RC(wq.push(eoff(c, dkv_all, (long)i * 2 * inner), kv_ld, e->enc.out_t, d, B * Lkv, 2 * inner, d, Gflat + e->kvall_g_off + (long)i * 2 * inner * d, st));
+        RC(wq.push(eoff(c, dkv_all, (long)i * 2 * inner), kv_ld, e->enc.out_t, d, (B / qgrp) * Lkv, 2 * inner, d, Gflat + e->kvall_g_off + (long)i * 2 * inner * d, st));
         e->kv_wgrad_done = true;
       }
       RC(wq.push(dqc, inner, b.xn2, d, M, inner, d, G(l.cq), st));
@@ -1439,15 +1449,28 @@ extern "C" int klab_engine_bucket_wait(klab_engine* e, int segment, int i, void*
   return (int)hipStreamWaitEvent((hipStream_t)stream, e->bucket_ev[segment][i], 0);
 }
 
-extern "C" size_t klab_engine_workspace_bytes(klab_engine* e, int B, int Ls, int Lt) {
-  if (!e || B <= 0 || Ls <= 0 || Lt <= 0) return 0;
+extern "C" size_t klab_engine_workspace_bytes_n(klab_engine* e, int B, int Ls, int Lt, int n) {
+  if (!e || B <= 0 || Ls <= 0 || Lt <= 0 || n < 1) return 0;
   // plan on a scratch engine that carries only what the plan reads (configuration, table sizes, arena extents): the bound
   // state of `e` -- and its live stream / event / graph handles -- is neither touched nor copied
   klab_engine tmp;
   tmp.cfg = e->cfg;
   for (int m = 0; m < 3; ++m) tmp.P[m].resize(e->P[m].size());
-  tmp.warena_elems = e->warena_elems; tmp.farena_elems = e->farena_elems; tmp.fp8 = e->fp8;
+  tmp.warena_elems = e->warena_elems; tmp.farena_elems = e->farena_elems; tmp.fp8 = e->fp8; tmp.ncap_next = n;
   return plan_workspace(&tmp, nullptr, B, Ls, Lt);
+}
+// the size of the binding that klab_engine_bind would make now: with the captions per image set for it, else 1
+extern "C" size_t klab_engine_workspace_bytes(klab_engine* e, int B, int Ls, int Lt) {
+  return e ? klab_engine_workspace_bytes_n(e, B, Ls, Lt, e->ncap_next) : 0;
+}
+
+// Captions per image of the NEXT klab_engine_bind, which takes the value and puts 1 back (klab_engine_workspace_bytes in between
+// reads it and leaves it): the decoder side of that binding runs B*n target sequences, image-major, over the B encoder outputs.
+// The current binding keeps its own.
+extern "C" int klab_engine_set_captions(klab_engine* e, int n) {
+  if (!e || n < 1) return KLAB_ERR_BADARG;
+  e->ncap_next = n;
+  return KLAB_OK;
 }
 
 extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* workspace, size_t ws_bytes, const void* const* swin_params,
@@ -1469,6 +1492,7 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
     if (e->seed_set && e->seed_dev) carry_rng = hipMemcpy(carry, e->seed_dev, sizeof(carry), hipMemcpyDeviceToHost) == hipSuccess;
   }
   const size_t need = plan_workspace(e, workspace, B, Ls, Lt);
+  e->ncap_next = 1;  // one-shot: a bind that sets nothing is ungrouped
   if (need > ws_bytes) return KLAB_ERR_BADARG;
   const void* const* src[3] = {swin_params, lang_params, main_params};
   for (int m = 0; m < 3; ++m) {
@@ -1748,7 +1772,7 @@ int forward_part_a(klab_engine* e, hipStream_t stream, float p, bool refresh_fro
   // fp8 mode: e4m3 copies + per-row scales of every GEMM weight, from the bf16 arena (which the casts above or the fused
   // optimizer step just refreshed)
   if (e->fp8 && e->n_qdesc) RC(klab_quant_fp8_arena(e->qdesc, e->n_qdesc, e->q_rows, e->warena, e->w8, e->wscale, c.ws()));
-  const int B = e->B, d = cfg.main.d_model;
+  const int B = e->B, Bd = e->Bd, d = cfg.main.d_model;
   // 2./3. The two towers are independent until the concat.  Swin-V2 (ref/models/model.py:22, rows [0, N_img)) is
   //    enqueued FIRST on the main stream -- its launches are long, so the host runs far ahead -- and the frozen
   //    language encoder (model.py:20-21, rows [N_img, Le); ~100 launches of ~5 us over 576 tokens, which would
@@ -1768,10 +1792,10 @@ int forward_part_a(klab_engine* e, hipStream_t stream, float p, bool refresh_fro
       RC(klab_relbias_fwd(e->W[2][e->mi.enc[0].relb], e->enc.bucket, e->enc.bias, H, e->enc.Lseq, e->enc.Lseq, cs.ws()));
       RC(klab_relbias_fwd(e->W[2][e->mi.dec[0].relb], e->dec.bucket, e->dec.bias, H, e->dec.Lseq, e->dec.Lseq, cs.ws()));
       e->bias_ready[STACK_ENC] = e->bias_ready[STACK_DEC] = true;
-      RC(klab_embed_fwd(tgt_ids, 1, e->Lt, cfg.main.start_id, cfg.main.pad_id, e->W[2][e->mi.shared], cfg.main.vocab, e->dec.h[0], B * e->Lt, d, p,
+      RC(klab_embed_fwd(tgt_ids, 1, e->Lt, cfg.main.start_id, cfg.main.pad_id, e->W[2][e->mi.shared], cfg.main.vocab, e->dec.h[0], Bd * e->Lt, d, p,
                         e->seed_dev, tag_of(STACK_DEC, 0, SITE_IN), e->err_dev, cs.ws()));
       e->dec_embed_ready = true;
-      RC(klab_ce_count(tgt_ids, B * e->Lt, e->inv_n, cs.ws()));  // 1 / n_valid of the labels: klab_ce_fwd then skips its counting launch
+      RC(klab_ce_count(tgt_ids, Bd * e->Lt, e->inv_n, cs.ws()));  // 1 / n_valid of the labels: klab_ce_fwd then skips its counting launch
       e->inv_n_ready = true;
     }
     RC(klab_embed_fwd(src_ids, 0, e->Ls, 0, 0, e->W[1][e->li.shared], cfg.lang.vocab, e->lang.h[0], B * e->Ls, d, 0.f, nullptr, 0, e->err_dev,
@@ -1788,12 +1812,12 @@ int forward_part_a(klab_engine* e, hipStream_t stream, float p, bool refresh_fro
   // 5. decoder: shift_right + embedding (HF/t5:1026-1028), cross K/V of all layers in one GEMM, stack
   const int inner = cfg.main.n_heads * cfg.main.d_kv, nld = cfg.main.n_dec_layers;
   if (e->dec_embed_ready) e->dec_embed_ready = false;
-  else RC(klab_embed_fwd(tgt_ids, 1, e->Lt, cfg.main.start_id, cfg.main.pad_id, e->W[2][e->mi.shared], cfg.main.vocab, e->dec.h[0], B * e->Lt, d, p,
+  else RC(klab_embed_fwd(tgt_ids, 1, e->Lt, cfg.main.start_id, cfg.main.pad_id, e->W[2][e->mi.shared], cfg.main.vocab, e->dec.h[0], Bd * e->Lt, d, p,
                          e->seed_dev, tag_of(STACK_DEC, 0, SITE_IN), e->err_dev, c.ws()));
   if (!encoder_current)
     RC(linear_fwd(c, e->enc.out_t, B * e->Le, d, e->kvall_w_off, nld * 2 * inner, e->kv_all, (long)nld * 2 * inner, c.dt));
-  RC(t5_stack_forward(c, cfg.main, e->P[2], e->W[2], e->mi.dec, e->mi.dec_final, e->dec, true, STACK_DEC, p, B, e->kv_all, e->Le,
-                      (long)nld * 2 * inner, nullptr, 0, 0, 0, p));
+  RC(t5_stack_forward(c, cfg.main, e->P[2], e->W[2], e->mi.dec, e->mi.dec_final, e->dec, true, STACK_DEC, p, Bd, e->kv_all, e->Le,
+                      (long)nld * 2 * inner, nullptr, 0, 0, 0, p, e->ncap));
   return 0;
 }
 
@@ -1918,12 +1942,12 @@ extern "C" int klab_engine_forward(klab_engine* e, const float* pixels, const lo
     e->pixels_cur = pixels;
   }
   RC((int)hipMemcpyAsync(e->src_buf, src_ids, (size_t)B * e->Ls * 8, hipMemcpyDeviceToDevice, c.s));
-  RC((int)hipMemcpyAsync(e->tgt_buf, tgt_ids, (size_t)B * e->Lt * 8, hipMemcpyDeviceToDevice, c.s));
+  RC((int)hipMemcpyAsync(e->tgt_buf, tgt_ids, (size_t)e->Bd * e->Lt * 8, hipMemcpyDeviceToDevice, c.s));
   const float* loss_w = nullptr;  // this forward's per-token loss weights (one-shot, staged like the labels)
   if (e->loss_w_armed) {
     const float* src_w = e->loss_w_armed;
     e->loss_w_armed = nullptr;
-    RC((int)hipMemcpyAsync(e->loss_w_buf, src_w, (size_t)B * e->Lt * 4, hipMemcpyDeviceToDevice, c.s));
+    RC((int)hipMemcpyAsync(e->loss_w_buf, src_w, (size_t)e->Bd * e->Lt * 4, hipMemcpyDeviceToDevice, c.s));
     loss_w = e->loss_w_buf;
   }
   if (!e->seed_set || seed != e->seed_base) {  // (re)seed the device-side counter RNG; each forward then advances it itself
@@ -1945,7 +1969,7 @@ extern "C" int klab_engine_forward(klab_engine* e, const float* pixels, const lo
     RC(run_graphed(e, (training & 1) ? 1 : 0, c.s, [&]() { return forward_part_a(e, c.s, p, false, tcur); }));
   }
   {
-    const int Md = B * e->Lt, V = cfg.main.vocab;
+    const int Md = e->Bd * e->Lt, V = cfg.main.vocab;
     klab_gemm_args g = G0(c, Md, V, d, e->dec.out_t, d, 1, woff(c, e->P[2][e->mi.head].warena_off), d, 1, e->logits, V, c.dt);
     g.alpha = cfg.main.scale_decoder_outputs ? 1.f / sqrtf((float)d) : 1.f;  // HF/t5:1044-1045
     g.name_tag = 1;
@@ -2018,7 +2042,7 @@ extern "C" int klab_engine_set_loss_out(klab_engine* e, float* out) {
   e->loss_out = e->use_graph ? nullptr : out;
   return e->loss_out ? 1 : 0;
 }
-// Options of the training loss (klab_ce_fwd_opts): eps and z persist until changed; `weights` (device, B*Lt floats, or NULL) is
+// Options of the training loss (klab_ce_fwd_opts): eps and z persist until changed; `weights` (device, B*n*Lt floats, or NULL) is
 // one-shot -- the next forward stages it beside the labels.  A caller whose forward fails early passes NULL again to disarm it.
 extern "C" int klab_engine_set_loss_options(klab_engine* e, float eps, float z, const float* weights) {
   if (!e || !(eps >= 0.f && eps < 1.f) || !(z >= 0.f) || !isfinite(z)) return KLAB_ERR_BADARG;
@@ -2036,9 +2060,9 @@ extern "C" const void* klab_engine_buffer(const klab_engine* e, const char* name
   auto set = [&](long r, long c2, int dt) { if (rows) *rows = r; if (cols) *cols = c2; if (dtype) *dtype = dt; };
   if (!strcmp(name, "encoder_input")) { set((long)e->B * e->Le, d, KLAB_F32); return e->enc.h[0]; }
   if (!strcmp(name, "encoder_out")) { set((long)e->B * e->Le, d, e->cfg.dtype); return e->enc.out_t; }
-  if (!strcmp(name, "decoder_out")) { set((long)e->B * e->Lt, d, e->cfg.dtype); return e->dec.out_t; }
-  if (!strcmp(name, "logits")) { set((long)e->B * e->Lt, e->cfg.main.vocab, e->cfg.dtype); return e->logits; }
-  if (!strcmp(name, "loss_row")) { set((long)e->B * e->Lt, 1, KLAB_F32); return e->loss_row; }
+  if (!strcmp(name, "decoder_out")) { set((long)e->Bd * e->Lt, d, e->cfg.dtype); return e->dec.out_t; }
+  if (!strcmp(name, "logits")) { set((long)e->Bd * e->Lt, e->cfg.main.vocab, e->cfg.dtype); return e->logits; }
+  if (!strcmp(name, "loss_row")) { set((long)e->Bd * e->Lt, 1, KLAB_F32); return e->loss_row; }
   return nullptr;
 }
 
@@ -2151,6 +2175,7 @@ int make_procs(const klab_engine* e, const klab_logits_proc_cfg* cfg, ProcSet& l
 }
 bool gen_shape_ok(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp) {
   if (!e->bound || g.n < 1 || g.max_length < 2 || g.max_length - 1 > e->Lt) return false;
+  if (e->ncap != 1) return false;  // a session's prefill is one decoder row per image (row b*Lt of the logits is position 0 of image b)
   if (g.want_logprobs && g.mode == KLAB_GEN_BEAM) return false;  // beam search keeps its own scores
   const int V = e->cfg.main.vocab;
   switch (g.mode) {
@@ -2554,7 +2579,7 @@ static int backward_segment(klab_engine* e, int segment, const float* dloss_dev,
   e->bucket_ev_live[segment] = false;
   if (segment == 0) {
     e->ev_next = 0;
-    const int Md = B * e->Lt, V = cfg.main.vocab;
+    const int Md = e->Bd * e->Lt, V = cfg.main.vocab;
     const float alpha = cfg.main.scale_decoder_outputs ? 1.f / sqrtf((float)d) : 1.f;
     Ctx cs{e, e->side, c.dt, c.es};
     // Clearing 242 MB of gradient slices and the bias accumulators took 36 + 12 us of the main chain (four fills in front of the
@@ -2598,8 +2623,8 @@ static int backward_segment(klab_engine* e, int segment, const float* dloss_dev,
       RC(klab_gemm(&g, cs.ws()));
     }
     float* dh0 = nullptr;
-    RC(t5_stack_backward(c, cfg.main, e->P[2], e->W[2], Gm, e->mi.dec, e->mi.dec_final, e->dec, true, STACK_DEC, p, B, e->kv_all, e->dkv_all,
-                         e->Le, (long)nld * 2 * inner, &dh0));
+    RC(t5_stack_backward(c, cfg.main, e->P[2], e->W[2], Gm, e->mi.dec, e->mi.dec_final, e->dec, true, STACK_DEC, p, e->Bd, e->kv_all, e->dkv_all,
+                         e->Le, (long)nld * 2 * inner, &dh0, e->ncap));
     // decoder input embedding: scatter-add into the tied table (second contributor); on the side stream BEHIND the
     // LM-head weight gradient, which read-modify-writes the same rows non-atomically
     RC(side_after_main(c));

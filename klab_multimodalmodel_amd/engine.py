@@ -114,6 +114,7 @@ ENGINE_SIGS = {
     "klab_engine_bucket_wait": ([C.c_void_p, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "klab_engine_set_bucket_events": ([C.c_void_p, C.c_int], C.c_int),
     "klab_engine_workspace_bytes": ([C.c_void_p, C.c_int, C.c_int, C.c_int], C.c_size_t),
+    "klab_engine_workspace_bytes_n": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
     "klab_engine_bind": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                           C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                           C.POINTER(C.c_void_p), C.c_void_p], C.c_int),
@@ -317,12 +318,16 @@ class Engine:
             out.append(ParamSpec(buf.value.decode(), tuple(shape[k] for k in range(nd.value)), go.value))
         return out
 
-    def workspace_bytes(self, B, Ls, Lt) -> int:
-        return int(self._lib.klab_engine_workspace_bytes(self._h, B, Ls, Lt))
+    def workspace_bytes(self, B, Ls, Lt, n=1) -> int:
+        """bytes of a binding of B images with n captions each: a query, it changes nothing in the engine"""
+        if int(n) < 1:
+            raise ValueError(f"captions per image has to be >= 1, got {n}")
+        return int(self._lib.klab_engine_workspace_bytes_n(self._h, B, Ls, Lt, int(n)))
 
-    def bind(self, B, Ls, Lt, tensors, main_grads, swin_grads, device):
-        """tensors: {model: [fp32 device tensors in table order]}."""
-        nbytes = self.workspace_bytes(B, Ls, Lt)
+    def bind(self, B, Ls, Lt, tensors, main_grads, swin_grads, device, n=1):
+        """tensors: {model: [fp32 device tensors in table order]}.  n: captions per image -- the decoder side of the binding runs
+        B*n target sequences in image-major order (tgt_ids [B, n, Lt]) over the B encoder outputs."""
+        nbytes = self.workspace_bytes(B, Ls, Lt, n)
         if nbytes == 0:
             raise ValueError("bad batch shape")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -353,12 +358,14 @@ class Engine:
             arrs[mname] = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         carr = (C.c_void_p * len(coords))(*[t.data_ptr() for t in coords])
         iarr = (C.c_void_p * len(index))(*[t.data_ptr() for t in index])
+        L.check(self._lib.klab_engine_set_captions(self._h, int(n)), "klab_engine_set_captions")  # one-shot: this bind takes it
         rc = self._lib.klab_engine_bind(self._h, B, Ls, Lt, ws.data_ptr(), nbytes, arrs["swin"], arrs["lang"], arrs["main"],
                                         main_grads.data_ptr(), swin_grads.data_ptr() if swin_grads is not None else None,
                                         lang_b.data_ptr(), enc_b.data_ptr(), dec_b.data_ptr(), carr, iarr, L.stream_ptr())
         L.check(rc, "klab_engine_bind")
         self._keep = (ws, lang_b, enc_b, dec_b, coords, index, tensors, main_grads, swin_grads)
         self.shape = (B, Ls, Lt)
+        self.captions = int(n)
         self.workspace = ws
         lp = self._lib.klab_engine_loss_ptr(self._h)
         off = lp - ws.data_ptr()
@@ -387,8 +394,8 @@ class Engine:
         return rc == 1
 
     def set_loss_options(self, eps=0.0, z=0.0, weights=None):
-        """label smoothing and z-loss of the forwards from now on; `weights` (fp32 [B, Lt] device tensor or None) for the next
-        forward only, which copies it (None disarms weights armed earlier)"""
+        """label smoothing and z-loss of the forwards from now on; `weights` (fp32 device tensor [B, Lt], [B, n, Lt] on a
+        binding with n captions per image, or None) for the next forward only, which copies it (None disarms weights armed earlier)"""
         L.check(self._lib.klab_engine_set_loss_options(self._h, float(eps), float(z), weights.data_ptr() if weights is not None else None),
                 "klab_engine_set_loss_options")
 

@@ -119,6 +119,7 @@ class _LossFn(torch.autograd.Function):
             eng.set_loss_options(eps, z, None)  # ... nor the one-shot loss weights
             raise
         model._token_losses_valid = True
+        model._token_losses_shape = tuple(tgt.shape)
         ctx.model = model
         ctx.eng = eng
         ctx.nparams = len(params)
@@ -254,6 +255,7 @@ class MyModel(nn.Module):
         self._loss_options = {"label_smoothing": 0.0, "z_loss": 0.0}
         self._loss_weights_next = None  # this call's target_encoding["loss_weights"], taken by _LossFn.forward
         self._token_losses_valid = False  # the engine's per-token losses are those of a loss forward of this binding
+        self._token_losses_shape = None  # ... and the shape of that forward's labels: [B, Lt] or [B, n, Lt]
         import weakref
         for p in self.transformer.parameters():  # lets klab_multimodalmodel_amd.optim.FusedAdam find its engine
             p._klab_owner = weakref.ref(self)
@@ -295,11 +297,12 @@ class MyModel(nn.Module):
 
     def _engine_for(self, pixels, src, tgt):
         B, Ls = src.shape
-        Lt = tgt.shape[1]
+        # [B, n, Lt]: n captions per image, image-major rows on the decoder side of the binding; [B, Lt] binds as n = 1
+        n, Lt = (tgt.shape[1], tgt.shape[2]) if tgt.dim() == 3 else (1, tgt.shape[1])
         dev = pixels.device
         if dev.type != "cuda":
             raise RuntimeError("klab MyModel runs on an MI355X (cuda/HIP device) only; there is no CPU fallback")
-        key = (B, Ls, Lt, dev)
+        key = (B, Ls, Lt, dev, n)
         if self._bound_key != key:
             eng = self._engine
             tensors = {"swin": [p.data for p in self.image_model.ordered()], "lang": [p.data for p in self.language_model.ordered()],
@@ -312,7 +315,7 @@ class MyModel(nn.Module):
                 self._flat["main"] = torch.zeros(eng.grad_elems["main"], device=dev)
                 self._flat["swin"] = torch.zeros(max(eng.grad_elems["swin"], 8), device=dev) if self.args.image_model_train else None
                 self._views = None
-            eng.bind(B, Ls, Lt, tensors, self._flat["main"], self._flat["swin"], dev)
+            eng.bind(B, Ls, Lt, tensors, self._flat["main"], self._flat["swin"], dev, n=n)
             eng.set_graph(self.use_graph)
             if self._pending_rng is not None:  # load_checkpoint before the first forward: continue the saved dropout stream
                 eng.set_rng(*self._pending_rng)
@@ -369,8 +372,8 @@ class MyModel(nn.Module):
         label_smoothing is torch.nn.functional.cross_entropy's (0 <= label_smoothing < 1), z_loss the coefficient of mesh-tensorflow
         T5's auxiliary z-loss (>= 0; T5, T5 v1.1 and Flan-T5 were pre-trained with 1e-4).  Per-token weights travel with the call
         instead: target_encoding["loss_weights"], a float [B, Lt] tensor on the model's device (finite, >= 0), used for that
-        forward only; the loss is sum w l / sum w over the tokens whose label is not -100.  With both options 0 and no weights the
-        forward runs exactly the launches of the plain loss.
+        forward only ([B, n, Lt] with labels [B, n, Lt]); the loss is sum w l / sum w over the tokens whose label is not -100.  With
+        both options 0 and no weights the forward runs exactly the launches of the plain loss.
         These are hyper-parameters of the training script, not model state: save, state_dict and checkpoint.py do not store them.
         Under klab DDP every rank normalises by its own sum of weights, exactly as it normalises by its own count of scored tokens
         without them."""
@@ -387,12 +390,12 @@ class MyModel(nn.Module):
         return dict(self._loss_options)
 
     def token_losses(self):
-        """fp32 [B, Lt] device tensor: a copy of the per-token losses l of the last loss forward (unweighted, with the loss options
-        of that forward; 0 where the label is -100).  sum w l / sum w over the scored tokens is the loss that forward returned."""
+        """fp32 [B, Lt] device tensor ([B, n, Lt] after a forward on [B, n, Lt] labels): a copy of the per-token losses l of the last
+        loss forward (unweighted, with the loss options of that forward; 0 where the label is -100).  sum w l / sum w over the scored
+        tokens is the loss that forward returned."""
         if not self._token_losses_valid:
             raise RuntimeError("token_losses(): no loss forward has run on this binding yet (generate and score keep none)")
-        B, _Ls, Lt = self._bound_key[:3]
-        return self._engine.buffer("loss_row").view(B, Lt).clone()
+        return self._engine.buffer("loss_row").view(self._token_losses_shape).clone()
 
     def flat_grads(self, model="main"):
         return self._flat.get(model)
@@ -421,13 +424,22 @@ class MyModel(nn.Module):
         src = src.to(torch.int64).contiguous()
         if return_loss:
             tgt = target_encoding["input_ids"].to(torch.int64).contiguous()
+            # n captions per image: labels [B, n, Lt] over the B images (one pass of the Swin tower and both encoders per image); the
+            # loss is the 2-D call's on pixel_values / source ids repeat_interleave(n, 0) and the labels viewed [B*n, Lt] -- one mean
+            # over the scored tokens of all captions.  A caption whose labels are all -100 (an image with fewer captions) adds nothing.
+            grouped = tgt.dim() == 3
+            if tgt.dim() not in (2, 3) or tgt.shape[0] != src.shape[0] or 0 in tgt.shape:
+                raise ValueError(f"target_encoding['input_ids'] has to be [B, Lt] or [B, n, Lt] with B = {src.shape[0]} (the images) and "
+                                 f"n >= 1 captions per image, got {tuple(tgt.shape)}")
             weights = target_encoding["loss_weights"] if "loss_weights" in target_encoding else None
             if weights is not None:
                 if not torch.is_tensor(weights) or not weights.is_floating_point() or tuple(weights.shape) != tuple(tgt.shape):
-                    raise ValueError(f"target_encoding['loss_weights'] has to be a float tensor {tuple(tgt.shape)}, got "
+                    raise ValueError(f"target_encoding['loss_weights'] has to be a float tensor {'[B, n, Lt] = ' if grouped else ''}"
+                                     f"{tuple(tgt.shape)}, got "
                                      f"{getattr(weights, 'dtype', type(weights))} {tuple(getattr(weights, 'shape', ()))}")
                 if weights.device != tgt.device:
-                    raise ValueError(f"target_encoding['loss_weights'] is on {weights.device}, the labels on {tgt.device}")
+                    raise ValueError(f"target_encoding['loss_weights'] {'[B, n, Lt] ' if grouped else ''}is on {weights.device}, "
+                                     f"the labels on {tgt.device}")
                 weights = weights.detach().to(torch.float32).contiguous()
             self._loss_weights_next = weights
             params = self._trainable()

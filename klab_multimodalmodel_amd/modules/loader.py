@@ -15,6 +15,7 @@ import torch
 from PIL import Image
 
 COCO_PROMPT = 'What does th image describe ?'  # verbatim, ref/modules/loader.py:38
+NO_CAPTION = ''  # fills an image's caption list up to captions_per_image; group_targets labels such a caption -100 throughout
 
 
 def pil_to_tensor01(image):
@@ -72,18 +73,27 @@ class DatasetLoader(torch.utils.data.Dataset):
 
 
 class COCODatasetLoader(DatasetLoader):
-    def __init__(self, data_dir='/data/datatset/mscoco2017', phase='train'):
+    # captions_per_image (klab extension; the reference keeps `loadAnns(...)[0]` only): 1 -- the item's target is the image's first
+    # caption, a string, as in the reference; n > 1 -- a list of its first n captions in file order, filled up with NO_CAPTION
+    # where the image has fewer.  MyModel.forward trains on all of them with one encoder pass per image (labels [B, n, Lt],
+    # see flatten_captions / group_targets).
+    def __init__(self, data_dir='/data/datatset/mscoco2017', phase='train', captions_per_image=1):
         super().__init__()
+        n = int(captions_per_image)
+        if n < 1:
+            raise ValueError(f"`captions_per_image` has to be a positive integer, but is {captions_per_image}")
+        self.captions_per_image = n
         with open(os.path.join(data_dir, 'annotations', f'captions_{phase}2017.json')) as f:
             ann = json.load(f)
-        first_caption = {}
-        for a in ann['annotations']:  # first annotation per image, in file order (= coco.getAnnIds(image_id)[0])
-            first_caption.setdefault(a['image_id'], a['caption'])
+        captions = {}
+        for a in ann['annotations']:  # annotations per image, in file order (= coco.getAnnIds(image_id)); [0] is the reference's
+            captions.setdefault(a['image_id'], []).append(a['caption'])
         img_dir = os.path.join(data_dir, f'{phase}2017')
         for info in ann['images']:
             self.images.append(os.path.join(img_dir, info['file_name']))
             self.src_texts.append(COCO_PROMPT)
-            self.tgt_texts.append(first_caption[info['id']])
+            caps = captions[info['id']]
+            self.tgt_texts.append(caps[0] if n == 1 else caps[:n] + [NO_CAPTION] * (n - len(caps[:n])))
 
 
 class RedCapsDatasetLoader(DatasetLoader):
@@ -107,6 +117,40 @@ def collate_decoded(batch):
     list of tgt texts)"""
     images, src, tgt = zip(*batch)
     return list(images), list(src), list(tgt)
+
+
+def flatten_captions(tgt, image_major=True):
+    """the B*n target strings of a batch of captions_per_image = n items in image-major order (image 0's n captions, then image
+    1's, ...): what the tokenizer is called on.  image_major=True: tgt is [B][n], as collate_decoded (or any collate that keeps
+    the items' lists) leaves it; False: [n][B], as torch's default collate transposes a batch of lists."""
+    rows = [list(r) for r in tgt]
+    if not rows or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("every image needs the same number of captions (COCODatasetLoader(captions_per_image=n) fills them up)")
+    if not image_major:
+        rows = [list(r) for r in zip(*rows)]
+    return [c for r in rows for c in r]
+
+
+def group_targets(encoding, texts, n):
+    """target_encoding for MyModel.forward from a tokenizer output over the B*n strings of flatten_captions: every [B*n, Lt] tensor
+    of `encoding` (input_ids, attention_mask, ...) viewed [B, n, Lt]; the labels of the captions that are NO_CAPTION set to -100
+    throughout, so that they add nothing to the loss or the gradients."""
+    n = int(n)
+    if n < 1 or len(texts) % n:
+        raise ValueError(f"{len(texts)} target strings are no multiple of n = {n} captions per image")
+    out = {}
+    for k in encoding.keys():
+        v = encoding[k]
+        if torch.is_tensor(v):
+            if v.dim() != 2 or v.shape[0] != len(texts):
+                raise ValueError(f"encoding[{k!r}] has to be [B*n, Lt] = [{len(texts)}, Lt], got {tuple(v.shape)}")
+            v = v.reshape(len(texts) // n, n, v.shape[1])
+        out[k] = v
+    if "input_ids" not in out or not torch.is_tensor(out["input_ids"]):
+        raise ValueError("encoding needs an `input_ids` tensor (tokenizer(..., return_tensors='pt'))")
+    empty = torch.tensor([t == NO_CAPTION for t in texts], dtype=torch.bool, device=out["input_ids"].device)
+    out["input_ids"] = out["input_ids"].masked_fill(empty.view(-1, n, 1), -100)
+    return out
 
 
 def get_dataloader(args, phase, rank):
