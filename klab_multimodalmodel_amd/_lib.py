@@ -186,6 +186,7 @@ SIGNATURES = {
     "klab_swin_cpb_bias": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "klab_swin_cpb_table": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "klab_swin_cpb_table_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "klab_swin_cpb_bias_bwd_pz": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "klab_cast_pack": [vp, i32, i64, vp, i32, vp],
     "klab_embed_fwd": [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, f32, vp, u32, vp, vp],
     "klab_embed_bwd": [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, f32, vp, u32, vp],

@@ -360,6 +360,31 @@ def decode_attn_map(q, k, out, *, R, H, Lk, dk, q_bstride, kv_bstride, ldk, out_
             "klab_t5_decode_attn_map")
 
 
+def decode_attn(q, k, v, ctx, *, R, H, Lk, dk, q_bstride, kv_bstride, ldk, ctx_bstride, kv_group=1, kv_slot=None, slot_ld=0,
+                bias_row=None, bias_ld=0):
+    """ctx[r*ctx_bstride + h*dk + c] = sum_j softmax_j(q_h . k_{h,j} + bias_row[h, j]) v_{h,j,c} (unscaled scores) for the one query
+    row of each of R decoding rows: row r's query at q + r*q_bstride; key j of row r at k + s*kv_bstride + j*ldk with
+    s = kv_slot[r*slot_ld + j] (int32 [R, slot_ld]) or, without a table, s = r // kv_group; v likewise; head h at column h*dk
+    (element strides; q, k, v and ctx bf16 or f32, the same).  bias_row f32 [H, bias_ld] or None.  q, k, v may be views into one
+    cache: only their data pointers are used (klab_t5_beam_decode_attn, csrc/attn_t5.hip)."""
+    if q is None or k is None or v is None or ctx is None:
+        raise ValueError("decode_attn: q, k, v and ctx are required")
+    if not (q.dtype == k.dtype == v.dtype == ctx.dtype) or q.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("decode_attn: q, k, v and ctx share one dtype, bf16 or f32")
+    if R <= 0 or H <= 0 or Lk <= 0 or kv_group < 1:
+        raise ValueError("decode_attn: R, H, Lk and kv_group are positive")
+    if kv_slot is not None and (kv_slot.dtype != torch.int32 or slot_ld < Lk):
+        raise ValueError("decode_attn: kv_slot is int32 with a pitch of at least Lk")
+    if bias_row is not None and (bias_row.dtype != torch.float32 or bias_ld < Lk):
+        raise ValueError("decode_attn: bias_row is float32 with a pitch of at least Lk")
+    if dk not in (8, 16, 32, 64, 128):
+        raise NotImplementedError(f"decode_attn: head dim {dk} (8, 16, 32, 64 or 128)")
+    lib = L.load()
+    L.check(lib.klab_t5_beam_decode_attn(L.dtype_code(q.dtype), q.data_ptr(), q_bstride, k.data_ptr(), v.data_ptr(), kv_bstride, ldk,
+                                         kv_group, L.ptr(kv_slot), slot_ld, L.ptr(bias_row), bias_ld, ctx.data_ptr(), ctx_bstride, R, H, Lk,
+                                         dk, L.stream_ptr()), "klab_t5_beam_decode_attn")
+
+
 def _swin_args(qkv, ctx, bias, logit_scale, lse, B, R, w, shift, H, Cc, bias_table=None, v_bias=None, dv_bias=None):
     a = L.SwinAttnArgs()
     a.v_bias, a.dv_bias = L.ptr(v_bias), L.ptr(dv_bias)
@@ -421,6 +446,22 @@ def swin_cpb_table_bwd(dbias_table, bias_table, coords, hidden, w2, dtable, dw0,
     L.check(lib.klab_swin_cpb_table_bwd(dbias_table.data_ptr(), bias_table.data_ptr(), coords.data_ptr(), hidden.data_ptr(), w2.data_ptr(),
                                         dtable.data_ptr(), dw0.data_ptr(), db0.data_ptr(), dw2.data_ptr(), coords.shape[0], heads,
                                         hidden.shape[1], L.stream_ptr()), "klab_swin_cpb_table_bwd")
+
+
+def swin_cpb_bias_bwd(dbias, bias, index, coords, hidden, w2, dtable, dw0, db0, dw2, *, heads, n=None, ntab=None, nhidden=None,
+                      dtable_zeroed=False, w0=None):
+    """backward of swin_cpb_bias from the dense dbias [H, n*n]: dtable [ntab, H] is scratch and result (cleared here unless
+    dtable_zeroed says the caller did; the scatter then adds to whatever it holds), dw0 [nh, 2], db0 [nh] and dw2 [H, nh] are
+    ACCUMULATED into.  n, ntab and nhidden default to what index, coords and hidden say (klab_swin_cpb_bias_bwd_pz; w0 is unused by
+    the gradient and may stay None)."""
+    lib = L.load()
+    ntab = coords.shape[0] if ntab is None else ntab
+    nhidden = hidden.shape[1] if nhidden is None else nhidden
+    n = int(round(index.numel() ** 0.5)) if n is None else n
+    L.check(lib.klab_swin_cpb_bias_bwd_pz(dbias.data_ptr(), bias.data_ptr(), index.data_ptr(), coords.data_ptr(), hidden.data_ptr(),
+                                          L.ptr(w0), w2.data_ptr(), dtable.data_ptr(), dw0.data_ptr(), db0.data_ptr(), dw2.data_ptr(),
+                                          ntab, n, heads, nhidden, 1 if dtable_zeroed else 0, L.stream_ptr()),
+            "klab_swin_cpb_bias_bwd_pz")
 
 
 def ce_fwd(logits, labels, inv_n, loss_row, loss, write_grad=True):
