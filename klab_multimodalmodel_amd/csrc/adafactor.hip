@@ -1,5 +1,5 @@
 // Fused multi-tensor Adafactor (math of transformers.optimization.Adafactor) for the trainable T5, with the compute-dtype
-// shadow copy the Adam step also writes (misc.hip, adam_step_kernel).  Four launches, whatever the number of tensors:
+// shadow copy the Adam step also writes (adamw.hip, adam_step_kernel).  Four launches, whatever the number of tensors:
 //
 //   (a)  stats   g, p in            row sums / column partial sums of g^2 + eps0, sum p^2; R (and the 1-D tensors' V) updated
 //   (a') reduce  partials in        column partials -> C (EMA folded in), mean(R), RMS(p), the factors rsqrt(R/mean R), rsqrt(C)
@@ -19,10 +19,10 @@
 
 #include "common.h"
 #include "klab_mm.h"
+#include "multi_tensor.h"  // AfDesc
 
 namespace klab {
 
-struct AfDesc { float* p; long goff, aoff, rows, cols, soff, tile0, tile_len, poff, factored; };  // klab_mm.h: 10 longs
 struct AfHyper { float beta2t, omb2, eps0, eps1, rel, clip, beta1, omb1, wd; int scale_param, use_m; };
 
 constexpr int AF_MAXD = 1024;     // tensors whose search keys fit the LDS copy (T5-large: ~560)

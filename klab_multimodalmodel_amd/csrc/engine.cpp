@@ -26,6 +26,7 @@
 
 #include "gemm_shared.h"  // klab::tl_launch_probe: a launch carries the probe's events as its own start / stop events
 #include "klab_mm.h"
+#include "multi_tensor.h"  // the descriptor tables the multi-tensor kernels read
 
 namespace {
 
@@ -34,6 +35,15 @@ namespace {
     int rc__ = (x);           \
     if (rc__ != 0) return rc__; \
   } while (0)
+
+// Bind time only: copy a host table to its device buffer and wait, so that the vector may go out of scope.
+template <typename D>
+int upload_table(void* dst, const std::vector<D>& d, hipStream_t s) {
+  if (d.empty()) return 0;
+  hipError_t er = hipMemcpyAsync(dst, d.data(), d.size() * sizeof(D), hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  return (int)er;
+}
 
 struct ParamInfo {
   std::string name;
@@ -538,7 +548,7 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
   if (e->fp8) {
     e->w8 = b.take((size_t)e->warena_elems);
     e->wscale = (float*)b.take((size_t)(e->warena_elems / 8 + 1) * 4);
-    e->qdesc = b.take(sizeof(long) * 4 * (e->P[0].size() + e->P[1].size() + e->P[2].size() + 1));
+    e->qdesc = b.take(sizeof(klab::QuantDesc) * (e->P[0].size() + e->P[1].size() + e->P[2].size() + 1));
     // activation staging: the widest A operand of any forward Linear (rows x K bytes) and its row scales
     const long R0q = c.swin.image_size / c.swin.patch;
     long mk = Mx * (c.main.d_ff > c.main.d_model ? c.main.d_ff : c.main.d_model);
@@ -556,10 +566,10 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
     e->xscales = (float*)b.take((size_t)e->xscales_rows * 4);
   }
   // two descriptor groups (trainable / frozen); the patch-embedding weight contributes one descriptor per row
-  e->cast_desc = b.take(sizeof(long) * 3 * 2 * (e->P[0].size() + e->P[1].size() + e->P[2].size() + c.swin.embed_dim + 1));
-  e->fcast_desc = b.take(sizeof(long) * 3 * (e->P[0].size() + 1));
-  e->adam_desc = b.take(sizeof(long) * 4 * (e->P[2].size() + 1));
-  e->af_desc = b.take(sizeof(long) * 10 * (e->P[2].size() + 1));
+  e->cast_desc = b.take(sizeof(klab::CastDesc) * 2 * (e->P[0].size() + e->P[1].size() + e->P[2].size() + c.swin.embed_dim + 1));
+  e->fcast_desc = b.take(sizeof(klab::CastDesc) * (e->P[0].size() + 1));
+  e->adam_desc = b.take(sizeof(klab::AdamDesc) * (e->P[2].size() + 1));
+  e->af_desc = b.take(sizeof(klab::AfDesc) * (e->P[2].size() + 1));
   {
     const int nle = c.main.n_layers, nldx = c.main.n_dec_layers;
     const int ncmax = (2 * nle + 1) > (3 * nldx + 1) ? (2 * nle + 1) : (3 * nldx + 1);
@@ -1515,11 +1525,10 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
     if (w <= 0) return KLAB_ERR_UNSUPPORTED;
     e->swin_ntab[st] = (2 * w - 1) * (2 * w - 1);
   }
-  // cast descriptors: {src, dst_off, n4_prefix}
   hipStream_t hs = (hipStream_t)stream;
   for (int grp = 0; grp < 2; ++grp) {  // 0: trainable (main, and Swin when --image_model_train), 1: frozen (lang, frozen Swin)
-    std::vector<long> d;
-    long pre = 0; int n = 0;
+    std::vector<klab::CastDesc> d;
+    long pre = 0;
     for (int m = 0; m < 3; ++m) {
       const bool frozen = (m == 1) || (m == 0 && !e->cfg.train_swin);
       if (frozen != (grp == 1)) continue;
@@ -1530,25 +1539,21 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
         if (m == 0 && (int)i == e->si.pew && e->pe_kp != e->pe_k0) {  // row by row into the padded pitch
           if (e->pe_k0 % 4) return KLAB_ERR_UNSUPPORTED;
           for (int r = 0; r < e->cfg.swin.embed_dim; ++r) {
-            d.push_back((long)(e->W[m][i] + (long)r * e->pe_k0)); d.push_back(p.warena_off + (long)r * e->pe_kp); d.push_back(pre);
-            pre += e->pe_k0 / 4; ++n;
+            d.push_back({e->W[m][i] + (long)r * e->pe_k0, p.warena_off + (long)r * e->pe_kp, pre});
+            pre += e->pe_k0 / 4;
           }
           continue;
         }
-        d.push_back((long)e->W[m][i]); d.push_back(p.warena_off); d.push_back(pre);
-        pre += p.numel / 4; ++n;
+        d.push_back({e->W[m][i], p.warena_off, pre});
+        pre += p.numel / 4;
       }
     }
+    const int n = (int)d.size();
     const size_t grp_cap = e->P[0].size() + e->P[1].size() + e->P[2].size() + e->cfg.swin.embed_dim + 1;
-    void* dst = grp == 0 ? e->cast_desc : (void*)((char*)e->cast_desc + sizeof(long) * 3 * grp_cap);
+    void* dst = (klab::CastDesc*)e->cast_desc + (size_t)grp * grp_cap;
     if (grp == 1) { e->cast_desc_frozen = dst; e->n_cast_frozen = n; e->cast_total4_frozen = pre; }
-    if (n == 0) { if (grp == 0) { e->n_cast = 0; e->cast_total4 = 0; } continue; }
-    hipError_t er0 = hipMemcpyAsync(dst, d.data(), d.size() * sizeof(long), hipMemcpyHostToDevice, hs);
-    if (er0 != hipSuccess) return (int)er0;
-    er0 = hipStreamSynchronize(hs);  // bind time only (d goes out of scope)
-    if (er0 != hipSuccess) return (int)er0;
-    if (grp == 1) continue;
-    e->n_cast = n; e->cast_total4 = pre;
+    else { e->n_cast = n; e->cast_total4 = pre; }
+    RC(upload_table(dst, d, hs));
   }
   e->frozen_valid = false;
   e->seg1_zeroed = e->dbias_zeroed[0] = e->dbias_zeroed[1] = e->denc_in_dxn = false;  // (hand-offs between backward segments of the OLD binding)
@@ -1563,69 +1568,55 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
     RC((int)hipMemsetAsync((char*)e->warena + (size_t)e->P[0][e->si.pew].warena_off * e->es, 0,
                            (size_t)e->cfg.swin.embed_dim * e->pe_kp * e->es, hs));
   {
-    std::vector<long> d;
-    long pre = 0; int n = 0;
+    std::vector<klab::CastDesc> d;
+    long pre = 0;
     for (size_t i = 0; i < e->P[0].size(); ++i) {
       const ParamInfo& p = e->P[0][i];
       if (p.farena_off < 0) continue;
       if (p.numel % 4) return KLAB_ERR_UNSUPPORTED;
-      d.push_back((long)e->W[0][i]); d.push_back(p.farena_off); d.push_back(pre);
-      pre += p.numel / 4; ++n;
+      d.push_back({e->W[0][i], p.farena_off, pre});
+      pre += p.numel / 4;
     }
-    e->n_fcast = n; e->fcast_total4 = pre;
+    e->n_fcast = (int)d.size(); e->fcast_total4 = pre;
     RC((int)hipMemsetAsync(e->farena, 0, (size_t)e->farena_elems * 4, hs));
-    if (n) {
-      hipError_t er = hipMemcpyAsync(e->fcast_desc, d.data(), d.size() * sizeof(long), hipMemcpyHostToDevice, hs);
-      if (er != hipSuccess) return (int)er;
-      er = hipStreamSynchronize(hs);
-      if (er != hipSuccess) return (int)er;
-    }
+    RC(upload_table(e->fcast_desc, d, hs));
   }
   if (e->fp8) {  // fp8 weight table: every arena tensor as rows x K (the padded patch-embedding weight stays bf16)
-    std::vector<long> d;
-    long row0 = 0; int n = 0;
+    std::vector<klab::QuantDesc> d;
+    long row0 = 0;
     for (int m = 0; m < 3; ++m)
       for (size_t i = 0; i < e->P[m].size(); ++i) {
         const ParamInfo& p = e->P[m][i];
         if (p.warena_off < 0 || p.shape.empty() || (m == 0 && (int)i == e->si.pew)) continue;
         const long rows = p.shape[0], K = p.numel / rows;
         if (!fp8_weight_ok(K) || (p.warena_off & 15)) continue;
-        d.push_back(p.warena_off); d.push_back(rows); d.push_back(K); d.push_back(row0);
-        row0 += rows; ++n;
+        d.push_back({p.warena_off, rows, K, row0});
+        row0 += rows;
       }
-    e->n_qdesc = n; e->q_rows = row0;
-    if (n) {
-      hipError_t er = hipMemcpyAsync(e->qdesc, d.data(), d.size() * sizeof(long), hipMemcpyHostToDevice, hs);
-      if (er != hipSuccess) return (int)er;
-      er = hipStreamSynchronize(hs);
-      if (er != hipSuccess) return (int)er;
-    }
+    e->n_qdesc = (int)d.size(); e->q_rows = row0;
+    RC(upload_table(e->qdesc, d, hs));
   }
-  std::vector<long> adam_tab;  // host copies of both optimizer tables stay alive until their one synchronise
   {  // fused Adam descriptors: every trainable tensor of the main T5 (tied tables appear once)
-    std::vector<long> d;
-    long pre = 0; int n = 0;
+    std::vector<klab::AdamDesc> d;
+    long pre = 0;
     bool ok = true;
     // tensors of backward segment 0 first, then segment 1: a prefix range of the table = one segment (the optimizer may
     // update segment 0 while segment 1's gradient all-reduce is still in flight, klab_engine_adam_step_segment)
     for (int seg = 0; seg < 2 && ok; ++seg) {
-      if (seg == 1) { e->adam_split4 = pre; e->n_adam_seg0 = n; }
+      if (seg == 1) { e->adam_split4 = pre; e->n_adam_seg0 = (int)d.size(); }
       for (size_t i = 0; i < e->P[2].size(); ++i) {
         const ParamInfo& p = e->P[2][i];
         if (p.grad_off < 0 || (p.grad_off >= e->seg_off[1]) != (seg == 1)) continue;
         if (p.numel % 4 || (p.grad_off & 3) || (p.warena_off >= 0 && (p.warena_off & 3))) { ok = false; break; }
-        d.push_back((long)e->W[2][i]); d.push_back(p.grad_off); d.push_back(p.warena_off); d.push_back(pre);
-        pre += p.numel / 4; ++n;
+        d.push_back({const_cast<float*>(e->W[2][i]), p.grad_off, p.warena_off, pre});
+        pre += p.numel / 4;
       }
     }
-    e->n_adam = ok ? n : 0; e->adam_total4 = pre;
+    if (!ok) d.clear();
+    e->n_adam = (int)d.size(); e->adam_total4 = pre;
     e->adam_ptrs.clear();
-    for (int k = 0; k < e->n_adam; ++k) e->adam_ptrs.push_back(d[(size_t)k * 4]);
-    if (e->n_adam) {  // (the synchronise is shared with the Adafactor table below: adam_tab lives until then)
-      hipError_t er = hipMemcpyAsync(e->adam_desc, d.data(), d.size() * sizeof(long), hipMemcpyHostToDevice, hs);
-      if (er != hipSuccess) return (int)er;
-    }
-    adam_tab.swap(d);
+    for (const klab::AdamDesc& a : d) e->adam_ptrs.push_back((long)a.p);
+    RC(upload_table(e->adam_desc, d, hs));
   }
   {  // fused Adafactor descriptors: the same tensors in the same order; rows = product of all dims but the last, 1-D = unfactored
     std::vector<long> rows, cols, idx;
@@ -1639,22 +1630,17 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
         cols.push_back(p.shape.size() >= 2 ? c : p.numel); idx.push_back((long)i);
       }
     const int n = (int)idx.size();
-    std::vector<long> plan((size_t)n * 4), d;
+    std::vector<long> plan((size_t)n * 4);
+    std::vector<klab::AfDesc> d;
     e->n_af = 0;
     if (e->n_adam == n && n > 0 && klab_adafactor_plan(n, rows.data(), cols.data(), fact.data(), plan.data(), e->af_totals) == KLAB_OK) {
       for (int k = 0; k < n; ++k) {
         const ParamInfo& p = e->P[2][idx[k]];
-        const long v[10] = {(long)e->W[2][idx[k]], p.grad_off, p.warena_off, rows[k], cols[k], plan[k * 4 + 0], plan[k * 4 + 1],
-                            plan[k * 4 + 2], plan[k * 4 + 3], (long)fact[k]};
-        d.insert(d.end(), v, v + 10);
+        d.push_back({const_cast<float*>(e->W[2][idx[k]]), p.grad_off, p.warena_off, rows[k], cols[k], plan[k * 4 + 0], plan[k * 4 + 1],
+                     plan[k * 4 + 2], plan[k * 4 + 3], (long)fact[k]});
       }
-      hipError_t er = hipMemcpyAsync(e->af_desc, d.data(), d.size() * sizeof(long), hipMemcpyHostToDevice, hs);
-      if (er != hipSuccess) return (int)er;
+      RC(upload_table(e->af_desc, d, hs));
       e->n_af = n;
-    }
-    if (e->n_adam) {
-      hipError_t er = hipStreamSynchronize(hs);
-      if (er != hipSuccess) return (int)er;
     }
   }
   for (int st = 0; st < 2; ++st) {  // norm-weight gradient destinations in the order the stack's backward visits them
@@ -1669,10 +1655,7 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
       dst.push_back(Gm + e->P[2][L[i].ln0].grad_off);
     }
     e->rms_ncalls[st] = (int)dst.size();
-    hipError_t er = hipMemcpyAsync(e->rms_dst_dev[st], dst.data(), dst.size() * sizeof(float*), hipMemcpyHostToDevice, hs);
-    if (er != hipSuccess) return (int)er;
-    er = hipStreamSynchronize(hs);
-    if (er != hipSuccess) return (int)er;
+    RC(upload_table(e->rms_dst_dev[st], dst, hs));
   }
   RC((int)hipMemsetAsync(e->seed_dev, 0, 512, hs));
   for (auto& g : e->gs) {  // rebinding drops the captured graphs (drained above)

@@ -22,6 +22,7 @@
 #include <utility>
 #include "klab_mm.h"
 #include "gemm_shared.h"
+#include "multi_tensor.h"
 
 #ifndef KLAB_GLDS_STAGES
 #define KLAB_GLDS_STAGES 4
@@ -845,8 +846,7 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __res
   if (row >= M) return;
   quant_row_fp8(x + (long)row * ldx, K, x8 + (long)row * ld8, scale + (long)row * scale_stride, threadIdx.x & 63);
 }
-// every GEMM weight of the compute-dtype arena at once: desc[i] = {arena element offset, rows, K, first global row}
-struct QuantDesc { long off; long rows; long K; long row0; };
+// every GEMM weight of the compute-dtype arena at once (QuantDesc: multi_tensor.h)
 __global__ __launch_bounds__(256) void quant_fp8_arena_kernel(const QuantDesc* __restrict__ dglob, int nd, long total_rows,
                                                               const bf16_t* __restrict__ arena, uint8_t* __restrict__ w8,
                                                               float* __restrict__ wscale) {

@@ -17,7 +17,7 @@
 //
 // A workgroup finds the tensor that owns a chunk by a binary search over the prefix sums of the tensors' partial counts.  Those
 // are built in LDS, from a tile of up to GC_MAXT table entries at a time: a table of up to 1024 tensors is read once per
-// workgroup and the search never leaves LDS (the chain of dependent loads described at adam_step_kernel, misc.hip); a longer
+// workgroup and the search never leaves LDS (the chain of dependent loads described in multi_tensor.h); a longer
 // table is walked tile by tile from global memory.
 #include <math.h>
 

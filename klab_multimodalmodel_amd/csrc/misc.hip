@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "klab_mm.h"
+#include "multi_tensor.h"
 
 namespace klab {
 
@@ -29,28 +30,13 @@ int ensure_dyn_lds(const void* kernel, size_t bytes) {
 // The master weights stay fp32 nn.Parameters (the reference trains in fp32, ref/train.py:25-28);
 // once per step the GEMM weights are cast into ONE arena in compute dtype, laid out so that q|k|v
 // (and all decoder layers' cross k|v) are row-concatenated: fused projections need no copies.
-struct CastDesc { const float* src; long dst_off; long n4_prefix; };  // prefix in units of 4 elements
-
 template <typename T>
 __global__ __launch_bounds__(256) void cast_pack_kernel(const CastDesc* __restrict__ dglob, int nd, long total4, T* __restrict__ dst) {
-  // the descriptor table in LDS: the search below is a chain of dependent loads (see adam_step_kernel)
-  constexpr int MAXD = 1024;
-  __shared__ CastDesc dsh[MAXD];
-  if (nd <= MAXD) {
-    for (int i = threadIdx.x; i < nd; i += blockDim.x) dsh[i] = dglob[i];
-    __syncthreads();
-  }
-  const CastDesc* d = nd <= MAXD ? dsh : dglob;
-  // A thread converts U vec4's, blockDim apart (so every wave-instruction is a contiguous 1 KiB read), all U loads in
-  // flight at once; the descriptor is found by ONE binary search per thread and then walked forward (a search per
-  // vec4 was 7 dependent loads in front of every 16-byte read: 2.4 TB/s; tensors are far longer than U*256 vec4's).
-  constexpr int U = 8;
+  __shared__ CastDesc dsh[MT_MAXD];
+  TableWalker<CastDesc> w{mt_stage_table(dsh, dglob, nd), nd, 0};
+  constexpr int U = 8;  // all U loads in flight at once (multi_tensor.h)
   for (long g0 = ((long)blockIdx.x * U) * blockDim.x + threadIdx.x; g0 < total4; g0 += (long)gridDim.x * U * blockDim.x) {
-    int lo = 0, hi = nd - 1;
-    while (lo < hi) {  // last descriptor with prefix <= g0
-      const int mid = (lo + hi + 1) >> 1;
-      if (d[mid].n4_prefix <= g0) lo = mid; else hi = mid - 1;
-    }
+    w.seek(g0);
     f32x4 v[U];
     T* o[U];
 #pragma unroll
@@ -58,85 +44,14 @@ __global__ __launch_bounds__(256) void cast_pack_kernel(const CastDesc* __restri
       const long g = g0 + (long)u * blockDim.x;
       o[u] = nullptr;
       if (g < total4) {
-        while (lo + 1 < nd && d[lo + 1].n4_prefix <= g) ++lo;
-        const long local = (g - d[lo].n4_prefix) * 4;
-        v[u] = *reinterpret_cast<const f32x4*>(d[lo].src + local);
-        o[u] = dst + d[lo].dst_off + local;
+        const long local = w.advance(g);
+        v[u] = *reinterpret_cast<const f32x4*>(w.cur().src + local);
+        o[u] = dst + w.cur().dst_off + local;
       }
     }
 #pragma unroll
     for (int u = 0; u < U; ++u)
-      if (o[u]) {
-        if constexpr (sizeof(T) == 2) *reinterpret_cast<bf16x4*>(o[u]) = bf16x4{(bf16_t)v[u][0], (bf16_t)v[u][1], (bf16_t)v[u][2], (bf16_t)v[u][3]};
-        else *reinterpret_cast<f32x4*>(o[u]) = v[u];
-      }
-  }
-}
-
-// ---- fused multi-tensor Adam with a compute-dtype shadow copy (math of torch.optim.Adam, ref/train.py:28) ----
-// One pass over the trainable tensors: p, g, m, v in (16-byte vectors), p, m, v out, and -- for GEMM weights -- the
-// bf16/f32 copy the next forward's GEMMs read, written straight into the engine's weight arena (the separate cast pass
-// over the masters disappears).  m / v live in flat buffers laid out like the flat gradient buffer.
-struct AdamDesc { float* p; long goff; long aoff; long n4_prefix; };  // aoff < 0: no arena copy
-struct AdamHyper { float lr_over_bc1, beta1, beta2, eps, weight_decay, inv_sqrt_bc2; };
-
-template <typename T, int U = 4>
-__global__ __launch_bounds__(256) void adam_step_kernel(const AdamDesc* __restrict__ dglob, int nd, long begin4, long total4, const float* __restrict__ grads,
-                                                        float* __restrict__ m, float* __restrict__ v, T* __restrict__ arena, AdamHyper h) {
-  // The descriptor table (one entry per tensor: ~130 for T5-small) is searched once per thread and iteration -- eight DEPENDENT loads,
-  // then three more per vector for the tensor's addresses.  From global memory that chain (~1.5 us of L2 round trips) ran in front
-  // of every batch of streaming loads and kept the kernel at 4.5 TB/s; a copy in LDS makes it ~100 cycles per step.
-  constexpr int MAXD = 1024;  // (T5-large: ~560 tensors; 32 KiB)
-  __shared__ AdamDesc dsh[MAXD];
-  const bool in_lds = nd <= MAXD;
-  if (in_lds) {
-    for (int i = threadIdx.x; i < nd; i += blockDim.x) dsh[i] = dglob[i];
-    __syncthreads();
-  }
-  const AdamDesc* d = in_lds ? dsh : dglob;
-  // vec4 indices [begin4, total4) of the descriptor table's prefix space (a sub-range = the tensors of one backward segment)
-  for (long g0 = begin4 + ((long)blockIdx.x * U) * blockDim.x + threadIdx.x; g0 < total4; g0 += (long)gridDim.x * U * blockDim.x) {
-    int lo = 0, hi = nd - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (d[mid].n4_prefix <= g0) lo = mid; else hi = mid - 1;
-    }
-    f32x4 pv[U], gv[U], mv[U], vv[U];
-    float* pp[U]; long go[U]; long ao[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long g = g0 + (long)u * blockDim.x;
-      pp[u] = nullptr;
-      if (g < total4) {
-        while (lo + 1 < nd && d[lo + 1].n4_prefix <= g) ++lo;
-        const long local = (g - d[lo].n4_prefix) * 4;
-        pp[u] = d[lo].p + local; go[u] = d[lo].goff + local; ao[u] = d[lo].aoff < 0 ? -1 : d[lo].aoff + local;
-        pv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(pp[u]));
-        gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(grads + go[u]));
-        mv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + go[u]));
-        vv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + go[u]));
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (pp[u]) {
-        f32x4 po, mo, vo;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float g = gv[u][i] + h.weight_decay * pv[u][i];
-          mo[i] = mv[u][i] + (1.f - h.beta1) * (g - mv[u][i]);         // exp_avg.lerp_(grad, 1 - beta1)
-          vo[i] = h.beta2 * vv[u][i] + (1.f - h.beta2) * g * g;        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-          const float denom = sqrtf(vo[i]) * h.inv_sqrt_bc2 + h.eps;
-          po[i] = pv[u][i] - h.lr_over_bc1 * (mo[i] / denom);
-        }
-        __builtin_nontemporal_store(po, reinterpret_cast<f32x4*>(pp[u]));
-        __builtin_nontemporal_store(mo, reinterpret_cast<f32x4*>(m + go[u]));
-        __builtin_nontemporal_store(vo, reinterpret_cast<f32x4*>(v + go[u]));
-        if (ao[u] >= 0) {
-          if constexpr (sizeof(T) == 2) *reinterpret_cast<bf16x4*>(arena + ao[u]) = bf16x4{(bf16_t)po[0], (bf16_t)po[1], (bf16_t)po[2], (bf16_t)po[3]};
-          else *reinterpret_cast<f32x4*>(arena + ao[u]) = po;
-        }
-      }
+      if (o[u]) mt_store_vec4(o[u], v[u]);
   }
 }
 
@@ -552,43 +467,12 @@ using namespace klab;
 
 extern "C" int klab_cast_pack(const void* desc_dev, int ndesc, long total4, void* dst, int dtype, void* stream) {
   if (!desc_dev || !dst || ndesc <= 0) return KLAB_ERR_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == KLAB_BF16)
-    hipLaunchKernelGGL(cast_pack_kernel<bf16_t>, dim3(stream_grid((total4 + 7) / 8)), dim3(256), 0, s, (const CastDesc*)desc_dev, ndesc, total4, (bf16_t*)dst);
-  else
-    hipLaunchKernelGGL(cast_pack_kernel<float>, dim3(stream_grid((total4 + 7) / 8)), dim3(256), 0, s, (const CastDesc*)desc_dev, ndesc, total4, (float*)dst);
+  mt_dispatch(dtype, dst, [&](auto* out) {
+    hipLaunchKernelGGL(cast_pack_kernel, dim3(stream_grid((total4 + 7) / 8)), dim3(256), 0, (hipStream_t)stream, (const CastDesc*)desc_dev, ndesc,
+                       total4, out);
+  });
   KLAB_LAUNCH_CHECK();
   return KLAB_OK;
-}
-
-extern "C" int klab_adam_step_range(const void* desc_dev, int ndesc, long begin4, long end4, const float* grads, float* m, float* v, void* arena,
-                                    int dtype, float lr, float beta1, float beta2, float eps, float weight_decay, float bias_corr1,
-                                    float bias_corr2, void* stream) {
-  if (!desc_dev || ndesc <= 0 || !grads || !m || !v || !arena || bias_corr1 <= 0.f || bias_corr2 <= 0.f || begin4 < 0 || end4 < begin4)
-    return KLAB_ERR_BADARG;
-  if (end4 == begin4) return KLAB_OK;
-  AdamHyper h{lr / bias_corr1, beta1, beta2, eps, weight_decay, 1.f / sqrtf(bias_corr2)};
-  hipStream_t s = (hipStream_t)stream;
-  constexpr int ADAM_GRID = 1024;
-  // non-temporal loads / stores (adam_step_kernel): every byte is touched once per step (415 -> 397 us); an 8-deep unroll measured
-  // 1.5 ms (spills)
-  constexpr int U = 4;
-  long gl = ((end4 - begin4 + U - 1) / U + 255) / 256;
-  const unsigned grid = (unsigned)(gl < 1 ? 1 : (gl > ADAM_GRID ? ADAM_GRID : gl));
-  if (dtype == KLAB_BF16)
-    hipLaunchKernelGGL((adam_step_kernel<bf16_t, U>), dim3(grid), dim3(256), 0, s, (const AdamDesc*)desc_dev, ndesc, begin4, end4, grads, m, v,
-                       (bf16_t*)arena, h);
-  else
-    hipLaunchKernelGGL((adam_step_kernel<float, U>), dim3(grid), dim3(256), 0, s, (const AdamDesc*)desc_dev, ndesc, begin4, end4, grads, m, v,
-                       (float*)arena, h);
-  KLAB_LAUNCH_CHECK();
-  return KLAB_OK;
-}
-extern "C" int klab_adam_step(const void* desc_dev, int ndesc, long total4, const float* grads, float* m, float* v, void* arena, int dtype,
-                              float lr, float beta1, float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
-                              void* stream) {
-  return klab_adam_step_range(desc_dev, ndesc, 0, total4, grads, m, v, arena, dtype, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2,
-                              stream);
 }
 
 extern "C" int klab_embed_fwd(const long long* ids, int shift_right, int L, int start_id, int pad_id, const float* table, int vocab,

@@ -408,12 +408,8 @@ class MyModel(nn.Module):
 
     # ---- the reference surface -----------------------------------------------------------------
     def forward(self, images, source_encoding, target_encoding=None, return_loss=True):
-        if self._pending_opt_stream is not None:  # an in-backward optimizer update nobody joined through step()
-            torch.cuda.current_stream().wait_stream(self._pending_opt_stream)
-            self._pending_opt_stream = None
-        if self._pending_reduce is not None:  # nobody consumed the last backward's gradients through FusedAdam: join now
-            red, self._pending_reduce = self._pending_reduce, None
-            red.finish()
+        self._join_pending_update()  # an in-backward optimizer update nobody joined through step()
+        self._join_pending_reduce()  # nobody consumed the last backward's gradients through FusedAdam: join now
         pixels = images["pixel_values"]
         src = source_encoding["input_ids"]
         if pixels.dim() != 4 or pixels.shape[1] != self.swin_cfg.num_channels:
@@ -775,12 +771,19 @@ class MyModel(nn.Module):
             info = {k: info[k] for k in ("cross_attention", "image_tokens", "image_grid")}
         return (seq, info) if return_logprobs or return_cross_attention else seq
 
-    def _join_pending_update(self):
+    def _join_pending_update(self, device=None):
         """an optimizer update still running on its own stream (optim.FusedAdam(step_in_backward=True)) writes the weights:
-        anything that reads them on the current stream waits for it first"""
+        anything that reads them on the current stream (of `device`, default the current one) waits for it first"""
         if self._pending_opt_stream is not None:
-            torch.cuda.current_stream().wait_stream(self._pending_opt_stream)
+            torch.cuda.current_stream(device).wait_stream(self._pending_opt_stream)
             self._pending_opt_stream = None
+
+    def _join_pending_reduce(self):
+        """klab DDP(overlap_optimizer=True) leaves the last backward's gradient all-reduces to whoever reads the gradients next:
+        wait (stream-wise) for them and do the reducer's bookkeeping"""
+        if self._pending_reduce is not None:
+            red, self._pending_reduce = self._pending_reduce, None
+            red.finish()
 
     def state_dict(self, *a, **k):
         self._join_pending_update()

@@ -30,6 +30,52 @@ from torch.optim import AdamW as _TorchAdamW
 from torch.optim import Optimizer
 
 
+# ---- which model owns these parameters, and do the fused paths apply to it ---------------------------------------------------------
+def _owners(params):
+    """(the klab MyModels that own some of `params`, whether every parameter has one): a model's trainable T5 carries `_klab_owner`"""
+    owners, all_owned = [], True
+    for p in params:
+        ref = getattr(p, "_klab_owner", None)
+        m = ref() if ref is not None else None
+        if m is None:
+            all_owned = False
+        elif all(m is not o for o in owners):
+            owners.append(m)
+    return owners, all_owned
+
+
+def _one_owner(params, allow_unowned=False):
+    """the one klab MyModel that owns `params`, else None.  Parameters nobody owns are tolerated only on request (clipping: the
+    kernels take any gradient; the optimizers and the average need the engine's table to list every tensor)."""
+    owners, all_owned = _owners(params)
+    return owners[0] if len(owners) == 1 and (all_owned or allow_unowned) else None
+
+
+def _join_reductions(params):
+    """gradients may still be in flight (klab DDP overlap_optimizer): join before torch reads them"""
+    for m in _owners(params)[0]:
+        m._join_pending_reduce()
+
+
+def _trainable_t5_of(params, grads_in_flat):
+    """(model, None) when `params` are exactly the trainable T5 of one bound klab MyModel -- with `grads_in_flat`, every `.grad`
+    also a view of the engine's flat gradient buffer --, else (None, reason)."""
+    model = _one_owner(params)
+    if model is None:
+        return None, "parameters not owned by one klab MyModel"
+    if model._flat.get("main") is None or model._engine.shape is None:
+        return None, "engine not bound yet"
+    if not grads_in_flat:
+        model._grad_targets()  # builds the parameter -> flat-buffer views if no backward has run yet
+    views = {id(p): v for p, v, mn in (model._views or []) if mn == "main"}
+    mine = {id(p) for p in params}
+    if mine != {id(p) for p in model.transformer.ordered() if p.requires_grad} or set(views) != mine:
+        return None, "not exactly the trainable T5 parameters"
+    if grads_in_flat and any(p.grad is None or p.grad.data_ptr() != views[id(p)].data_ptr() for p in params):
+        return None, "gradients are not views of the flat buffer"
+    return model, None
+
+
 class FusedAdam(Optimizer):
     _torch_cls = _TorchAdam  # the optimizer every other situation is delegated to
 
@@ -60,10 +106,7 @@ class FusedAdam(Optimizer):
 
     def _in_backward_ok(self, model):
         """may segment 0 be updated underneath this backward? (the groups' side of the question)"""
-        if len(self.param_groups) != 1:
-            return False
-        g = self.param_groups[0]
-        return not (g["amsgrad"] or g["maximize"])
+        return self._groups_ok() is None
 
     def _second_backward_error(self):
         return RuntimeError(f"{type(self).__name__}(step_in_backward=True) supports exactly one backward() per step(); with gradient "
@@ -99,17 +142,11 @@ class FusedAdam(Optimizer):
         self.in_backward_updates += 1
         model._pending_opt_stream = self._opt_stream
 
-    # ---- which model owns these parameters -------------------------------------------------------------------------
+    def _all_params(self):
+        return [p for g in self.param_groups for p in g["params"]]  # (torch refuses a parameter in two groups)
+
     def _find_owner(self):
-        owner = None
-        for g in self.param_groups:
-            for p in g["params"]:
-                ref = getattr(p, "_klab_owner", None)
-                m = ref() if ref is not None else None
-                if m is None or (owner is not None and m is not owner):
-                    return None
-                owner = m
-        return owner
+        return _one_owner(self._all_params())
 
     def _groups_ok(self):
         """None when the groups' settings allow the one-kernel path, else the reason"""
@@ -125,21 +162,15 @@ class FusedAdam(Optimizer):
         why = self._groups_ok()
         if why is not None:
             return None, why
-        model = self._find_owner()
-        if model is None:
-            return None, "parameters not owned by one klab MyModel"
-        if model._flat.get("main") is None or model._engine.shape is None:
-            return None, "engine not bound yet"
-        views = {id(p): v for p, v, mn in (model._views or []) if mn == "main"}
-        params = [p for g in self.param_groups for p in g["params"]]  # (torch refuses a parameter in two groups)
-        mine = {id(p) for p in params}
-        if mine != {id(p) for p in model.transformer.ordered() if p.requires_grad} or set(views) != mine:
-            return None, "not exactly the trainable T5 parameters"
-        for p in params:
-            v = views[id(p)]
-            if p.grad is None or p.grad.data_ptr() != v.data_ptr():
-                return None, "gradients are not views of the flat buffer"
-        return model, None
+        return _trainable_t5_of(self._all_params(), grads_in_flat=True)
+
+    def _moments(self, model):
+        """(param, exp_avg view, exp_avg_sq view) of every trainable T5 tensor: the flat buffers are laid out like `model`'s flat
+        gradient buffer"""
+        for p, v, mn in model._views:
+            if mn == "main" and p.requires_grad:
+                off = v.storage_offset()
+                yield p, self._m[off:off + p.numel()].view(p.shape), self._v[off:off + p.numel()].view(p.shape)
 
     # ---- torch.optim API --------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -153,14 +184,7 @@ class FusedAdam(Optimizer):
             if self._bw_token is not None:
                 raise RuntimeError(f"{type(self).__name__}(step_in_backward=True): segment 0 was updated during backward() but step() cannot "
                                    f"take the fused path any more ({why})")
-            for grp in self.param_groups:  # gradients may still be in flight (klab DDP overlap_optimizer): join before torch reads them
-                for p in grp["params"]:
-                    ref = getattr(p, "_klab_owner", None)
-                    owner = ref() if ref is not None else None
-                    red = getattr(owner, "_pending_reduce", None) if owner is not None else None
-                    if red is not None:
-                        owner._pending_reduce = None
-                        red.finish()
+            _join_reductions(self._all_params())
             if self._fallback is None or self._fb_reason is None:  # (later steps keep the reason of the first)
                 self._fb_reason = why
             self._step_fallback()
@@ -207,14 +231,10 @@ class FusedAdam(Optimizer):
             if self._m is not None:  # carry the fused state over (one-way)
                 model = self._owner() if self._owner is not None else None
                 if model is not None:
-                    for p, v, mn in model._views:
-                        if mn != "main" or not p.requires_grad:
-                            continue
-                        off = v.storage_offset()
+                    for p, m, v in self._moments(model):
                         self._fallback.state[p] = {
                             "step": torch.tensor(float(self._steps), device=p.device if self._fallback.defaults.get("fused") else "cpu"),
-                            "exp_avg": self._m[off:off + p.numel()].view(p.shape).clone(),
-                            "exp_avg_sq": self._v[off:off + p.numel()].view(p.shape).clone()}
+                            "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
         self._fallback.step()
 
     def state_dict(self):
@@ -223,12 +243,8 @@ class FusedAdam(Optimizer):
             return self._fallback.state_dict()
         model = self._owner() if self._owner is not None else None
         if model is not None and self._m is not None:
-            for p, v, mn in model._views:
-                if mn == "main" and p.requires_grad:
-                    off = v.storage_offset()
-                    self.state[p] = {"step": torch.tensor(float(self._steps)),
-                                     "exp_avg": self._m[off:off + p.numel()].view(p.shape).clone(),
-                                     "exp_avg_sq": self._v[off:off + p.numel()].view(p.shape).clone()}
+            for p, m, v in self._moments(model):
+                self.state[p] = {"step": torch.tensor(float(self._steps)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
         return super().state_dict()
 
     def load_state_dict(self, state_dict):
@@ -246,13 +262,12 @@ class FusedAdam(Optimizer):
         if model is not None and model._views:
             flat = model._flat["main"]
             self._m, self._v = torch.zeros_like(flat), torch.zeros_like(flat)
-            for p, v, mn in model._views:
+            for p, m, v in self._moments(model):
                 st = self.state.get(p)
-                if mn != "main" or not st:
+                if not st:
                     continue
-                off = v.storage_offset()
-                self._m[off:off + p.numel()].view(p.shape).copy_(st["exp_avg"])
-                self._v[off:off + p.numel()].view(p.shape).copy_(st["exp_avg_sq"])
+                m.copy_(st["exp_avg"])
+                v.copy_(st["exp_avg_sq"])
                 steps = max(steps, int(float(st["step"])))
             self._owner = weakref.ref(model)
             self._steps = steps
@@ -411,27 +426,14 @@ class FusedAdafactor(Optimizer):
             return min(1e-6 * t if group["warmup_init"] else 1e-2, 1.0 / math.sqrt(t))
         return group["lr"]
 
+    _all_params = FusedAdam._all_params
     _find_owner = FusedAdam._find_owner
 
     def _fast_ok(self):
         """(model, None) when the fused path applies, else (None, reason): FusedAdam's ownership test."""
         if len(self.param_groups) != 1:
             return None, "several param groups"
-        g = self.param_groups[0]
-        model = self._find_owner()
-        if model is None:
-            return None, "parameters not owned by one klab MyModel"
-        if model._flat.get("main") is None or model._engine.shape is None:
-            return None, "engine not bound yet"
-        views = {id(p): v for p, v, mn in (model._views or []) if mn == "main"}
-        mine = {id(p) for p in g["params"]}
-        if mine != {id(p) for p in model.transformer.ordered() if p.requires_grad} or set(views) != mine:
-            return None, "not exactly the trainable T5 parameters"
-        for p in g["params"]:
-            v = views[id(p)]
-            if p.grad is None or p.grad.data_ptr() != v.data_ptr():
-                return None, "gradients are not views of the flat buffer"
-        return model, None
+        return _trainable_t5_of(self.param_groups[0]["params"], grads_in_flat=True)
 
     # ---- flat state <-> per-parameter (HF) state ------------------------------------------------------------------------------
     def _attach(self, model):
@@ -514,14 +516,7 @@ class FusedAdafactor(Optimizer):
                 self._refused = (id(model), model._bound_key)  # asked once per binding, not on every step
                 model, why = None, "a tensor shape the Adafactor kernels do not cover"
         if model is None:
-            for grp in self.param_groups:  # gradients may still be in flight (klab DDP overlap_optimizer): join before torch reads them
-                for p in grp["params"]:
-                    ref = getattr(p, "_klab_owner", None)
-                    owner = ref() if ref is not None else None
-                    red = getattr(owner, "_pending_reduce", None) if owner is not None else None
-                    if red is not None:
-                        owner._pending_reduce = None
-                        red.finish()
+            _join_reductions(self._all_params())
             self._fb_reason = why
             self._export()
             self._flat_live = False
@@ -537,14 +532,8 @@ class FusedAdafactor(Optimizer):
         self._steps += 1
         t = self._steps
         beta2t = 1.0 - math.pow(t, g["decay_rate"])
-        red = getattr(model, "_pending_reduce", None)
-        if red is not None:  # klab DDP(overlap_optimizer=True): RMS(u) needs every gradient, so the whole reduction is joined first
-            model._pending_reduce = None
-            red.finish()
-        side = getattr(model, "_pending_opt_stream", None)
-        if side is not None:  # an in-backward update of another optimizer still writes the weights
-            torch.cuda.current_stream(self._st.device).wait_stream(side)
-            model._pending_opt_stream = None
+        model._join_pending_reduce()  # klab DDP(overlap_optimizer=True): RMS(u) needs every gradient, so the whole reduction is joined first
+        model._join_pending_update(self._st.device)  # an in-backward update of another optimizer still writes the weights
         model._engine.adafactor_step(self._st, self._m, self._scal, self._scratch, beta2t, 1.0 - beta2t, float(g["eps"][0]), float(g["eps"][1]),
                                      float(self._rel_step(g, t)), float(g["clip_threshold"]), float(g["beta1"] or 0.0),
                                      1.0 - float(g["beta1"] or 0.0), float(g["weight_decay"]), g["scale_parameter"])
@@ -710,24 +699,14 @@ class WeightEMA:
     # ---- which form applies ---------------------------------------------------------------------------------------------------
     def _fast_ok(self):
         """(model, None) when the one-launch path applies, else (None, reason)"""
-        owner = None
-        for p in self._params:
-            ref = getattr(p, "_klab_owner", None)
-            m = ref() if ref is not None else None
-            if m is None or (owner is not None and m is not owner):
-                return None, "parameters not owned by one klab MyModel"
-            owner = m
-        model = owner
-        flat = model._flat.get("main")
-        if flat is None or model._engine.shape is None or model._bound_key is None:
+        model, why = _trainable_t5_of(self._params, grads_in_flat=False)
+        if model is None:
+            return None, why
+        if model._bound_key is None:  # (moved with .to() since the last forward)
             return None, "engine not bound yet"
+        flat = model._flat["main"]
         if any(p.device != flat.device or p.dtype != torch.float32 for p in self._params):
             return None, "parameters are not fp32 tensors on the engine's device"
-        model._grad_targets()  # builds the parameter -> flat-buffer views if no backward has run yet
-        views = {id(p) for p, _v, mn in model._views if mn == "main"}
-        mine = {id(p) for p in self._params}
-        if mine != {id(p) for p in model.transformer.ordered() if p.requires_grad} or views != mine:
-            return None, "not exactly the trainable T5 parameters"
         key = (model._bound_key, model._views)
         if self._checked is None or self._checked[0] != key[0] or self._checked[1] is not key[1]:
             try:
@@ -888,19 +867,6 @@ class _ClipState:
         self.res = torch.zeros(self.nt + 2, dtype=torch.float32, device=dev)
 
 
-def _clip_owner(params):
-    """the one klab MyModel that owns some of `params` (its trainable T5 carries `_klab_owner`), else None"""
-    owner = None
-    for p in params:
-        ref = getattr(p, "_klab_owner", None)
-        m = ref() if ref is not None else None
-        if m is not None:
-            if owner is not None and m is not owner:
-                return None
-            owner = m
-    return owner
-
-
 def _clip_native(params, grads, norm_type):
     """(state, owner) when the kernels apply to `grads` (the gradients of `params` that are not None), else (None, why)"""
     if norm_type != 2.0 and norm_type != math.inf:
@@ -921,7 +887,7 @@ def _clip_native(params, grads, norm_type):
         _lib.load()
     except (_lib.KlabError, OSError, AttributeError):
         return None, "the library does not load"
-    owner = _clip_owner(params)
+    owner = _one_owner(params, allow_unowned=True)
     if owner is not None:
         # kept on the model until it is re-bound: `_views` is a new list after every rebind (`_apply`, `_engine_for`)
         owner._grad_targets()
@@ -946,14 +912,8 @@ def _clip_join(owner, dev):
     if opt is not None and opt._bw_token is not None:
         raise RuntimeError("clip_grad_norm_ needs the whole gradient before any update, but FusedAdam(step_in_backward=True) has "
                            "already updated segment 0 underneath this backward(); construct the optimizer with step_in_backward=False")
-    red = owner._pending_reduce
-    if red is not None:  # klab DDP(overlap_optimizer=True): the last all-reduces are not joined yet
-        owner._pending_reduce = None
-        red.finish()
-    side = owner._pending_opt_stream
-    if side is not None:
-        torch.cuda.current_stream(dev).wait_stream(side)
-        owner._pending_opt_stream = None
+    owner._join_pending_reduce()  # klab DDP(overlap_optimizer=True): the last all-reduces are not joined yet
+    owner._join_pending_update(dev)
 
 
 def _clip_norms(st, owner, norm_type):
