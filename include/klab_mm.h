@@ -549,6 +549,36 @@ int klab_ema_swap_range(const void* desc_dev, int ndesc, long begin4, long end4,
  * KLAB_ERR_BADARG when the engine is unbound. */
 int klab_engine_ema_update(klab_engine* e, float* ema, float w, void* stream);
 int klab_engine_ema_swap(klab_engine* e, float* ema, void* stream);
+/* LoRA adapters in merged-weight form (csrc/lora.hip).  desc_dev: a caller-owned device table of ndesc entries of 11 longs, one per
+ * target matrix W [out, in] with lora_A [r, in], lora_B [out, r] and s = alpha / r:
+ *   {W, A, B (f32 device pointers, 16-byte aligned), arena_off, grad_off (elements), out | in << 32, r | bits(s) << 32,
+ *    n4_prefix (exclusive prefix sum of r * in / 4), rb_prefix (exclusive prefix sum of ceil(out / klab_lora_row_block())),
+ *    slab_off (element offset of the tensor's [row blocks, r, in] dA partials in the slab), db_off}
+ * in % 4 == 0, 1 <= r <= 64.  One launch whatever the number of tensors (klab_lora_grads: two); f32 FMAs only, no floating-point
+ * atomics, the same bits on every run.  ndesc == 0: KLAB_OK without a launch; ndesc > 1024: KLAB_ERR_UNSUPPORTED.
+ *   merge   arena[arena_off + i * in + j] = (dtype)(W[i,j] + s * sum_k B[i,k] A[k,j]): W from the f32 master, products and sums in
+ *           f32 (at most r + 1 roundings), one rounding into the arena type (KLAB_BF16: nearest-even; KLAB_F32: the bits).
+ *           to_master != 0: the same f32 value goes into W itself and no arena is touched (arena and dtype are ignored).
+ *           A, B (and W, unless to_master) are only read.
+ *   grads   dB[i,k] = s * sum_j dW[i,j] A[k,j] and dA[k,j] = s * sum_i B[i,k] dW[i,j], dW = grads + grad_off in W's own layout, read
+ *           once.  dA of entry t is stored at out[4 * n4_prefix], dB at out[db_off]; both are overwritten, never added to.  slab:
+ *           caller-owned f32 scratch; only the tensors' [row blocks, r, in] ranges are written. */
+int klab_lora_merge(const void* desc_dev, int ndesc, void* arena, int dtype, int to_master, void* stream);
+int klab_lora_grads(const void* desc_dev, int ndesc, const float* grads, float* out, float* slab, void* stream);
+int klab_lora_row_block(void);
+/* the engine's side of the table: out[2 i] = arena_off and out[2 i + 1] = grad_off of parameter i of the trainable T5 (parameter
+ * table order; -1: none).  Fixed by the configuration: valid before and across klab_engine_bind.  Returns the number of parameters,
+ * or KLAB_ERR_BADARG when max_n is smaller. */
+int klab_engine_lora_layout(klab_engine* e, int max_n, long* out);
+/* Registers (ndesc > 0) or clears (ndesc == 0) the adapter table.  While one is registered, every forward that casts the
+ * trainable weights into the arena runs klab_lora_merge right behind that cast (captured graphs contain it and read the live A,
+ * B and s on replay).  The registration survives klab_engine_bind; captured graphs are dropped.  With no table registered every call
+ * issues exactly the launches it issued before.  KLAB_ERR_UNSUPPORTED: ndesc > 1024, or an fp8 engine. */
+int klab_engine_lora_set(klab_engine* e, const void* desc_dev, int ndesc);
+/* klab_lora_grads on the registered table and the engine's flat gradient buffer, on the caller's stream behind
+ * klab_engine_backward of segments 0 and 1 (each returns with its side-stream weight gradients joined, as
+ * klab_engine_adam_step relies on).  KLAB_ERR_UNSUPPORTED when no table is registered. */
+int klab_engine_lora_grads(klab_engine* e, float* out, float* slab, void* stream);
 /* Adafactor (the rule of transformers.optimization.Adafactor) for ALL parameters of the trainable T5 in four launches, whatever
  * the number of tensors: statistics (row / column sums of g^2 + eps0, sum p^2), their reduction (EMA into R / C, mean R, RMS(p)),
  * sum u^2, apply.  Tensors with >= 2 dims are factored (rows = product of all dims but the last), 1-D tensors keep a full second

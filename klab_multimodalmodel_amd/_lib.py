@@ -133,6 +133,9 @@ SIGNATURES = {
     "klab_adamw_step_range": [vp, i32, vp, C.POINTER(AdamWGroup), i32, i64, i64, vp, vp, vp, vp, i32, vp],
     "klab_ema_update_range": [vp, i32, i64, i64, vp, f32, vp],
     "klab_ema_swap_range": [vp, i32, i64, i64, vp, vp, i32, vp],
+    "klab_lora_merge": [vp, i32, vp, i32, i32, vp],
+    "klab_lora_grads": [vp, i32, vp, vp, vp, vp],
+    "klab_lora_row_block": [],
     "klab_adafactor_plan": [i32, vp, vp, vp, vp, vp],
     "klab_adafactor_step": [vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, f32, f32, f32, i32, vp],
     "klab_grad_norm_chunk": [],

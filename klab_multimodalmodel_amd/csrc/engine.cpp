@@ -169,6 +169,7 @@ struct klab_engine {
   void* cast_desc = nullptr; int n_cast = 0; long cast_total4 = 0;      // trainable GEMM weights (cast every forward)
   void* adam_desc = nullptr; int n_adam = 0; long adam_total4 = 0, adam_split4 = 0;
   std::vector<long> adam_ptrs; int n_adam_seg0 = 0;  // host copy of the table's order (klab_engine_adam_layout)
+  const void* lora_desc = nullptr; int n_lora = 0;  // the caller's LoraDesc table (klab_engine_lora_set); survives a re-bind
   void* af_desc = nullptr; int n_af = 0; long af_totals[4] = {0, 0, 0, 0};  // Adafactor: state elems, tiles, scratch elems, scalar elems
   // RMS-norm weight gradients of a stack: per-workgroup partials of every norm, folded by one reduction per stack
   float* rms_part = nullptr; long rms_part_stride = 0; float** rms_dst_dev[2] = {nullptr, nullptr}; int rms_ncalls[2] = {0, 0};
@@ -1747,6 +1748,8 @@ int forward_part_a(klab_engine* e, hipStream_t stream, float p, bool refresh_fro
   hipLaunchKernelGGL(seed_step_kernel, dim3(1), dim3(1), 0, c.s, e->seed_dev);
   // 1. weights: fp32 masters -> compute-dtype arena (+ fused f32 bias vectors)
   if (e->n_cast && !trainable_current) RC(klab_cast_pack(e->cast_desc, e->n_cast, e->cast_total4, e->warena, c.dt, c.ws()));
+  // LoRA: W + s B A over the copies just written, from the fp32 masters (one launch; inside the captured sequence, reads the live A, B)
+  if (e->n_lora && !trainable_current) RC(klab_lora_merge(e->lora_desc, e->n_lora, e->warena, c.dt, 0, c.ws()));
   if (refresh_frozen || e->cfg.train_swin) {
     if (refresh_frozen && e->n_cast_frozen)
       RC(klab_cast_pack(e->cast_desc_frozen, e->n_cast_frozen, e->cast_total4_frozen, e->warena, c.dt, c.ws()));
@@ -1862,6 +1865,33 @@ extern "C" int klab_engine_adamw_step(klab_engine* e, int segment, float* m, flo
   if (!e->n_adam) return KLAB_ERR_UNSUPPORTED;
   const long b4 = segment == 1 ? e->adam_split4 : 0, e4 = segment == 0 ? e->adam_split4 : e->adam_total4;
   return klab_adamw_step_range(e->adam_desc, e->n_adam, group_of_dev, groups, ngroups, b4, e4, e->G[2], m, v, e->warena, e->cfg.dtype, stream);
+}
+
+extern "C" int klab_engine_lora_layout(klab_engine* e, int max_n, long* out) {
+  if (!e || !out || max_n < (int)e->P[2].size()) return KLAB_ERR_BADARG;
+  for (size_t i = 0; i < e->P[2].size(); ++i) { out[2 * i] = e->P[2][i].warena_off; out[2 * i + 1] = e->P[2][i].grad_off; }
+  return (int)e->P[2].size();
+}
+
+extern "C" int klab_engine_lora_set(klab_engine* e, const void* desc_dev, int ndesc) {
+  if (!e || ndesc < 0 || (ndesc > 0 && !desc_dev)) return KLAB_ERR_BADARG;
+  if (ndesc > klab::MT_MAXD || (ndesc > 0 && e->fp8)) return KLAB_ERR_UNSUPPORTED;
+  if (e->bound) {  // captured forwards hold the old sequence (with or without the merge, and the old table's address)
+    drain_engine(e);
+    for (auto& g : e->gs) {
+      if (g.exec) hipGraphExecDestroy(g.exec);
+      g = klab_engine::GraphSlot();
+    }
+  }
+  e->lora_desc = ndesc ? desc_dev : nullptr;
+  e->n_lora = ndesc;
+  return KLAB_OK;
+}
+
+extern "C" int klab_engine_lora_grads(klab_engine* e, float* out, float* slab, void* stream) {
+  if (!e || !e->bound || !out || !slab || !e->G[2]) return KLAB_ERR_BADARG;
+  if (!e->n_lora) return KLAB_ERR_UNSUPPORTED;
+  return klab_lora_grads(e->lora_desc, e->n_lora, e->G[2], out, slab, stream);
 }
 
 extern "C" int klab_engine_ema_update(klab_engine* e, float* ema, float w, void* stream) {

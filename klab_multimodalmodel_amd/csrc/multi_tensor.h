@@ -1,6 +1,7 @@
 // Multi-tensor kernels: ONE launch over many tensors, whatever their number.  The engine builds a descriptor table per kernel
 // family at bind time (engine.cpp, klab_engine_bind) from the structs below; the kernels (misc.hip: cast_pack, adamw.hip: Adam
-// and AdamW, ema.hip, gemm.hip: the fp8 weight quantiser, adafactor.hip) read exactly these structs.
+// and AdamW, ema.hip, gemm.hip: the fp8 weight quantiser, adafactor.hip) read exactly these structs.  LoraDesc tables (lora.hip) are
+// the caller's: Python fills them from klab_engine_lora_layout.
 //
 // The vec4 walkers (cast_pack, Adam, AdamW, EMA) see the tensors as one space of 16-byte vectors: descriptor i owns the vec4
 // indices [n4_prefix[i], n4_prefix[i + 1]).  A thread handles U vec4s a block width apart (every wave instruction is a contiguous
@@ -24,7 +25,13 @@ struct AdamDesc { float* p; long goff; long aoff; long n4_prefix; };   // goff: 
 // klab_mm.h (klab_engine_adafactor_layout): 10 longs per tensor, read as such by Python
 struct AfDesc { float* p; long goff, aoff, rows, cols, soff, tile0, tile_len, poff, factored; };
 struct QuantDesc { long off; long rows; long K; long row0; };  // {arena element offset, rows, K, first global row}
+// One LoRA target W [out, in] with A [r, in], B [out, r] and s = alpha / r (lora.hip; 11 longs per tensor to Python, {out, in} and
+// {r, s} sharing one each).  aoff: arena copy, goff: dW in the flat gradient buffer.  n4_prefix: prefix sum of r * in / 4 -- dA lies
+// at out[4 * n4_prefix], dB at out[db_off].  rb_prefix: prefix sum of the tensors' row blocks (ceil(out / klab_lora_row_block())),
+// slab_off: the tensor's dA partials [row blocks, r, in] in the caller's slab.  in % 4 == 0, 1 <= r <= 64.
+struct LoraDesc { float* w; const float* a; const float* b; long aoff, goff; int out, in; int r; float s; long n4_prefix, rb_prefix, slab_off, db_off; };
 // n4_prefix is in units of 4 elements everywhere
+static_assert(sizeof(LoraDesc) == 88, "eleven longs per tensor");
 static_assert(sizeof(CastDesc) == 24 && sizeof(AdamDesc) == 32 && sizeof(AfDesc) == 80 && sizeof(QuantDesc) == 32,
               "the tables are arrays of longs to the engine's device buffers and to Python");
 

@@ -193,6 +193,9 @@ class DistributedDataParallel(nn.Module):
         consumer of the gradients is FusedAdam (the reference's loop, ref/train.py:62-69); anything else that reads
         `.grad` first (clipping, logging) must call `ddp.join()` before.  The next forward joins in any case."""
         super().__init__()
+        if getattr(module, "_lora", None) is not None:
+            raise NotImplementedError("klab DDP reduces the flat gradient buffers of the base model; reducing only the LoRA adapters' "
+                                      "gradients is not implemented: merge_and_unload() or detach() the adapters first")
         self.module = module
         self.process_group = process_group
         self.device_ids = device_ids

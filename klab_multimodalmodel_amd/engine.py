@@ -142,6 +142,9 @@ ENGINE_SIGS = {
     "klab_engine_adamw_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(L.AdamWGroup), C.c_int, C.c_void_p], C.c_int),
     "klab_engine_ema_update": ([C.c_void_p, C.c_void_p, C.c_float, C.c_void_p], C.c_int),
     "klab_engine_ema_swap": ([C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "klab_engine_lora_layout": ([C.c_void_p, C.c_int, C.POINTER(C.c_long)], C.c_int),
+    "klab_engine_lora_set": ([C.c_void_p, C.c_void_p, C.c_int], C.c_int),
+    "klab_engine_lora_grads": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_adafactor_state_elems": ([C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)], C.c_int),
     "klab_engine_adafactor_layout": ([C.c_void_p, C.c_int, C.POINTER(C.c_long)], C.c_int),
     "klab_engine_adafactor_step": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_float] * 9 + [C.c_int, C.c_void_p],
@@ -571,6 +574,31 @@ class Engine:
         if ema.dtype != torch.float32 or not ema.is_contiguous() or ema.numel() < self.grad_elems["main"]:
             raise ValueError("the EMA buffer has to be a contiguous fp32 tensor of the flat gradient buffer's size")
         L.check(self._lib.klab_engine_ema_swap(self._h, ema.data_ptr(), L.stream_ptr()), "klab_engine_ema_swap")
+
+    def lora_layout(self):
+        """{parameter name of the trainable T5: (arena element offset, flat-gradient element offset)}, -1 = none; fixed by the
+        configuration (valid before and across bind)"""
+        n = len(self.params["main"])
+        buf = (C.c_long * (2 * n))()
+        rc = self._lib.klab_engine_lora_layout(self._h, n, buf)
+        if rc != n:
+            L.check(rc if rc < 0 else L.ERR_BADARG, "klab_engine_lora_layout")
+        return {spec.name: (int(buf[2 * i]), int(buf[2 * i + 1])) for i, spec in enumerate(self.params["main"])}
+
+    def lora_set(self, desc):
+        """registers the adapter table (ops.lora_table's int64 device tensor; the engine keeps it across re-binds and merges
+        W + s B A into the arena behind every cast of the trainable weights), None clears it"""
+        if desc is None:
+            L.check(self._lib.klab_engine_lora_set(self._h, None, 0), "klab_engine_lora_set")
+        else:
+            assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 11 and desc.is_contiguous() and desc.is_cuda
+            L.check(self._lib.klab_engine_lora_set(self._h, desc.data_ptr(), desc.shape[0]), "klab_engine_lora_set")
+        self._lora_desc = desc  # (the engine reads the caller's tensor)
+
+    def lora_grads(self, out, slab):
+        """dA and dB of every registered adapter from the flat gradient buffer, in two launches on the current stream (after
+        backward segments 0 and 1); out, slab: the fp32 device buffers ops.lora_table sized"""
+        L.check(self._lib.klab_engine_lora_grads(self._h, out.data_ptr(), slab.data_ptr(), L.stream_ptr()), "klab_engine_lora_grads")
 
     def adafactor_sizes(self):
         """(state, scalar, scratch) element counts of the f32 buffers klab_engine_adafactor_step works on"""

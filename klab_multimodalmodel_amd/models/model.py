@@ -123,6 +123,10 @@ class _LossFn(torch.autograd.Function):
         ctx.model = model
         ctx.eng = eng
         ctx.nparams = len(params)
+        # LoRA (lora.attach): the adapter parameters travel behind the base parameters; the arena now holds W + s B A of these versions
+        ctx.nlora = len(model._lora.parameters()) if model._lora is not None else 0
+        if model._lora is not None:
+            model._lora._note_forward()
         model._fwd_token += 1
         ctx.token = model._fwd_token
         return out[0] if direct_loss else eng.loss_view[0].clone()
@@ -137,6 +141,8 @@ class _LossFn(torch.autograd.Function):
             # a second backward() before step() (gradient accumulation): segment 0 was already updated underneath the first one.
             # The gradients are no longer "fresh" now, so _segment_ready below would never be asked: say it here.
             raise opt._second_backward_error()
+        if ctx.nlora and model._lora is None:
+            raise RuntimeError("klab MyModel: the LoRA adapters of this forward() were removed before its backward()")
         g = gout.detach().to(torch.float32).contiguous().view(1)
         direct = model._direct_grads
         targets = model._grad_targets()
@@ -194,12 +200,13 @@ class _LossFn(torch.autograd.Function):
                                 # the running sums were added on the current stream AFTER the engine's per-layer events:
                                 # the reducer must order itself behind the stream, not behind those events
                                 model._segment_hook(s2, False)
-            return (None,) * (5 + ctx.nparams)
+            # dA and dB are projected out of the full dW the segments left in the flat buffer, on this stream behind them
+            return (None,) * (5 + ctx.nparams - ctx.nlora) + (model._lora._grads(eng) if ctx.nlora else ())
         grads = []
         views = {id(p): v for p, v in targets}
         for p in model._trainable():
             grads.append(views[id(p)])
-        return (None, None, None, None, None) + tuple(grads)
+        return (None, None, None, None, None) + tuple(grads) + (model._lora._grads(eng) if ctx.nlora else ())
 
 
 class MyModel(nn.Module):
@@ -245,6 +252,7 @@ class MyModel(nn.Module):
         self._optimizer_in_backward = None  # weakref to an optim.FusedAdam(step_in_backward=True) after its first fused step
         self._pending_opt_stream = None  # stream of an in-backward optimizer update that step() has not joined yet
         self._reducer = None  # klab DDP's SegmentReducer
+        self._lora = None  # lora.LoraAdapters while adapters are attached (lora.attach)
         self._pending_reduce = None  # klab DDP(overlap_optimizer=True): reducer whose last all-reduces are not joined yet
         self.use_graph = os.environ.get("KLAB_GRAPH", "0") == "1"  # hipGraph replay of the engine's launch sequences
         self._seed_base = torch.initial_seed() & 0xFFFFFFFF
@@ -324,15 +332,23 @@ class MyModel(nn.Module):
             self._frozen_fp = None
             self._train_fp = None
             self._token_losses_valid = False
+            if self._lora is not None:  # (the engine keeps the registration across re-binds; a moved model gets a new table)
+                self._lora._install()
         return self._engine
 
     def _note_optimizer_step(self):
         """called by optim.FusedAdam: the step kernel rewrote the masters AND their compute-dtype copies."""
         self._train_fp = sum(p._version for p in self.transformer.parameters())
+        if self._lora is not None:  # the copies are those of the bare masters now: the next forward casts and merges again
+            self._lora._fp = None
 
     def _trainable_current(self):
         """True when nothing wrote the trainable T5 since the last fused optimizer step (tensor version counters) and the
-        engine was not re-bound: the forward may then skip its fp32 -> bf16 weight cast."""
+        engine was not re-bound: the forward may then skip its fp32 -> bf16 weight cast.  With LoRA adapters attached: when nothing
+        wrote a base or an adapter parameter since the last loss forward of this binding (the arena holds W + s B A of exactly
+        these versions); otherwise the engine casts and then merges."""
+        if self._lora is not None:
+            return self._lora._current()
         if self._train_fp is None:
             return False
         if sum(p._version for p in self.transformer.parameters()) != self._train_fp:
@@ -439,8 +455,10 @@ class MyModel(nn.Module):
                 weights = weights.detach().to(torch.float32).contiguous()
             self._loss_weights_next = weights
             params = self._trainable()
+            if self._lora is not None:  # behind the base parameters: the loss has a grad_fn although the base T5 is frozen
+                params = params + [p for p in self._lora.parameters()]
             # (grad mode is off inside Function.forward, so decide here whether d logits must be produced)
-            want_grad = torch.is_grad_enabled() and len(params) > 0
+            want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
             return _LossFn.apply(self, want_grad, pixels, src, tgt, *params)
         return self.generate(pixels, src)
 

@@ -633,6 +633,81 @@ def ema_swap(desc, ema, arena, *, begin4=0, end4=None, total4=None):
                                     L.dtype_code(arena.dtype), L.stream_ptr()), "klab_ema_swap_range")
 
 
+def lora_row_block():
+    """rows of a target matrix one workgroup of the LoRA kernels owns (a compile-time constant of the library; no GPU needed)"""
+    return int(L.load().klab_lora_row_block())
+
+
+def lora_plan(shapes, row_block=None):
+    """host side of the LoRA table for targets of shapes [(out, in, r)]: per tensor (n4_prefix, rb_prefix, slab_off, db_off) and the
+    element counts (out_elems, slab_elems) of the two fp32 buffers klab_lora_grads writes -- dA of tensor t at out[4 * n4_prefix], dB
+    at out[db_off], its partials [row blocks, r, in] at slab[slab_off]"""
+    rb = lora_row_block() if row_block is None else int(row_block)
+    n4 = blocks = slab = 0
+    rows = []
+    for out, inn, r in shapes:
+        out, inn, r = int(out), int(inn), int(r)
+        if out < 1 or inn < 4 or inn % 4 or not 1 <= r <= 64:
+            raise ValueError(f"klab: LoRA target [{out}, {inn}] with r = {r}: needs in % 4 == 0 and 1 <= r <= 64")
+        nb = (out + rb - 1) // rb
+        rows.append([n4, blocks, slab, 0])
+        n4 += r * inn // 4
+        blocks += nb
+        slab += nb * r * inn
+    db = 4 * n4
+    for row, (out, _inn, r) in zip(rows, shapes):
+        row[3] = db
+        db += (int(out) * int(r) + 3) & ~3
+    return [tuple(r) for r in rows], db, slab
+
+
+def lora_table(entries):
+    """the device table of lora_merge / lora_grads: entries = [(W [out, in], A [r, in], B [out, r], arena_off, grad_off, s)], fp32
+    contiguous tensors of one device; returns (desc int64 [n, 11], plan rows, out_elems, slab_elems) as lora_plan gives them"""
+    import struct
+    shapes = []
+    for W, A, B, aoff, goff, _s in entries:
+        for t in (W, A, B):
+            if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.data_ptr() % 16:
+                raise ValueError("klab: LoRA tensors have to be contiguous 16-byte aligned fp32 device tensors")
+        if W.dim() != 2 or tuple(A.shape) != (A.shape[0], W.shape[1]) or tuple(B.shape) != (W.shape[0], A.shape[0]):
+            raise ValueError(f"klab: LoRA shapes W {tuple(W.shape)}, A {tuple(A.shape)}, B {tuple(B.shape)} do not fit")
+        if int(aoff) % 4 or int(goff) % 4:
+            raise ValueError("klab: arena and gradient offsets have to be multiples of 4 elements")
+        shapes.append((W.shape[0], W.shape[1], A.shape[0]))
+    plan, out_elems, slab_elems = lora_plan(shapes)
+    rows = []
+    for (W, A, B, aoff, goff, s), (out, inn, r), (n4, rbp, so, db) in zip(entries, shapes, plan):
+        sbits = struct.unpack("<I", struct.pack("<f", float(s)))[0]
+        rs = (sbits << 32) | r
+        rows.append([W.data_ptr(), A.data_ptr(), B.data_ptr(), int(aoff), int(goff), (inn << 32) | out, rs - (1 << 64) if rs >= 1 << 63 else rs,
+                     n4, rbp, so, db])
+    dev = entries[0][0].device if entries else "cuda"
+    host = torch.tensor(rows, dtype=torch.int64).reshape(-1, 11).pin_memory()  # pinned: the upload does not synchronise
+    return host.to(dev, non_blocking=True), plan, out_elems, slab_elems
+
+
+def lora_merge(desc, arena=None, to_master=False):
+    """arena[arena_off + i * in + j] = cast(W[i,j] + s sum_k B[i,k] A[k,j]) for every tensor of the table in ONE launch
+    (klab_lora_merge; arena bf16 or fp32); to_master=True: the same fp32 value into W itself, no arena"""
+    lib = L.load()
+    assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 11 and desc.is_contiguous()
+    if not to_master and (arena is None or arena.dtype not in (torch.float32, torch.bfloat16)):
+        raise ValueError("klab: lora_merge needs a bf16 or fp32 arena (or to_master=True)")
+    L.check(lib.klab_lora_merge(desc.data_ptr(), desc.shape[0], None if to_master else arena.data_ptr(),
+                                0 if to_master else L.dtype_code(arena.dtype), int(bool(to_master)), L.stream_ptr()), "klab_lora_merge")
+
+
+def lora_grads(desc, grads, out, slab):
+    """dB = s dW A^T and dA = s B^T dW of every tensor of the table from the flat gradient buffer `grads`, in two launches
+    (klab_lora_grads); out, slab: fp32 device buffers of at least lora_plan's out_elems / slab_elems.  Both outputs are overwritten."""
+    lib = L.load()
+    assert desc.dtype == torch.int64 and desc.dim() == 2 and desc.shape[1] == 11 and desc.is_contiguous()
+    assert grads.dtype == out.dtype == slab.dtype == torch.float32 and out.is_contiguous() and slab.is_contiguous()
+    L.check(lib.klab_lora_grads(desc.data_ptr(), desc.shape[0], grads.data_ptr(), out.data_ptr(), slab.data_ptr(), L.stream_ptr()),
+            "klab_lora_grads")
+
+
 def grad_norm_chunk():
     """elements per fp64 partial of grad_norm (a compile-time constant of the library; no GPU needed)"""
     return int(L.load().klab_grad_norm_chunk())
