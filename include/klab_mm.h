@@ -353,6 +353,18 @@ int klab_ce_fwd(void* logits, long ld, int dtype, const long long* labels, int r
 int klab_ce_wsum(const long long* labels, const float* weights, int rows, float* inv_w, void* stream);
 int klab_ce_fwd_opts(void* logits, long ld, int dtype, const long long* labels, const float* weights, int rows, int V, float eps, float z,
                      float* inv_w, float* loss_row, float* loss, int write_grad, void* stream);
+/* the same mixed with knowledge distillation (csrc/ce_distill.hip): teacher logits t [rows, V] (bf16 or f32 whatever the student's
+ * dtype, row stride ldt >= V, FINITE -- a precondition, not checked on the device), temperature T > 0, alpha in [0, 1]:
+ *   kl_i = KL(softmax(t / T) || softmax(x / T)),  l_i = (1 - alpha) ce_i + alpha T^2 kl_i with ce_i the l_i above (0 where the label is -100),
+ *   d l / d x_j = (w_i / W) [(1 - alpha) (the bracket above) + alpha T (softmax(x / T)_j - softmax(t / T)_j)].
+ * loss_row receives the unweighted l_i, kl_row the unweighted kl_i (without alpha T^2; 0 where the label is -100).  The teacher is only
+ * read; a teacher range that overlaps the logits range, alpha outside [0, 1] or T not finite and > 0 return KLAB_ERR_BADARG, a width or
+ * stride off either dtype's 16-byte vector KLAB_ERR_UNSUPPORTED, before anything is launched.  inv_w, write_grad and the launch count are
+ * klab_ce_fwd_opts'; no float atomics, the same bits on every run.  With alpha == 0 logits, inv_w, loss_row and loss equal
+ * klab_ce_fwd_opts' bit for bit. */
+int klab_ce_fwd_distill(void* logits, long ld, int dtype, const void* teacher, long ldt, int t_dtype, const long long* labels,
+                        const float* weights, int rows, int V, float eps, float z, float alpha, float temperature, float* inv_w,
+                        float* loss_row, float* kl_row, float* loss, int write_grad, void* stream);
 int klab_im2col_patch(const float* pixels, void* out, int dtype, int B, int Cin, int Himg, int P, void* stream);
 /* same, rows of `ldo` >= Cin*P*P elements with the tail columns zero-filled (lets the patch-embedding GEMM run with K
  * padded to a multiple of 32); P == 4 takes a one-thread-per-patch vector path */
@@ -885,6 +897,15 @@ int klab_engine_set_loss_out(klab_engine* e, float* out);
  * eps == z == 0 and no weights the forward issues klab_ce_fwd as before (graph slots included); otherwise klab_ce_wsum and
  * klab_ce_fwd_opts, eagerly -- never from a captured graph, which would replay the options of the capture. */
 int klab_engine_set_loss_options(klab_engine* e, float eps, float z, const float* weights);
+/* Knowledge distillation in the training loss (klab_ce_fwd_distill).  alpha (in [0, 1]) and temperature (finite, > 0) persist until
+ * changed.  `teacher` (device, B*n*Lt x V logits of dtype t_dtype = KLAB_BF16 or KLAB_F32, row stride V, finite; or NULL) is one-shot
+ * and NOT staged: the NEXT klab_engine_forward reads it in place in its loss launch and then forgets the pointer, so it has to stay
+ * alive and unchanged until that launch has run; it must not overlap the engine's own logits (KLAB_ERR_BADARG).  A caller whose
+ * forward failed early passes NULL to disarm it.  With alpha > 0 and a teacher armed the forward issues klab_ce_wsum and
+ * klab_ce_fwd_distill, eagerly -- never from a captured graph, which would replay the teacher's address and the options of the
+ * capture; with alpha == 0 or no teacher armed it issues exactly the launches described above.  The per-token kl is the buffer
+ * "kl_row" of klab_engine_buffer. */
+int klab_engine_set_distill(klab_engine* e, float alpha, float temperature, const void* teacher, int t_dtype);
 const int* klab_engine_err_ptr(const klab_engine* e);
 /* device words {seed of the current step, base seed, forwards since seeding} (for stream-ordered snapshots; see klab_engine_get_rng) */
 const uint32_t* klab_engine_rng_ptr(const klab_engine* e);

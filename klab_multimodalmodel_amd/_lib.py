@@ -200,6 +200,8 @@ SIGNATURES = {
     "klab_ce_wsum": [vp, vp, i32, vp, vp],
     "klab_ce_fwd_opts": [vp, i64, i32, vp, vp, i32, i32, f32, f32, vp, vp, vp, i32, vp],
     "klab_engine_set_loss_options": [vp, f32, f32, vp],
+    "klab_ce_fwd_distill": [vp, i64, i32, vp, i64, i32, vp, vp, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, i32, vp],
+    "klab_engine_set_distill": [vp, f32, f32, vp, i32],
     "klab_engine_set_captions": [vp, i32],
     "klab_im2col_patch": [vp, vp, i32, i32, i32, i32, i32, vp],
     "klab_im2col_patch_ld": [vp, vp, i32, i32, i32, i32, i32, i32, vp],

@@ -223,6 +223,11 @@ struct klab_engine {
   float loss_eps = 0.f, loss_z = 0.f;
   const float* loss_w_armed = nullptr;
   float *loss_w_buf = nullptr, *inv_w = nullptr;
+  // klab_engine_set_distill: alpha and T persist, the teacher's logits are one-shot and read in place (never staged: Bd*Lt x V)
+  float kd_alpha = 0.f, kd_T = 1.f;
+  const void* kd_teacher = nullptr;
+  int kd_tdtype = KLAB_BF16;
+  float* kl_row = nullptr;
   bool bias_ready[3] = {false, false, false};  // [stack id]: the stack's position bias was computed ahead of it, on the side stream
   bool dec_embed_ready = false;   // ... and the decoder's input embedding
   bool inv_n_ready = false;       // ... and 1 / n_valid of the labels
@@ -588,6 +593,7 @@ size_t plan_workspace(klab_engine* e, void* base, int B, int Ls, int Lt) {
   e->dkv_all = b.take((size_t)Me * nld * 2 * inner * es);
   e->logits = b.take((size_t)Md * c.main.vocab * es);
   e->loss_row = (float*)b.take((size_t)Md * 4);
+  e->kl_row = (float*)b.take((size_t)Md * 4);
   e->dh_a = (float*)b.take((size_t)Mx * d * 4);
   e->dh_b = (float*)b.take((size_t)Mx * d * 4);
   e->dxn = (float*)b.take((size_t)Mx * d * 4);
@@ -1562,6 +1568,7 @@ extern "C" int klab_engine_bind(klab_engine* e, int B, int Ls, int Lt, void* wor
   e->wplan.valid = false;  // rebuilt at the next backward, for the new binding's buffers
   e->loss_out = nullptr;
   e->loss_w_armed = nullptr;
+  e->kd_teacher = nullptr;
   e->forced_armed = ForcedTable();
   e->attn_armed = AttnMaps();
   e->gen.maps = AttnMaps();  // (sized for the old binding's rows)
@@ -1963,6 +1970,8 @@ extern "C" int klab_engine_forward(klab_engine* e, const float* pixels, const lo
     RC((int)hipMemcpyAsync(e->loss_w_buf, src_w, (size_t)e->Bd * e->Lt * 4, hipMemcpyDeviceToDevice, c.s));
     loss_w = e->loss_w_buf;
   }
+  const void* kd_teacher = e->kd_teacher;  // this forward's teacher logits (one-shot, read in place by the loss launch)
+  e->kd_teacher = nullptr;
   if (!e->seed_set || seed != e->seed_base) {  // (re)seed the device-side counter RNG; each forward then advances it itself
     hipLaunchKernelGGL(seed_set_kernel, dim3(1), dim3(1), 0, c.s, e->seed_dev, seed);
     e->seed_base = seed; e->seed_set = true;
@@ -1999,7 +2008,13 @@ extern "C" int klab_engine_forward(klab_engine* e, const float* pixels, const lo
     e->inv_n_ready = false;
     float* loss_dst = e->loss_out && !e->use_graph ? e->loss_out : e->loss;  // (replayed graphs write the fixed address)
     e->loss_out = nullptr;
-    if (!loss_w && e->loss_eps == 0.f && e->loss_z == 0.f) {
+    if (kd_teacher && e->kd_alpha > 0.f) {
+      // distillation: eager like the options path below, never a graph slot -- the teacher's address and the options change
+      // between steps and a replay would bake them in
+      RC(klab_ce_wsum(e->tgt_buf, loss_w, Md, e->inv_w, c.ws()));
+      RC(klab_ce_fwd_distill(e->logits, V, c.dt, kd_teacher, V, e->kd_tdtype, e->tgt_buf, loss_w, Md, V, e->loss_eps, e->loss_z, e->kd_alpha,
+                             e->kd_T, e->inv_w, e->loss_row, e->kl_row, loss_dst, (want_grad ? 1 : 0) | 2, c.ws()));
+    } else if (!loss_w && e->loss_eps == 0.f && e->loss_z == 0.f) {
       RC(run_graphed(e, want_grad ? 3 : 2, c.s, [&]() {
         return klab_ce_fwd(e->logits, V, c.dt, e->tgt_buf, Md, V, e->inv_n, e->loss_row, loss_dst, (want_grad ? 1 : 0) | (counted ? 2 : 0), c.ws());
       }));
@@ -2064,6 +2079,22 @@ extern "C" int klab_engine_set_loss_options(klab_engine* e, float eps, float z, 
   e->loss_w_armed = weights;
   return KLAB_OK;
 }
+// Distillation in the training loss (klab_ce_fwd_distill): alpha and temperature persist until changed; `teacher` (device, B*n*Lt x V
+// logits, or NULL) is one-shot and read in place by the next forward's loss launch.  A caller whose forward fails early passes NULL
+// again to disarm it.
+extern "C" int klab_engine_set_distill(klab_engine* e, float alpha, float temperature, const void* teacher, int t_dtype) {
+  if (!e || !(alpha >= 0.f && alpha <= 1.f) || !(temperature > 0.f) || !isfinite(temperature)) return KLAB_ERR_BADARG;
+  if (teacher) {
+    if (!e->bound || (t_dtype != KLAB_BF16 && t_dtype != KLAB_F32)) return KLAB_ERR_BADARG;
+    const size_t Md = (size_t)e->Bd * e->Lt, V = (size_t)e->cfg.main.vocab;
+    const uintptr_t x0 = (uintptr_t)e->logits, x1 = x0 + Md * V * e->es;
+    const uintptr_t t0 = (uintptr_t)teacher, t1 = t0 + Md * V * (t_dtype == KLAB_BF16 ? 2 : 4);
+    if (x0 < t1 && t0 < x1) return KLAB_ERR_BADARG;
+  }
+  e->kd_alpha = alpha; e->kd_T = temperature;
+  e->kd_teacher = teacher; e->kd_tdtype = t_dtype;
+  return KLAB_OK;
+}
 extern "C" const int* klab_engine_err_ptr(const klab_engine* e) { return e ? e->err_dev : nullptr; }
 extern "C" const uint32_t* klab_engine_rng_ptr(const klab_engine* e) { return e ? e->seed_dev : nullptr; }
 
@@ -2076,6 +2107,7 @@ extern "C" const void* klab_engine_buffer(const klab_engine* e, const char* name
   if (!strcmp(name, "decoder_out")) { set((long)e->Bd * e->Lt, d, e->cfg.dtype); return e->dec.out_t; }
   if (!strcmp(name, "logits")) { set((long)e->Bd * e->Lt, e->cfg.main.vocab, e->cfg.dtype); return e->logits; }
   if (!strcmp(name, "loss_row")) { set((long)e->Bd * e->Lt, 1, KLAB_F32); return e->loss_row; }
+  if (!strcmp(name, "kl_row")) { set((long)e->Bd * e->Lt, 1, KLAB_F32); return e->kl_row; }
   return nullptr;
 }
 

@@ -402,6 +402,13 @@ class Engine:
         L.check(self._lib.klab_engine_set_loss_options(self._h, float(eps), float(z), weights.data_ptr() if weights is not None else None),
                 "klab_engine_set_loss_options")
 
+    def set_distill(self, alpha=0.0, temperature=1.0, teacher=None):
+        """distillation weight and temperature of the forwards from now on; `teacher` (contiguous bf16 or fp32 device tensor of
+        B*n*Lt x V logits, or None) for the next forward only, which reads it in place (None disarms a teacher armed earlier)"""
+        code = L.dtype_code(teacher.dtype) if teacher is not None else L.dtype_code(torch.bfloat16)
+        L.check(self._lib.klab_engine_set_distill(self._h, float(alpha), float(temperature), teacher.data_ptr() if teacher is not None else None,
+                                                  code), "klab_engine_set_distill")
+
     # ---- decoding sessions (HF `_beam_search`, `_sample`, greedy decoding); the workspace is the caller's, the binding's is
     # untouched ----------------------------------------------------------------------------------------------------------------
     GEN_MODES = {"pick": L.GEN_PICK, "sample": L.GEN_SAMPLE, "beam": L.GEN_BEAM, "force": L.GEN_FORCE}

@@ -104,21 +104,30 @@ class _LossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, want_grad, pixels, src, tgt, *params):
         eng = model._engine_for(pixels, src, tgt)
+        weights, model._loss_weights_next = model._loss_weights_next, None
+        teacher, model._teacher_next = model._teacher_next, None
+        eps, z = model._loss_options["label_smoothing"], model._loss_options["z_loss"]
+        alpha, temp = model._distill_options["distill_alpha"], model._distill_options["distill_temperature"]
+        if teacher is not None:  # (the binding exists only now; nothing is armed yet)
+            model._check_teacher_alias(eng, teacher)
         # a fresh tensor per step, written by the cross-entropy kernel itself (no copy launch behind it)
         out = torch.empty(1, device=pixels.device, dtype=torch.float32)
         direct_loss = eng.set_loss_out(out)
-        weights, model._loss_weights_next = model._loss_weights_next, None
-        eps, z = model.loss_options["label_smoothing"], model.loss_options["z_loss"]
+        model._logits_valid = False
         # the engine keeps a device-side counter RNG: the base only (re)seeds it, every forward advances it
         try:
             eng.set_loss_options(eps, z, weights)
+            eng.set_distill(alpha, temp, teacher)
             eng.forward(pixels, src, tgt, training=int(model.transformer.training) | (2 if model._frozen_unchanged() else 0) | (4 if model._trainable_current() else 0),
                         seed=model._seed_base, want_grad=want_grad)
         except Exception:
             eng.set_loss_out(None)  # a forward that failed before its cross-entropy must not leave the one-shot pointer armed
             eng.set_loss_options(eps, z, None)  # ... nor the one-shot loss weights
+            eng.set_distill(alpha, temp, None)  # ... nor the one-shot teacher
             raise
         model._token_losses_valid = True
+        model._token_kl_valid = teacher is not None
+        model._logits_valid = not want_grad  # (with gradients the loss kernel has replaced the logits by d loss / d logits)
         model._token_losses_shape = tuple(tgt.shape)
         ctx.model = model
         ctx.eng = eng
@@ -261,8 +270,12 @@ class MyModel(nn.Module):
         self._train_fp = None  # version fingerprint of the trainable T5 right after a klab FusedAdam step (bf16 copies current)
         self._fwd_token = 0
         self._loss_options = {"label_smoothing": 0.0, "z_loss": 0.0}
+        self._distill_options = {"distill_alpha": 0.0, "distill_temperature": 1.0}
         self._loss_weights_next = None  # this call's target_encoding["loss_weights"], taken by _LossFn.forward
+        self._teacher_next = None  # this call's target_encoding["teacher_logits"], taken by _LossFn.forward
         self._token_losses_valid = False  # the engine's per-token losses are those of a loss forward of this binding
+        self._token_kl_valid = False  # ... and its per-token kl those of a distillation forward
+        self._logits_valid = False  # the engine's logits buffer holds the logits of the last loss forward (it wrote no gradient)
         self._token_losses_shape = None  # ... and the shape of that forward's labels: [B, Lt] or [B, n, Lt]
         import weakref
         for p in self.transformer.parameters():  # lets klab_multimodalmodel_amd.optim.FusedAdam find its engine
@@ -331,7 +344,7 @@ class MyModel(nn.Module):
             self._bound_key = key
             self._frozen_fp = None
             self._train_fp = None
-            self._token_losses_valid = False
+            self._token_losses_valid = self._token_kl_valid = self._logits_valid = False
             if self._lora is not None:  # (the engine keeps the registration across re-binds; a moved model gets a new table)
                 self._lora._install()
         return self._engine
@@ -381,7 +394,7 @@ class MyModel(nn.Module):
         return [(p, v) for p, v, _m in self._views if p.requires_grad]
 
     # ---- loss options -------------------------------------------------------------------------
-    def set_loss_options(self, label_smoothing=0.0, z_loss=0.0):
+    def set_loss_options(self, label_smoothing=0.0, z_loss=0.0, distill_alpha=0.0, distill_temperature=1.0):
         """Options of the training loss, for every forward from now on (train and eval mode, with or without gradients; generate and
         score are not touched).  For each scored token with logits x, label y and lse = logsumexp(x):
             l = lse - (1 - label_smoothing) x_y - (label_smoothing / V) sum_j x_j + z_loss lse^2
@@ -392,26 +405,71 @@ class MyModel(nn.Module):
         both options 0 and no weights the forward runs exactly the launches of the plain loss.
         These are hyper-parameters of the training script, not model state: save, state_dict and checkpoint.py do not store them.
         Under klab DDP every rank normalises by its own sum of weights, exactly as it normalises by its own count of scored tokens
-        without them."""
+        without them.
+        Knowledge distillation: with distill_alpha in (0, 1] every loss forward needs target_encoding["teacher_logits"], a bf16 or
+        fp32 tensor [B, Lt, V] ([B, n, Lt, V] with labels [B, n, Lt]) of FINITE teacher logits, contiguous and on the model's device,
+        read in place by that forward's loss kernel and never copied (keep it alive and unchanged until the forward has run).  With
+        T = distill_temperature (finite, > 0), p = softmax(t / T) and q = softmax(x / T) the token's loss becomes
+            (1 - distill_alpha) l + distill_alpha T^2 KL(p || q)
+        (Hinton's form: the T^2 keeps the soft term's gradient scale independent of T); tokens without a label add nothing to either
+        term, weights and the normalisation are as above.  With distill_alpha == 0 a teacher is refused and every forward issues the
+        launches it issues without this option.  distill.teacher_logits computes the tensor from a second MyModel."""
         eps, z = float(label_smoothing), float(z_loss)
+        alpha, temp = float(distill_alpha), float(distill_temperature)
         if not (math.isfinite(eps) and 0.0 <= eps < 1.0):
             raise ValueError(f"`label_smoothing` has to be a finite float in [0, 1), but is {label_smoothing}")
         if not (math.isfinite(z) and z >= 0.0):
             raise ValueError(f"`z_loss` has to be a finite float >= 0, but is {z_loss}")
+        if not (math.isfinite(alpha) and 0.0 <= alpha <= 1.0):
+            raise ValueError(f"`distill_alpha` has to be a finite float in [0, 1], but is {distill_alpha}")
+        if not (math.isfinite(temp) and temp > 0.0):
+            raise ValueError(f"`distill_temperature` has to be a finite float > 0, but is {distill_temperature}")
         self._loss_options = {"label_smoothing": eps, "z_loss": z}
+        self._distill_options = {"distill_alpha": alpha, "distill_temperature": temp}
 
     @property
     def loss_options(self):
-        """dict(label_smoothing, z_loss) as set_loss_options left them"""
-        return dict(self._loss_options)
+        """dict(label_smoothing, z_loss) as set_loss_options left them, and distill_alpha and distill_temperature beside them once
+        either differs from its default (0 and 1): a model that never asked for distillation reads back the two options it always had"""
+        out = dict(self._loss_options)
+        if self._distill_options != {"distill_alpha": 0.0, "distill_temperature": 1.0}:
+            out.update(self._distill_options)
+        return out
 
     def token_losses(self):
         """fp32 [B, Lt] device tensor ([B, n, Lt] after a forward on [B, n, Lt] labels): a copy of the per-token losses l of the last
-        loss forward (unweighted, with the loss options of that forward; 0 where the label is -100).  sum w l / sum w over the scored
-        tokens is the loss that forward returned."""
+        loss forward (unweighted, with the loss options of that forward -- under distillation the combined
+        (1 - alpha) l + alpha T^2 kl; 0 where the label is -100).  sum w l / sum w over the scored tokens is the loss that forward
+        returned."""
         if not self._token_losses_valid:
             raise RuntimeError("token_losses(): no loss forward has run on this binding yet (generate and score keep none)")
         return self._engine.buffer("loss_row").view(self._token_losses_shape).clone()
+
+    def token_kl(self):
+        """fp32 device tensor shaped like token_losses(): a copy of the per-token KL(softmax(t / T) || softmax(x / T)) of the last loss
+        forward (unweighted, without the factor alpha T^2; 0 where the label is -100).  That forward must have had a teacher."""
+        if not self._token_kl_valid:
+            raise RuntimeError("token_kl(): the last loss forward on this binding had no target_encoding['teacher_logits'] "
+                               "(or none has run yet; generate and score keep none)")
+        return self._engine.buffer("kl_row").view(self._token_losses_shape).clone()
+
+    def logits(self):
+        """A VIEW [B, Lt, V] ([B, n, Lt, V] after a forward on [B, n, Lt] labels) of the engine's logits in the model's compute dtype,
+        after a loss forward that wrote no gradient.  Valid until this model's next forward, generate or score: clone it to keep it."""
+        if not self._logits_valid:
+            raise RuntimeError("logits(): the engine holds no logits: no loss forward has run on this binding since the last generate or "
+                               "score, or the last one replaced them in place by d loss / d logits (grad mode on with trainable "
+                               "parameters).  Call the model under torch.no_grad() first")
+        return self._engine.buffer("logits").view(*self._token_losses_shape, -1)
+
+    def _check_teacher_alias(self, eng, teacher):
+        own = eng.buffer("logits")
+        a0, a1 = own.data_ptr(), own.data_ptr() + own.numel() * own.element_size()
+        b0, b1 = teacher.data_ptr(), teacher.data_ptr() + teacher.numel() * teacher.element_size()
+        if a0 < b1 and b0 < a1:
+            raise ValueError(f"target_encoding['teacher_logits'] {tuple(teacher.shape)} {teacher.dtype} overlaps this model's own logits buffer "
+                             "(a view from logits() of the same model?): the loss kernel rewrites that buffer while it reads the teacher; "
+                             "pass a clone")
 
     def flat_grads(self, model="main"):
         return self._flat.get(model)
@@ -453,7 +511,28 @@ class MyModel(nn.Module):
                     raise ValueError(f"target_encoding['loss_weights'] {'[B, n, Lt] ' if grouped else ''}is on {weights.device}, "
                                      f"the labels on {tgt.device}")
                 weights = weights.detach().to(torch.float32).contiguous()
+            teacher = target_encoding["teacher_logits"] if "teacher_logits" in target_encoding else None
+            alpha = self._distill_options["distill_alpha"]
+            if teacher is not None:
+                want = tuple(tgt.shape) + (self.main_cfg.vocab_size,)
+                if not torch.is_tensor(teacher) or teacher.dtype not in (torch.bfloat16, torch.float32) or tuple(teacher.shape) != want:
+                    raise ValueError(f"target_encoding['teacher_logits'] has to be a bfloat16 or float32 tensor "
+                                     f"{'[B, n, Lt, V] = ' if grouped else '[B, Lt, V] = '}{want}, got "
+                                     f"{getattr(teacher, 'dtype', type(teacher))} {tuple(getattr(teacher, 'shape', ()))}")
+                if teacher.device != pixels.device:
+                    raise ValueError(f"target_encoding['teacher_logits'] {tuple(teacher.shape)} is on {teacher.device}, the model's inputs on "
+                                     f"{pixels.device}")
+                if not teacher.is_contiguous():
+                    raise ValueError(f"target_encoding['teacher_logits'] {tuple(teacher.shape)} with strides {tuple(teacher.stride())} is not "
+                                     "contiguous (it is read in place, never copied)")
+                if alpha == 0.0:
+                    raise ValueError(f"target_encoding['teacher_logits'] {tuple(teacher.shape)} was given, but distill_alpha is 0: call "
+                                     "set_loss_options(distill_alpha=...) first or leave the teacher out")
+                teacher = teacher.detach()
+            elif alpha > 0.0:
+                raise ValueError(f"distill_alpha is {alpha}, but target_encoding has no 'teacher_logits' for this loss forward")
             self._loss_weights_next = weights
+            self._teacher_next = teacher
             params = self._trainable()
             if self._lora is not None:  # behind the base parameters: the loss has a grad_fn although the base T5 is frozen
                 params = params + [p for p in self._lora.parameters()]
@@ -581,7 +660,7 @@ class MyModel(nn.Module):
         self.transformer.eval()
         try:
             eng = self._engine_for(pixels, src, tgt)
-            self._token_losses_valid = False  # (these forwards score a pad target ...
+            self._token_losses_valid = self._token_kl_valid = self._logits_valid = False  # (these forwards score a pad target ...
             eng.set_loss_options()                # ... with the plain loss: the launches generate always issued)
             for t in range(steps):
                 eng.forward(pixels, src, tgt, training=(8 if t > 0 else 0) | (2 if t > 0 else 0), seed=self._seed_base, want_grad=False)
@@ -658,7 +737,7 @@ class MyModel(nn.Module):
         self.transformer.eval()
         try:
             eng = self._engine_for(pixels, src, tgt)
-            self._token_losses_valid = False  # (this forward scores a pad target ...
+            self._token_losses_valid = self._token_kl_valid = self._logits_valid = False  # (this forward scores a pad target ...
             eng.set_loss_options()                # ... with the plain loss: the launches generate and score always issued)
             eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
             gen = eng.gen_cfg("force", N, L + 1, cfg.eos_token_id, cfg.pad_token_id, want_logprobs=True)
@@ -713,7 +792,7 @@ class MyModel(nn.Module):
         self.transformer.eval()
         try:
             eng = self._engine_for(pixels, src, tgt)
-            self._token_losses_valid = False  # (this forward scores a pad target ...
+            self._token_losses_valid = self._token_kl_valid = self._logits_valid = False  # (this forward scores a pad target ...
             eng.set_loss_options()                # ... with the plain loss: the launches generate and score always issued)
             eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
             gen = eng.gen_cfg(mode, n, max_length, cfg.eos_token_id, pad, temperature, top_k, top_p, seed, length_penalty, early_stopping,

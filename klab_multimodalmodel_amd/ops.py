@@ -492,6 +492,18 @@ def ce_fwd_opts(logits, labels, weights, inv_w, loss_row, loss, *, eps=0.0, z=0.
                                  L.stream_ptr()), "klab_ce_fwd_opts")
 
 
+def ce_fwd_distill(logits, teacher, labels, weights, inv_w, loss_row, kl_row, loss, *, eps=0.0, z=0.0, alpha=0.5, temperature=1.0,
+                   write_grad=True):
+    """ce_fwd_opts mixed with the KL divergence from `teacher` ([rows, V] bf16 or f32 logits, only read, finite) at `temperature`:
+    l = (1 - alpha) ce + alpha T^2 kl; loss_row gets the unweighted l, kl_row the unweighted kl"""
+    lib = L.load()
+    rows, V = logits.shape
+    L.check(lib.klab_ce_fwd_distill(logits.data_ptr(), logits.stride(0), L.dtype_code(logits.dtype), teacher.data_ptr(), teacher.stride(0),
+                                    L.dtype_code(teacher.dtype), labels.data_ptr(), L.ptr(weights), rows, V, float(eps), float(z), float(alpha),
+                                    float(temperature), inv_w.data_ptr(), loss_row.data_ptr(), kl_row.data_ptr(), loss.data_ptr(),
+                                    int(write_grad), L.stream_ptr()), "klab_ce_fwd_distill")
+
+
 def embed_fwd(ids, table, out, *, shift_right=False, L_seq=1, start_id=0, pad_id=0, drop_p=0.0, seed=None, tag=0, err=None):
     lib = L.load()
     rows, d = out.shape
