@@ -906,10 +906,35 @@ int klab_engine_set_loss_options(klab_engine* e, float eps, float z, const float
  * capture; with alpha == 0 or no teacher armed it issues exactly the launches described above.  The per-token kl is the buffer
  * "kl_row" of klab_engine_buffer. */
 int klab_engine_set_distill(klab_engine* e, float alpha, float temperature, const void* teacher, int t_dtype);
+/* Normaliser of the weighted training loss (klab_ce_fwd_opts / klab_ce_fwd_distill).  mode 0 (the default): sum w l / sum w, as
+ * described above.  mode 1: sum w l / N with N the number of labels != -100 -- the forward's two eager loss branches then fill
+ * inv_w with klab_ce_count instead of klab_ce_wsum, and weights of either sign are meaningful (signed advantages, whose sum is near
+ * zero).  Persists until changed.  With no weights and eps == z == 0 the forward issues klab_ce_fwd in either mode. */
+int klab_engine_set_weight_norm(klab_engine* e, int mode);
 const int* klab_engine_err_ptr(const klab_engine* e);
 /* device words {seed of the current step, base seed, forwards since seeding} (for stream-ordered snapshots; see klab_engine_get_rng) */
 const uint32_t* klab_engine_rng_ptr(const klab_engine* e);
 const void* klab_engine_buffer(const klab_engine* e, const char* name, long* rows, long* cols, int* dtype);
+
+/* ---- self-critical sequence training (csrc/scst.hip) ------------------------------------------------------------------------
+ * klab_ciderd_rewards: out[r] (f32 [rows]) = CIDEr-D, over units = token ids, of hypothesis row r of hyp (int64 [rows, L] as
+ * generate returns them: column 0 the start token, pads after EOS; rows = B * n_h, row r belongs to image r / n_h) against the
+ * present references of its image in refs (int64 [B, R, Lr] in label format: closed by EOS, whatever follows ignored; a row whose
+ * first entry is negative is absent).  Units: the tokens through the first EOS, the EOS itself when count_eos; an id < 0 or
+ * >= 0xFFFF ends the sequence.  (keys, idf): the document-frequency table, cap slots (a power of two >= 2), key = t0 | t1 << 16 |
+ * t2 << 32 | t3 << 48 with 0xFFFF in absent positions, all ones = empty slot, home slot (key * 0x9E3779B97F4A7C15) >> (64 - log2
+ * cap), linear probing with wrap-around; an n-gram it does not hold weighs log_n.  Exactly 0 when the image has no present
+ * reference or the hypothesis no units.  One launch; the same bits on every run.
+ * KLAB_ERR_UNSUPPORTED (before anything is enqueued): L > 65, Lr > 64, R outside 1..16.
+ * klab_scst_targets: seq int64 [rows, L] (rows = B * n), rewards f32 [rows] -> labels int64 [rows, Lt] (seq's columns 1.. through
+ * the row's first EOS, all L - 1 without one; -100 behind), weights f32 [rows, Lt] (the row's advantage on its scored columns, 0
+ * elsewhere) and advantages f32 [rows].  mode 0: reward - baseline[b] (f32 [B]); 1: leave-one-out, reward - (sum of the image's
+ * other rewards, in index order) / (n - 1), n >= 2; 2: the reward.  Lt >= L - 1.  Every output element is stored exactly once. */
+int klab_ciderd_rewards(const long long* hyp, int rows, int n_h, int L, const long long* refs, int R, int Lr,
+                        const unsigned long long* keys, const float* idf, long cap, float log_n, float sigma, int eos, int count_eos,
+                        float* out, void* stream);
+int klab_scst_targets(const long long* seq, int rows, int n, int L, const float* rewards, const float* baseline, int mode, int eos, int Lt,
+                      long long* labels, float* weights, float* advantages, void* stream);
 
 /* ---- crash diagnostics (opt-in; csrc/diag.cpp) -------------------------------------------------------------------------
  * klab_segv_trace_install: on SIGSEGV / SIGBUS / SIGABRT / SIGFPE / SIGILL write the context string and the native backtrace

@@ -223,6 +223,7 @@ struct klab_engine {
   float loss_eps = 0.f, loss_z = 0.f;
   const float* loss_w_armed = nullptr;
   float *loss_w_buf = nullptr, *inv_w = nullptr;
+  int weight_norm = 0;  // klab_engine_set_weight_norm: 0 = sum w l / sum w, 1 = sum w l / (number of labels)
   // klab_engine_set_distill: alpha and T persist, the teacher's logits are one-shot and read in place (never staged: Bd*Lt x V)
   float kd_alpha = 0.f, kd_T = 1.f;
   const void* kd_teacher = nullptr;
@@ -1938,6 +1939,12 @@ extern "C" int klab_engine_set_graph(klab_engine* e, int on) {
   return 0;
 }
 
+// inv_w of the two eager loss branches: 1 / sum of the weights, or 1 / count of the labels (klab_engine_set_weight_norm)
+static int loss_norm(klab_engine* e, const float* loss_w, int rows, void* stream) {
+  if (e->weight_norm == 1) return klab_ce_count(e->tgt_buf, rows, e->inv_w, stream);
+  return klab_ce_wsum(e->tgt_buf, loss_w, rows, e->inv_w, stream);
+}
+
 extern "C" int klab_engine_forward(klab_engine* e, const float* pixels, const long long* src_ids, const long long* tgt_ids, int training,
                                    uint32_t seed, int want_grad, void* stream) {
   if (!e || !e->bound || !pixels || !src_ids || !tgt_ids) return KLAB_ERR_BADARG;
@@ -2011,7 +2018,7 @@ extern "C" int klab_engine_forward(klab_engine* e, const float* pixels, const lo
     if (kd_teacher && e->kd_alpha > 0.f) {
       // distillation: eager like the options path below, never a graph slot -- the teacher's address and the options change
       // between steps and a replay would bake them in
-      RC(klab_ce_wsum(e->tgt_buf, loss_w, Md, e->inv_w, c.ws()));
+      RC(loss_norm(e, loss_w, Md, c.ws()));
       RC(klab_ce_fwd_distill(e->logits, V, c.dt, kd_teacher, V, e->kd_tdtype, e->tgt_buf, loss_w, Md, V, e->loss_eps, e->loss_z, e->kd_alpha,
                              e->kd_T, e->inv_w, e->loss_row, e->kl_row, loss_dst, (want_grad ? 1 : 0) | 2, c.ws()));
     } else if (!loss_w && e->loss_eps == 0.f && e->loss_z == 0.f) {
@@ -2021,7 +2028,7 @@ extern "C" int klab_engine_forward(klab_engine* e, const float* pixels, const lo
     } else {
       // label smoothing, z-loss or weights: eager like the LM head beside it, never a graph slot -- the options change between
       // steps and a replay would bake them in
-      RC(klab_ce_wsum(e->tgt_buf, loss_w, Md, e->inv_w, c.ws()));
+      RC(loss_norm(e, loss_w, Md, c.ws()));
       RC(klab_ce_fwd_opts(e->logits, V, c.dt, e->tgt_buf, loss_w, Md, V, e->loss_eps, e->loss_z, e->inv_w, e->loss_row, loss_dst,
                           (want_grad ? 1 : 0) | 2, c.ws()));
     }
@@ -2077,6 +2084,12 @@ extern "C" int klab_engine_set_loss_options(klab_engine* e, float eps, float z, 
   if (weights && !e->bound) return KLAB_ERR_BADARG;
   e->loss_eps = eps; e->loss_z = z;
   e->loss_w_armed = weights;
+  return KLAB_OK;
+}
+// Normaliser of the weighted loss: 0 = the sum of the weights, 1 = the count of the labels (signed weights).  Persists.
+extern "C" int klab_engine_set_weight_norm(klab_engine* e, int mode) {
+  if (!e || (mode != 0 && mode != 1)) return KLAB_ERR_BADARG;
+  e->weight_norm = mode;
   return KLAB_OK;
 }
 // Distillation in the training loss (klab_ce_fwd_distill): alpha and temperature persist until changed; `teacher` (device, B*n*Lt x V

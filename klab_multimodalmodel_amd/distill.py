@@ -21,7 +21,7 @@ def teacher_logits(teacher, images, source_encoding, target_encoding, student=No
         raise ValueError(f"the teacher's vocab_size is {teacher.main_cfg.vocab_size}, the student's {student.main_cfg.vocab_size}: "
                          "distillation needs logits over one vocabulary")
     was_training = teacher.transformer.training
-    saved = (dict(teacher._loss_options), dict(teacher._distill_options))
+    saved = (dict(teacher._loss_options), dict(teacher._distill_options), teacher._weight_norm)
     teacher.transformer.eval()
     try:
         teacher.set_loss_options()
@@ -29,6 +29,6 @@ def teacher_logits(teacher, images, source_encoding, target_encoding, student=No
             teacher(images, source_encoding, {"input_ids": target_encoding["input_ids"]})
         return teacher.logits()
     finally:
-        teacher._loss_options, teacher._distill_options = saved
+        teacher._loss_options, teacher._distill_options, teacher._weight_norm = saved
         teacher.transformer.train(was_training)
 

@@ -402,6 +402,10 @@ class Engine:
         L.check(self._lib.klab_engine_set_loss_options(self._h, float(eps), float(z), weights.data_ptr() if weights is not None else None),
                 "klab_engine_set_loss_options")
 
+    def set_weight_norm(self, count=False):
+        """normaliser of the weighted loss of the forwards from now on: the sum of the weights, or (count) the number of labels"""
+        L.check(self._lib.klab_engine_set_weight_norm(self._h, 1 if count else 0), "klab_engine_set_weight_norm")
+
     def set_distill(self, alpha=0.0, temperature=1.0, teacher=None):
         """distillation weight and temperature of the forwards from now on; `teacher` (contiguous bf16 or fp32 device tensor of
         B*n*Lt x V logits, or None) for the next forward only, which reads it in place (None disarms a teacher armed earlier)"""

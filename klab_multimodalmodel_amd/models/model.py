@@ -117,6 +117,7 @@ class _LossFn(torch.autograd.Function):
         # the engine keeps a device-side counter RNG: the base only (re)seeds it, every forward advances it
         try:
             eng.set_loss_options(eps, z, weights)
+            eng.set_weight_norm(model._weight_norm == "count")
             eng.set_distill(alpha, temp, teacher)
             eng.forward(pixels, src, tgt, training=int(model.transformer.training) | (2 if model._frozen_unchanged() else 0) | (4 if model._trainable_current() else 0),
                         seed=model._seed_base, want_grad=want_grad)
@@ -271,6 +272,7 @@ class MyModel(nn.Module):
         self._fwd_token = 0
         self._loss_options = {"label_smoothing": 0.0, "z_loss": 0.0}
         self._distill_options = {"distill_alpha": 0.0, "distill_temperature": 1.0}
+        self._weight_norm = "sum"  # normaliser of a weighted loss: "sum" of the weights or "count" of the scored tokens
         self._loss_weights_next = None  # this call's target_encoding["loss_weights"], taken by _LossFn.forward
         self._teacher_next = None  # this call's target_encoding["teacher_logits"], taken by _LossFn.forward
         self._token_losses_valid = False  # the engine's per-token losses are those of a loss forward of this binding
@@ -394,14 +396,14 @@ class MyModel(nn.Module):
         return [(p, v) for p, v, _m in self._views if p.requires_grad]
 
     # ---- loss options -------------------------------------------------------------------------
-    def set_loss_options(self, label_smoothing=0.0, z_loss=0.0, distill_alpha=0.0, distill_temperature=1.0):
+    def set_loss_options(self, label_smoothing=0.0, z_loss=0.0, distill_alpha=0.0, distill_temperature=1.0, weight_norm="sum"):
         """Options of the training loss, for every forward from now on (train and eval mode, with or without gradients; generate and
         score are not touched).  For each scored token with logits x, label y and lse = logsumexp(x):
             l = lse - (1 - label_smoothing) x_y - (label_smoothing / V) sum_j x_j + z_loss lse^2
         label_smoothing is torch.nn.functional.cross_entropy's (0 <= label_smoothing < 1), z_loss the coefficient of mesh-tensorflow
         T5's auxiliary z-loss (>= 0; T5, T5 v1.1 and Flan-T5 were pre-trained with 1e-4).  Per-token weights travel with the call
-        instead: target_encoding["loss_weights"], a float [B, Lt] tensor on the model's device (finite, >= 0), used for that
-        forward only ([B, n, Lt] with labels [B, n, Lt]); the loss is sum w l / sum w over the tokens whose label is not -100.  With
+        instead: target_encoding["loss_weights"], a float [B, Lt] tensor on the model's device (finite; >= 0 under
+        weight_norm="sum"), used for that forward only ([B, n, Lt] with labels [B, n, Lt]); the loss is sum w l / sum w over the tokens whose label is not -100.  With
         both options 0 and no weights the forward runs exactly the launches of the plain loss.
         These are hyper-parameters of the training script, not model state: save, state_dict and checkpoint.py do not store them.
         Under klab DDP every rank normalises by its own sum of weights, exactly as it normalises by its own count of scored tokens
@@ -413,7 +415,12 @@ class MyModel(nn.Module):
             (1 - distill_alpha) l + distill_alpha T^2 KL(p || q)
         (Hinton's form: the T^2 keeps the soft term's gradient scale independent of T); tokens without a label add nothing to either
         term, weights and the normalisation are as above.  With distill_alpha == 0 a teacher is refused and every forward issues the
-        launches it issues without this option.  distill.teacher_logits computes the tensor from a second MyModel."""
+        launches it issues without this option.  distill.teacher_logits computes the tensor from a second MyModel.
+        weight_norm: "sum" (the default) normalises a weighted loss by the sum of the weights, as above.  "count" makes it
+            sum w l / N,   N = the number of tokens whose label is not -100,
+        with d/dx = (w / N) [...]: the form for weights of either sign, such as the advantages of self-critical training
+        (scst.SelfCritical), whose sum is near zero.  All-ones weights give the plain loss's bits under both; without weights and
+        with neutral options "count" runs the plain launches.  Under klab DDP every rank divides by its own count."""
         eps, z = float(label_smoothing), float(z_loss)
         alpha, temp = float(distill_alpha), float(distill_temperature)
         if not (math.isfinite(eps) and 0.0 <= eps < 1.0):
@@ -424,16 +431,22 @@ class MyModel(nn.Module):
             raise ValueError(f"`distill_alpha` has to be a finite float in [0, 1], but is {distill_alpha}")
         if not (math.isfinite(temp) and temp > 0.0):
             raise ValueError(f"`distill_temperature` has to be a finite float > 0, but is {distill_temperature}")
+        if weight_norm not in ("sum", "count"):
+            raise ValueError(f"`weight_norm` has to be 'sum' or 'count', but is {weight_norm!r}")
         self._loss_options = {"label_smoothing": eps, "z_loss": z}
         self._distill_options = {"distill_alpha": alpha, "distill_temperature": temp}
+        self._weight_norm = weight_norm
 
     @property
     def loss_options(self):
         """dict(label_smoothing, z_loss) as set_loss_options left them, and distill_alpha and distill_temperature beside them once
-        either differs from its default (0 and 1): a model that never asked for distillation reads back the two options it always had"""
+        either differs from its default (0 and 1): a model that never asked for distillation reads back the two options it always had.
+        weight_norm is reported likewise, once it differs from 'sum'"""
         out = dict(self._loss_options)
         if self._distill_options != {"distill_alpha": 0.0, "distill_temperature": 1.0}:
             out.update(self._distill_options)
+        if self._weight_norm != "sum":
+            out["weight_norm"] = self._weight_norm
         return out
 
     def token_losses(self):

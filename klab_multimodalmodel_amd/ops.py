@@ -504,6 +504,30 @@ def ce_fwd_distill(logits, teacher, labels, weights, inv_w, loss_row, kl_row, lo
                                     int(write_grad), L.stream_ptr()), "klab_ce_fwd_distill")
 
 
+def ciderd_rewards(hyp, refs, keys, idf, log_n, out, *, n_h=1, sigma=6.0, eos=1, count_eos=True):
+    """out[r] (f32 [rows]) = CIDEr-D over token ids of row r of hyp (int64 [rows, L], start token first) against the present
+    references of image r // n_h in refs (int64 [B, R, Lr], label format); (keys, idf): the document-frequency table
+    (int64-viewed uint64 keys and f32 values, a power of two of slots), log_n the weight of an n-gram it does not hold"""
+    lib = L.load()
+    rows, Lh = hyp.shape
+    B, R, Lr = refs.shape
+    if rows != B * n_h:
+        raise ValueError(f"hyp holds {rows} rows, refs {B} images of {n_h} hypotheses")
+    L.check(lib.klab_ciderd_rewards(hyp.data_ptr(), rows, int(n_h), Lh, refs.data_ptr(), R, Lr, keys.data_ptr(), idf.data_ptr(), keys.numel(),
+                                    float(log_n), float(sigma), int(eos), int(bool(count_eos)), out.data_ptr(), L.stream_ptr()),
+            "klab_ciderd_rewards")
+
+
+def scst_targets(seq, rewards, baseline, labels, weights, advantages, *, n, mode, eos=1):
+    """labels / weights [rows, Lt] and advantages [rows] of the sequences seq (int64 [rows, L], rows = B * n) under rewards
+    (f32 [rows]); mode 0: minus baseline (f32 [B]), 1: leave-one-out over the image's n rows, 2: no baseline"""
+    lib = L.load()
+    rows, Ls = seq.shape
+    L.check(lib.klab_scst_targets(seq.data_ptr(), rows, int(n), Ls, rewards.data_ptr(), L.ptr(baseline), int(mode), int(eos),
+                                  labels.shape[-1], labels.data_ptr(), weights.data_ptr(), advantages.data_ptr(), L.stream_ptr()),
+            "klab_scst_targets")
+
+
 def embed_fwd(ids, table, out, *, shift_right=False, L_seq=1, start_id=0, pad_id=0, drop_p=0.0, seed=None, tag=0, err=None):
     lib = L.load()
     rows, d = out.shape
