@@ -5,7 +5,8 @@
 //                      Two launches: one 256-thread workgroup per row streams the row once (online max / sum-exp and a
 //                      per-thread sorted candidate list, merged across the workgroup in LDS), then one wave per sample merges
 //                      the k sorted row lists.  Ties are broken by the LOWER flat index, in both stages.
-//   klab_beam_topk_scores : the same over rows that already hold processed log-probabilities (csrc/logits_proc.hip).
+//   klab_beam_topk_scores : the same over rows that already hold processed log-probabilities (csrc/logits_proc.hip); candidates are
+//                      ranked by row + running score as f32 rounds it, so scores the add makes equal tie by the lower index too.
 //   klab_beam_update : one wave per sample; HF's `_get_running_beams_for_next_iteration`, `_update_finished_beams`,
 //                      `_check_early_stop_heuristic` and the per-sample part of `_beam_search_has_unfinished_sequences`
 //                      over fixed-shape state (klab_beam_update_args, include/klab_mm.h).
@@ -64,12 +65,18 @@ __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_rows_kernel(const T* _
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) { lv[c] = -INFINITY; li[c] = INT_MAX; }
   float m = -INFINITY, s = 0.f;
+  const float rs = run_score[r];
+  // NORMED ranks by the final score row[j] + run_score[r], not by row[j]: the add can round distinct scores to one value (every
+  // score of a -1e9 beam does), and such candidates tie by the lower index like any others.  (The log-softmax form ranks a row by
+  // its logits: equal logits are the ties it orders by index.)
   auto take = [&](float xv, int j) {
     if constexpr (!NORMED) {
       if (xv > m) { s = s * __expf(m - xv) + 1.f; m = xv; }
       else s += __expf(xv - m);
+      list_insert<KMAX>(lv, li, xv, j);
+    } else {
+      list_insert<KMAX>(lv, li, xv + rs, j);
     }
-    list_insert<KMAX>(lv, li, xv, j);
   };
   constexpr int VEC = 16 / sizeof(T);
   int j0 = 0;
@@ -103,7 +110,6 @@ __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_rows_kernel(const T* _
   float S = 0.f;
   for (int w = 0; w < TOPK_THREADS / 64; ++w) S += s_red[1][w] * __expf(s_red[0][w] - M);
   const float logS = logf(S);
-  const float rs = run_score[r];
   const int beam = r % k;
   __syncthreads();  // s_red is reused below
   // K2 rounds of a workgroup argmax over the heads of the per-thread sorted lists
@@ -121,7 +127,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_rows_kernel(const T* _
     if (h < KMAX && s_i[tid * KMAX + h] == bi) ++h;  // indices are unique within a row: exactly one thread advances
     if (tid == 0) {
       const long o = (long)r * K2 + n;
-      row_score[o] = (NORMED ? bv : ((bv - M) - logS)) + rs;  // log_softmax (x - max - log sum exp), then + running score
+      row_score[o] = NORMED ? bv : ((bv - M) - logS) + rs;  // log_softmax (x - max - log sum exp), then + running score
       row_idx[o] = bi == INT_MAX ? INT_MAX : beam * V + bi;
     }
   }

@@ -229,7 +229,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(klab_sample
         if (c < nv) o[c] = k[c] >= lo ? sample_val(k[c]) : -INFINITY;
     }
   }
-  // 4. draw: exclusive scan of the per-thread kept mass in token order (threads own consecutive token ranges)
+  // 4. draw: exclusive scan of the per-thread kept mass in token order (threads own consecutive token ranges).  The exclusive
+  //    value is the previous lane's inclusive one, not inc - ts: behind kept tokens of negligible mass the difference cancels to
+  //    0 in the thread that holds the row's mass, which then looks like the first one and takes a u = 0 draw from them
   float inc = ts;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
@@ -237,8 +239,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(klab_sample
     if (lane >= o) inc += t;
   }
   if (lane == 63) s_f[wid] = inc;
+  const float prev = __shfl_up(inc, 1, 64);
   __syncthreads();
-  float base = inc - ts, G = 0.f;
+  float base = lane ? prev : 0.f, G = 0.f;
   for (int q = 0; q < SAMPLE_WAVES; ++q) {
     if (q < wid) base += s_f[q];
     G += s_f[q];

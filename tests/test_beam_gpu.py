@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.beam_ref import update_reference
 from tests.helpers import GOLD, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -142,41 +143,7 @@ def test_beam_decode_attn_slot_table_matches_gather(dtype):
     _check_against_formula("group", out, qc.view(R, H, dk), kv4[:, :, 0], kv4[:, :, 1], None, dtype)
 
 
-# ---- klab_beam_update against a torch restatement of HF's helpers (transformers/generation/utils.py) --------------------------
-def _gather(t, idx):
-    while idx.dim() < t.dim():
-        idx = idx.unsqueeze(-1)
-    return torch.take_along_dim(t, idx, dim=1)
-
-
-def _hf_step(st, cs, ci, c, k, V, Lm, eos, lp, es):
-    """one iteration of `_beam_search` from the top-k candidates on (cur_len = c, decoder_prompt_len = 1)"""
-    K2 = 2 * k
-    beam, tok = ci // V, ci % V
-    trs = _gather(st["run_seq"], beam).clone()
-    trs[:, :, c] = tok
-    hits = (tok == eos) | (c + 1 >= Lm)
-    trl = cs + hits.float() * -1.0e9                                                   # _get_running_beams_for_next_iteration
-    ni = torch.topk(trl, k)[1]
-    out = dict(run_seq=_gather(trs, ni), run_score=_gather(trl, ni), tok=_gather(tok, ni), par=_gather(beam, ni))
-    did = hits & (torch.arange(K2) < k)[None]                                          # _update_finished_beams
-    tlp = cs / ((c + 1 - 1) ** lp)
-    tlp = tlp + (st["fin_flag"].all(-1, keepdim=True) & (es is True)).float() * -1.0e9
-    tlp = tlp + (~st["unsat"]).float() * -1.0e9
-    tlp = tlp + (~did) * -1.0e9
-    msc = torch.cat((st["fin_score"], tlp), 1)
-    mi = torch.topk(msc, k)[1]
-    out["fin_score"] = _gather(msc, mi)
-    out["fin_flag"] = _gather(torch.cat((st["fin_flag"], did), 1), mi)
-    out["fin_seq"] = _gather(torch.cat((st["fin_seq"], trs), 1), mi)
-    bhl = (Lm - 1) if (es == "never" and lp > 0.0) else c                              # _check_early_stop_heuristic (cur_len c+1)
-    best = out["run_score"][:, :1] / (bhl ** lp)
-    worst = torch.where(out["fin_flag"], out["fin_score"].min(1, keepdim=True)[0], -1.0e9)
-    out["unsat"] = st["unsat"] & (best > worst).any(-1, keepdim=True)
-    out["word"] = (int(out["unsat"].any()) | (2 * int((~out["fin_flag"].all(-1)).any())) | (4 * int((~hits.all(-1)).any())))
-    return out
-
-
+# ---- klab_beam_update against the restatement of HF's helpers (tests/beam_ref.py: update_reference) ---------------------------------
 def _state(B, k, Lm, g, c, full, unsat):
     run_seq = torch.randint(2, 50, (B, k, Lm), generator=g)
     run_seq[:, :, 0] = 0
@@ -208,7 +175,7 @@ def test_beam_update_matches_reference_step(es, lp):
         tok = torch.stack([torch.randperm(V - 2, generator=g)[:K2] + 2 for _ in range(B)])
         tok[:, eos_at] = eos
         ci = beam * V + tok
-        ref = _hf_step(st, cs, ci, c, k, V, Lm, eos, lp, es)
+        ref = update_reference(st, cs, ci, c, dict(k=k, V=V, Lm=Lm, eos=eos, lp=lp, es={False: 0, True: 1, "never": 2}[es]))
         dev = {n: t.cuda().contiguous() for n, t in st.items()}
         run_out = torch.zeros_like(dev["run_seq"])
         fin_out = torch.zeros_like(dev["fin_seq"])
@@ -232,6 +199,7 @@ def test_beam_update_matches_reference_step(es, lp):
         assert torch.equal(fin_flag.cpu().bool(), ref["fin_flag"]), what
         fl = ref["fin_flag"]
         assert torch.equal(fin_out.cpu()[fl], ref["fin_seq"][fl]), what  # unfinished pool entries are placeholders
+        assert torch.equal(dev["fin_len"].cpu()[fl], ref["fin_len"][fl]), what
         assert torch.equal(unsat_d.cpu().bool(), ref["unsat"].view(-1)), what
         assert int(stop[c]) == ref["word"], what
         if c + 1 >= Lm:
