@@ -446,7 +446,7 @@ typedef struct klab_engine klab_engine;
 
 int klab_sizeof_t5_cfg(void);    /* sizeof(klab_t5_cfg) / sizeof(klab_model_cfg): the ctypes mirrors are checked against them */
 int klab_sizeof_model_cfg(void);
-int klab_sizeof_sample_args(void); /* likewise klab_sample_args, klab_logits_proc_args, klab_gen_cfg */
+int klab_sizeof_sample_args(void); /* likewise klab_sample_args, klab_logits_proc_args, klab_gen_cfg, klab_constrain_args (below) */
 int klab_sizeof_logits_proc_args(void);
 int klab_sizeof_gen_cfg(void);
 klab_engine* klab_engine_create(const klab_model_cfg* cfg); /* NULL on an invalid config (e.g. Swin width != d_model:
@@ -783,6 +783,40 @@ int klab_logits_process_rows(const klab_logits_proc_args* a, void* stream);
  * log_softmax): per sample b, the 2k best of  scores row b*k+j + run_score[b*k+j], same order, ties and buffers.           */
 int klab_beam_topk_scores(const float* scores, long ld, int row_div, const float* run_score, int B, int k, int V, float* row_score,
                           int* row_idx, float* out_score, int* out_idx, void* stream);
+/* ---- trie-constrained decoding (HF's PrefixConstrainedLogitsProcessor without the host callback; csrc/constrain.hip) -----------
+ * The trie (klab_multimodalmodel_amd/constrain.py), int32 on the device, CSR: node i's edges are child_tok[child_off[i] ..
+ * child_off[i+1]) (token ids, ascending) and lead to child_node[same index]; child_off is [n_nodes + 1], the other two [n_edges].
+ * EOS is an ordinary edge to a leaf.  A row's state is the node it stands on: >= 0 a node, -1 off the trie.
+ * klab_constrain_rows: one launch advances every row's node and masks its scores.
+ *   advance: first != 0: node_out[r] = root[r / root_div]; else node_out[r] = the child of node_in[parent ? parent[r] : r] behind
+ *     token last_tok[r] (int64), -1 when that node is -1 or has no such edge (a wave-cooperative 64-ary search over child_tok).
+ *     node_in and node_out are different buffers when parent is given (rows read each other's state).
+ *   mask: scores = the fp32 value of logits row (r / row_div) (element stride ld, dtype bf16 or f32), or with log_softmax != 0 their
+ *     log_softmax over the WHOLE row (the reduction of klab_logits_process_rows, bit for bit); out[r*ld_out + j] = the score where
+ *     j is a child token of node_out[r], -inf elsewhere.  A node without children and the state -1 allow exactly eos_id.  out is
+ *     f32 [rows, ld_out >= V]; columns >= V are never written.  out may be the f32 input itself (row_div 1, ld_out == ld).
+ * V <= 32768 (KLAB_ERR_UNSUPPORTED above).  KLAB_ERR_BADARG: a NULL among logits, out, node_out, child_off, the tables of a trie
+ * with edges, root (first) or node_in / last_tok (not first); ld or ld_out < V; n_nodes < 1, n_edges < 0 or n_edges > n_nodes - 1.
+ * Indices read from the tables are checked against n_nodes / n_edges / V on the device before they are used.                 */
+typedef struct {
+  int dtype;
+  const void* logits; long ld; int row_div;
+  int rows, V, log_softmax;
+  const int* child_off; const int* child_tok; const int* child_node; int n_nodes, n_edges;
+  int first; const int* root; int root_div;
+  const int* node_in; const int* parent; const long long* last_tok;
+  int* node_out;
+  int eos_id;
+  float* out; long ld_out;
+} klab_constrain_args;
+int klab_constrain_rows(const klab_constrain_args* a, void* stream);
+int klab_sizeof_constrain_args(void);
+/* The constraint of a decoding session: the trie's tables (device memory, owned by the caller and alive while the session runs, as
+ * the forced table; not copied) and root_dev [B] int32 on the device, the start node of every image, shared by its n rows.   */
+typedef struct {
+  const int* child_off; const int* child_tok; const int* child_node; int n_nodes, n_edges;
+  const int* root_dev;
+} klab_constraint_cfg;
 /* Logits-processor settings of a decoding session (host memory; bad_off / bad_tok are copied at klab_engine_gen_begin).
  * KLAB_ERR_BADARG for penalty <= 0, negative sizes, empty entries or ids >= vocab; KLAB_ERR_UNSUPPORTED for more than 1024
  * bad-word tokens in all.                                                                                                 */
@@ -829,7 +863,20 @@ typedef struct {
  *   f32, len [M] int32, order [B*n_out] int32 (n_out <= n <= 64; order may be NULL), and the log-probabilities themselves into
  *   token_logprobs [M, length] f32 when not NULL.  All device memory.
  * gen_set_attn / gen_attn_bytes (sampling, pick and force): the session also writes the head-mean cross-attention map of every
- *   position into a caller-owned f32 [n_dec_layers, M, max_length, Le] buffer armed in front of gen_begin (below).             */
+ *   position into a caller-owned f32 [n_dec_layers, M, max_length, Le] buffer armed in front of gen_begin (below).
+ * gen_set_constraint (pick, sampling and beam search; vocab <= 32768; KLAB_GEN_FORCE with one: KLAB_ERR_BADARG at gen_begin): every
+ *   row may only choose a child of the trie node it stands on (klab_constrain_rows).  As the forced table and the maps, the
+ *   constraint is armed in front of gen_begin and klab_gen_cfg keeps its fields and its size (below).  The workspace grows, behind everything else, by two int32 [M] node buffers used ping-pong and, where the session has none, by the
+ *   f32 [M, vocab] rows.  Every constrained position costs one launch more than the same position unconstrained:
+ *     pick, sampling: klab_constrain_rows on the logits into the f32 rows, then the existing chooser over them -- the processors
+ *       (the session's settings, for pick neutral ones without) with pick, or the processors in place and klab_sample_rows;
+ *     beam search: klab_constrain_rows with log_softmax, then klab_beam_topk_scores; with processors klab_logits_process_rows with
+ *       log_softmax, then the constraint in place (a mask of -inf commutes with every processor).
+ *   The advance reads the tokens chosen last (the next decoder inputs) and, under beam search, klab_beam_update's parent rows; the
+ *   first chosen position (1, or n_forced + 1 behind a decoder prompt, which is not walked) starts every row at root_dev[image].
+ *   gen_buffer "nodes": [M, 1] int32, the node every row stood on when the last position was chosen (the walk over the tokens
+ *   chosen before it).  The log-probabilities of a want_logprobs session are those of the masked scores.  A session begun without
+ *   a constraint armed launches exactly what it launched before the setter existed, and every buffer lies where it lay.        */
 #define KLAB_GEN_PICK 0
 #define KLAB_GEN_SAMPLE 1
 #define KLAB_GEN_BEAM 2
@@ -869,6 +916,13 @@ int klab_engine_gen_set_forced(klab_engine* e, const long long* tokens_dev, long
  * the streams they are given.                                                                                                */
 size_t klab_engine_gen_attn_bytes(klab_engine* e, const klab_gen_cfg* cfg);
 int klab_engine_gen_set_attn(klab_engine* e, float* maps_dev, size_t bytes, void* stream);
+/* The constraint of the NEXT klab_engine_gen_begin (one-shot in the same way: gen_begin takes it whether it succeeds or fails, so a
+ * session begun without this call never sees one).  The struct is copied here; the tables and root_dev are device memory owned by the
+ * caller and alive while the session runs.  NULL disarms.  KLAB_ERR_BADARG for a NULL child_off or root_dev, NULL edge tables of a
+ * trie with edges, n_nodes < 1, n_edges < 0 or n_edges > n_nodes - 1.  While a constraint is armed klab_engine_gen_workspace_bytes
+ * answers for the session the next gen_begin starts: it includes the constraint's buffers (0 for KLAB_GEN_FORCE or vocab > 32768).
+ * stream is unused today: the session's own launches read the tables on the streams they are given.                          */
+int klab_engine_gen_set_constraint(klab_engine* e, const klab_constraint_cfg* k, void* stream);
 size_t klab_engine_gen_workspace_bytes(klab_engine* e, const klab_gen_cfg* cfg);
 int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, void* ws, void* stream);
 int klab_engine_gen_step(klab_engine* e, int t, void* ws, void* stream);

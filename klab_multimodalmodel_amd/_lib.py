@@ -91,6 +91,17 @@ class LogitsProcCfg(C.Structure):  # klab_logits_proc_cfg
                 ("n_bad", i32), ("bad_off", C.POINTER(i32)), ("bad_tok", C.POINTER(i32))]
 
 
+class ConstrainArgs(C.Structure):  # klab_constrain_args
+    _fields_ = [("dtype", i32), ("logits", vp), ("ld", i64), ("row_div", i32), ("rows", i32), ("V", i32), ("log_softmax", i32),
+                ("child_off", vp), ("child_tok", vp), ("child_node", vp), ("n_nodes", i32), ("n_edges", i32),
+                ("first", i32), ("root", vp), ("root_div", i32), ("node_in", vp), ("parent", vp), ("last_tok", vp), ("node_out", vp),
+                ("eos_id", i32), ("out", vp), ("ld_out", i64)]
+
+
+class ConstraintCfg(C.Structure):  # klab_constraint_cfg
+    _fields_ = [("child_off", vp), ("child_tok", vp), ("child_node", vp), ("n_nodes", i32), ("n_edges", i32), ("root_dev", vp)]
+
+
 class AdamWGroup(C.Structure):  # klab_adamw_group
     _fields_ = [("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("bias_corr1", f32), ("bias_corr2", f32)]
 
@@ -168,6 +179,8 @@ SIGNATURES = {
     "klab_sizeof_gen_cfg": [],
     "klab_force_rows": [C.POINTER(ForceArgs), vp],
     "klab_sizeof_force_args": [],
+    "klab_constrain_rows": [C.POINTER(ConstrainArgs), vp],
+    "klab_sizeof_constrain_args": [],
     "klab_beam_topk_scores": [vp, i64, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "klab_dbias_reduce": [vp, i32, vp, i32, i32, i32, i32, vp],
     "klab_swin_mlp_fused": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],

@@ -124,6 +124,8 @@ struct GenRun {
   ProcSet lp;
   ForcedTable forced;
   AttnMaps maps;
+  klab_constraint_cfg cons{};  // the session's copy of its constraint (klab_engine_gen_set_constraint); child_off NULL: none
+  const klab_constraint_cfg* constraint() const { return cons.child_off ? &cons : nullptr; }
   int cur = 0;
 };
 
@@ -184,6 +186,7 @@ struct klab_engine {
   GenRun gen;
   ForcedTable forced_armed;  // one-shot: taken (and cleared) by the next klab_engine_gen_begin
   AttnMaps attn_armed;       // one-shot in the same way
+  klab_constraint_cfg cons_armed{};  // ... and so is the constraint (child_off NULL: none)
   // lang scratch (no grad => reused across layers)
   void* kv_all = nullptr; void* dkv_all = nullptr;
   void* logits = nullptr; float *loss_row = nullptr, *inv_n = nullptr, *loss = nullptr;
@@ -2231,11 +2234,12 @@ int make_procs(const klab_engine* e, const klab_logits_proc_cfg* cfg, ProcSet& l
   }
   return 0;
 }
-bool gen_shape_ok(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp) {
+bool gen_shape_ok(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp, const klab_constraint_cfg* k) {
   if (!e->bound || g.n < 1 || g.max_length < 2 || g.max_length - 1 > e->Lt) return false;
   if (e->ncap != 1) return false;  // a session's prefill is one decoder row per image (row b*Lt of the logits is position 0 of image b)
   if (g.want_logprobs && g.mode == KLAB_GEN_BEAM) return false;  // beam search keeps its own scores
   const int V = e->cfg.main.vocab;
+  if (k && (V > 32768 || g.mode == KLAB_GEN_FORCE)) return false;  // the register row of klab_constrain_rows; a force session chooses nothing
   switch (g.mode) {
     case KLAB_GEN_BEAM:
       return g.n <= 16 && V >= 2 * g.n && (!lp.on || V <= 32768) && g.early_stopping >= 0 && g.early_stopping <= 2;
@@ -2258,11 +2262,13 @@ struct GenWs {
   // sampling and pick
   long long* seq; int* done;
   float* logprob = nullptr;  // want_logprobs only: [M, max_length]
+  int* node[2] = {nullptr, nullptr};  // a constraint only: the rows' trie nodes [M], ping-pong by position parity
 };
 // decoder scratch, logits and self-attention cache for M = B*n rows, the mode's state, the next decoder inputs, the stop words, then
 // the processors' f32 rows [M, V] (not for pick, which writes none), the bad-words table and, with want_logprobs, the per-token
-// log-probabilities [M, max_length] (last, so that every other buffer lies where it lies without them)
-size_t plan_gen(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp, void* base, GenWs& w) {
+// log-probabilities [M, max_length] (behind those, so that every other buffer lies where it lies without them); behind all of it a
+// constraint's two node buffers [M] and, where the session has none above, its f32 rows [M, V]
+size_t plan_gen(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp, const klab_constraint_cfg* k, void* base, GenWs& w) {
   Bump b(base);
   const klab_t5_cfg& cfg = e->cfg.main;
   const size_t es = e->es;
@@ -2293,9 +2299,14 @@ size_t plan_gen(const klab_engine* e, const klab_gen_cfg& g, const ProcSet& lp, 
     w.seq = (long long*)b.take(M * Lm * 8); w.done = (int*)b.take(M * 4);
   }
   w.prev = (long long*)b.take(M * 8); w.stop = (int*)b.take((long)Lm * 4);
-  if (lp.on && g.mode != KLAB_GEN_PICK) w.proc = (float*)b.take(M * V * 4);
+  const bool proc_rows = lp.on && g.mode != KLAB_GEN_PICK;
+  if (proc_rows) w.proc = (float*)b.take(M * V * 4);
   if (!lp.table.empty()) w.table = (int*)b.take(lp.table.size() * 4);
   if (g.want_logprobs) w.logprob = (float*)b.take(M * Lm * 4);
+  if (k) {
+    w.node[0] = (int*)b.take(M * 4); w.node[1] = (int*)b.take(M * 4);
+    if (!proc_rows) w.proc = (float*)b.take(M * V * 4);
+  }
   return b.off;
 }
 klab_logits_proc_args proc_args(const ProcSet& lp, const int* table, int dtype, const void* logits, long ld, int row_div, int rows, int V,
@@ -2331,11 +2342,31 @@ klab_beam_update_args beam_args(const klab_engine* e, const GenWs& w, int c) {
 // the processed arg-max.  A position the session's forced table covers (every position of a force session: scoring, EOS finishes
 // a row, the token's log-probability is kept; positions 1 .. n of a pick or sample session: the decoder prompt, no logits read)
 // is one klab_force_rows instead.
+// A constraint adds one klab_constrain_rows per chosen position (a mask of -inf commutes with every processor): on the logits into
+// the f32 rows in front of the chooser, which then reads those; under beam search with log_softmax in front of the top-2k, or in
+// place behind the processors.
 int gen_pos(klab_engine* e, const Ctx& c, const GenWs& w, const void* logits, long ld, int row_div, int pos) {
   const GenRun& g = e->gen;
   const int B = e->B, n = g.cfg.n, V = e->cfg.main.vocab, start = e->cfg.main.start_id;
+  const klab_constraint_cfg* k = g.constraint();
+  // the constraint of position pos over `from` into the f32 rows: the first chosen position starts at the roots, every later one
+  // moves over the tokens chosen last (beam search: from the parent row's node)
+  auto constrain = [&](int dt, const void* from, long ld_from, int div_from, int log_softmax) {
+    klab_constrain_args a;
+    memset(&a, 0, sizeof(a));
+    a.dtype = dt; a.logits = from; a.ld = ld_from; a.row_div = div_from; a.rows = B * n; a.V = V; a.log_softmax = log_softmax;
+    a.child_off = k->child_off; a.child_tok = k->child_tok; a.child_node = k->child_node; a.n_nodes = k->n_nodes; a.n_edges = k->n_edges;
+    a.first = pos == g.forced.n + 1; a.root = k->root_dev; a.root_div = n;
+    a.node_in = w.node[(pos + 1) & 1]; a.node_out = w.node[pos & 1];
+    a.parent = g.cfg.mode == KLAB_GEN_BEAM ? w.parent : nullptr; a.last_tok = w.prev;
+    a.eos_id = g.cfg.eos_id; a.out = w.proc; a.ld_out = V;
+    return klab_constrain_rows(&a, c.ws());
+  };
   if (g.cfg.mode == KLAB_GEN_BEAM) {
-    if (!g.lp.on) {
+    if (k && !g.lp.on) {
+      RC(constrain(c.dt, logits, ld, row_div, 1));
+      RC(klab_beam_topk_scores(w.proc, V, 1, w.run_score, B, n, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws()));
+    } else if (!g.lp.on) {
       RC(klab_beam_topk(c.dt, logits, ld, row_div, w.run_score, B, n, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws()));
     } else {
       klab_logits_proc_args p = proc_args(g.lp, w.table, c.dt, logits, ld, row_div, B * n, V, w.run_seq[(pos + 1) & 1], g.cfg.max_length,
@@ -2343,6 +2374,7 @@ int gen_pos(klab_engine* e, const Ctx& c, const GenWs& w, const void* logits, lo
       p.log_softmax = 1;
       p.out = w.proc; p.ld_out = V;
       RC(klab_logits_process_rows(&p, c.ws()));
+      if (k) RC(constrain(KLAB_F32, w.proc, V, 1, 0));
       RC(klab_beam_topk_scores(w.proc, V, 1, w.run_score, B, n, V, w.row_score, w.row_idx, w.cand_score, w.cand_idx, c.ws()));
     }
     klab_beam_update_args a = beam_args(e, w, pos);
@@ -2361,8 +2393,12 @@ int gen_pos(klab_engine* e, const Ctx& c, const GenWs& w, const void* logits, lo
     return klab_force_rows(&a, c.ws());
   }
   int dt = c.dt;
+  if (k) {
+    RC(constrain(c.dt, logits, ld, row_div, 0));
+    dt = KLAB_F32; logits = w.proc; ld = V; row_div = 1;
+  }
   if (g.lp.on || g.cfg.mode == KLAB_GEN_PICK) {
-    klab_logits_proc_args p = proc_args(g.lp, w.table, c.dt, logits, ld, row_div, B * n, V, w.seq, g.cfg.max_length, pos, start,
+    klab_logits_proc_args p = proc_args(g.lp, w.table, dt, logits, ld, row_div, B * n, V, w.seq, g.cfg.max_length, pos, start,
                                         g.cfg.eos_id);
     if (g.cfg.mode == KLAB_GEN_PICK) {
       p.pick = 1; p.done = w.done; p.pad_id = g.cfg.pad_id; p.tokens = w.prev; p.stop_word = w.stop + pos;
@@ -2388,9 +2424,11 @@ int gen_pos(klab_engine* e, const Ctx& c, const GenWs& w, const void* logits, lo
 
 extern "C" size_t klab_engine_gen_workspace_bytes(klab_engine* e, const klab_gen_cfg* cfg) {
   ProcSet lp;
-  if (!e || !cfg || make_procs(e, cfg->procs, lp) || !gen_shape_ok(e, *cfg, lp)) return 0;
+  if (!e || !cfg) return 0;
+  const klab_constraint_cfg* k = e->cons_armed.child_off ? &e->cons_armed : nullptr;  // (armed for the next gen_begin; not taken here)
+  if (make_procs(e, cfg->procs, lp) || !gen_shape_ok(e, *cfg, lp, k)) return 0;
   GenWs w;
-  return plan_gen(e, *cfg, lp, nullptr, w);
+  return plan_gen(e, *cfg, lp, k, nullptr, w);
 }
 
 // Precondition: klab_engine_forward in evaluation mode on this binding (the prefill; its logits row b*Lt is position 0 of sample b)
@@ -2412,7 +2450,7 @@ static size_t gen_attn_bytes(const klab_engine* e, const klab_gen_cfg& g) {
 
 extern "C" size_t klab_engine_gen_attn_bytes(klab_engine* e, const klab_gen_cfg* cfg) {
   ProcSet lp;
-  if (!e || !cfg || make_procs(e, cfg->procs, lp) || !gen_shape_ok(e, *cfg, lp)) return 0;
+  if (!e || !cfg || make_procs(e, cfg->procs, lp) || !gen_shape_ok(e, *cfg, lp, nullptr)) return 0;
   return gen_attn_bytes(e, *cfg);
 }
 
@@ -2426,16 +2464,30 @@ extern "C" int klab_engine_gen_set_attn(klab_engine* e, float* maps_dev, size_t 
   return 0;
 }
 
+extern "C" int klab_engine_gen_set_constraint(klab_engine* e, const klab_constraint_cfg* k, void* stream) {
+  (void)stream;  // the tables are read by the session's own launches, on the streams they are given
+  if (!e) return KLAB_ERR_BADARG;
+  e->cons_armed = klab_constraint_cfg{};
+  if (!k) return 0;  // disarm
+  if (!k->child_off || !k->root_dev || k->n_nodes < 1 || k->n_edges < 0 || k->n_edges > k->n_nodes - 1 ||
+      (k->n_edges > 0 && (!k->child_tok || !k->child_node)))
+    return KLAB_ERR_BADARG;
+  e->cons_armed = *k;
+  return 0;
+}
+
 extern "C" int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, void* ws, void* stream) {
   if (!e) return KLAB_ERR_BADARG;
   const ForcedTable forced = e->forced_armed;  // consumed whatever happens below
   e->forced_armed = ForcedTable();
   const AttnMaps maps = e->attn_armed;  // ... and so are the maps
   e->attn_armed = AttnMaps();
+  const klab_constraint_cfg cons = e->cons_armed;  // ... and the constraint
+  e->cons_armed = klab_constraint_cfg{};
   if (!cfg || !ws) return KLAB_ERR_BADARG;
   ProcSet lp;
   RC(make_procs(e, cfg->procs, lp));
-  if (!gen_shape_ok(e, *cfg, lp)) return KLAB_ERR_BADARG;
+  if (!gen_shape_ok(e, *cfg, lp, cons.child_off ? &cons : nullptr)) return KLAB_ERR_BADARG;
   if (maps.p && (cfg->mode == KLAB_GEN_BEAM || maps.bytes < gen_attn_bytes(e, *cfg))) return KLAB_ERR_BADARG;
   // a table: never under beam search; a force session needs every position 1 .. max_length - 1 from it; a prompt (pick, sample)
   // leaves at least nothing beyond the sequence, and keeps no log-probabilities (klab_gen_finalize would take an EOS inside the
@@ -2445,6 +2497,7 @@ extern "C" int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, vo
     return KLAB_ERR_BADARG;
   GenRun& g = e->gen;
   g.cfg = *cfg; g.cfg.procs = nullptr;
+  g.cons = cons;
   g.lp = std::move(lp);
   g.forced = forced;
   g.maps = maps;
@@ -2453,7 +2506,7 @@ extern "C" int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, vo
   const klab_t5_cfg& mc = e->cfg.main;
   const int n = g.cfg.n, Lm = g.cfg.max_length, B = e->B, inner = mc.n_heads * mc.d_kv;
   GenWs w;
-  plan_gen(e, g.cfg, g.lp, ws, w);
+  plan_gen(e, g.cfg, g.lp, g.constraint(), ws, w);
   if (!g.lp.table.empty()) RC((int)hipMemcpyAsync(w.table, g.lp.table.data(), g.lp.table.size() * 4, hipMemcpyHostToDevice, c.s));
   if (g.cfg.mode == KLAB_GEN_BEAM) {
     klab_beam_update_args a = beam_args(e, w, 1);
@@ -2487,10 +2540,10 @@ extern "C" int klab_engine_gen_begin(klab_engine* e, const klab_gen_cfg* cfg, vo
 extern "C" int klab_engine_gen_step(klab_engine* e, int t, void* ws, void* stream) {
   if (!e || !ws) return KLAB_ERR_BADARG;
   GenRun& g = e->gen;
-  if (g.cur < 1 || t != g.cur || t > g.cfg.max_length - 2 || !gen_shape_ok(e, g.cfg, g.lp)) return KLAB_ERR_BADARG;
+  if (g.cur < 1 || t != g.cur || t > g.cfg.max_length - 2 || !gen_shape_ok(e, g.cfg, g.lp, g.constraint())) return KLAB_ERR_BADARG;
   Ctx c{e, (hipStream_t)stream, e->cfg.dtype, e->es};
   GenWs w;
-  plan_gen(e, g.cfg, g.lp, ws, w);
+  plan_gen(e, g.cfg, g.lp, g.constraint(), ws, w);
   DecodeRows r = w.rows;
   if (g.cfg.mode == KLAB_GEN_BEAM) r.kv_slot = w.slot[t & 1];
   if (g.maps.p) { r.maps = g.maps.p; r.done = w.done; }
@@ -2503,14 +2556,14 @@ extern "C" int klab_engine_gen_step(klab_engine* e, int t, void* ws, void* strea
 extern "C" const int* klab_engine_gen_stop_word(klab_engine* e, void* ws, int pos) {
   if (!e || !ws || e->gen.cur < 1 || pos < 1 || pos >= e->gen.cfg.max_length) return nullptr;
   GenWs w;
-  plan_gen(e, e->gen.cfg, e->gen.lp, ws, w);
+  plan_gen(e, e->gen.cfg, e->gen.lp, e->gen.constraint(), ws, w);
   return w.stop + pos;
 }
 
 extern "C" const void* klab_engine_gen_buffer(klab_engine* e, void* ws, const char* name, long* rows, long* cols, int* dtype) {
   if (!e || !ws || !name || e->gen.cur < 1) return nullptr;
   GenWs w;
-  plan_gen(e, e->gen.cfg, e->gen.lp, ws, w);
+  plan_gen(e, e->gen.cfg, e->gen.lp, e->gen.constraint(), ws, w);
   if (rows) *rows = w.rows.M;
   if (!strcmp(name, "logits")) {
     if (cols) *cols = e->cfg.main.vocab;
@@ -2520,6 +2573,10 @@ extern "C" const void* klab_engine_gen_buffer(klab_engine* e, void* ws, const ch
   if (!strcmp(name, "tokens")) {
     if (cols) *cols = 1;
     return w.prev;
+  }
+  if (!strcmp(name, "nodes") && w.node[0]) {
+    if (cols) *cols = 1;
+    return w.node[e->gen.cur & 1];
   }
   if (!strcmp(name, "logprobs") && w.logprob) {
     if (cols) *cols = e->gen.cfg.max_length;
@@ -2533,7 +2590,7 @@ extern "C" int klab_engine_gen_result(klab_engine* e, void* ws, int n, int lengt
   if (!e || !ws || e->gen.cur < 1 || !seq) return KLAB_ERR_BADARG;
   const klab_gen_cfg& g = e->gen.cfg;
   GenWs w;
-  plan_gen(e, g, e->gen.lp, ws, w);
+  plan_gen(e, g, e->gen.lp, e->gen.constraint(), ws, w);
   const size_t Lm = g.max_length, k = g.n, B = e->B;
   hipStream_t s = (hipStream_t)stream;
   if (g.mode != KLAB_GEN_BEAM) {
@@ -2553,7 +2610,7 @@ extern "C" int klab_engine_gen_scores(klab_engine* e, void* ws, int length, int 
   const klab_gen_cfg& g = e->gen.cfg;
   if (length < 2 || length > e->gen.cur + 1) return KLAB_ERR_BADARG;
   GenWs w;
-  plan_gen(e, g, e->gen.lp, ws, w);
+  plan_gen(e, g, e->gen.lp, e->gen.constraint(), ws, w);
   const size_t Lm = g.max_length;
   RC(klab_gen_finalize(w.logprob, (long)Lm, w.seq, (long)Lm, e->B, g.n, length, g.eos_id, length_penalty, n_out, score, len, order, stream));
   if (!token_logprobs) return 0;

@@ -18,13 +18,11 @@
 
 #include "common.h"
 #include "klab_mm.h"
+#include "row_regs.h"
 
 namespace klab {
 
-constexpr int PROC_THREADS = 1024;
-constexpr int PROC_NPT = 32;         // scores per thread = bits per bitmap word: V <= 32768
 constexpr int PROC_MAX_HIST = 1024;  // cur_len
-constexpr int PROC_WAVES = PROC_THREADS / 64;
 
 __global__ __launch_bounds__(PROC_THREADS) void logits_process_rows_kernel(klab_logits_proc_args a) {
   __shared__ uint32_t s_pen[PROC_THREADS], s_ban[PROC_THREADS];
@@ -39,54 +37,8 @@ __global__ __launch_bounds__(PROC_THREADS) void logits_process_rows_kernel(klab_
   for (int p = tid; p < L; p += PROC_THREADS) s_hist[p] = p == 0 ? a.start_id : (int)a.seq[(long)r * a.ld_seq + p];
   // 1. scores (the padding slots past V hold -inf and are never written)
   float v[PROC_NPT];
-  if (a.dtype == KLAB_F32) {
-    const float* x = (const float*)a.logits + (long)(r / a.row_div) * a.ld + j0;
-    if (nv == PROC_NPT && ((uintptr_t)x % 16) == 0) {
-#pragma unroll
-      for (int c = 0; c < PROC_NPT; c += 4) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(x + c);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) v[c + t] = q[t];
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < PROC_NPT; ++c) v[c] = c < nv ? x[c] : -INFINITY;
-    }
-  } else {
-    const bf16_t* x = (const bf16_t*)a.logits + (long)(r / a.row_div) * a.ld + j0;
-    if (nv == PROC_NPT && ((uintptr_t)x % 16) == 0) {
-#pragma unroll
-      for (int c = 0; c < PROC_NPT; c += 8) {
-        const bf16x8 q = *reinterpret_cast<const bf16x8*>(x + c);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) v[c + t] = (float)q[t];
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < PROC_NPT; ++c) v[c] = c < nv ? (float)x[c] : -INFINITY;
-    }
-  }
-  if (a.log_softmax) {
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < PROC_NPT; ++c) m = fmaxf(m, v[c]);
-    m = wave_max(m);
-    if (lane == 0) s_f[0][wid] = m;
-    __syncthreads();
-    float M = s_f[0][0];
-    for (int q = 1; q < PROC_WAVES; ++q) M = fmaxf(M, s_f[0][q]);
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < PROC_NPT; ++c) s += c < nv ? expf(v[c] - M) : 0.f;
-    s = wave_sum(s);
-    if (lane == 0) s_f[1][wid] = s;
-    __syncthreads();
-    float S = 0.f;
-    for (int q = 0; q < PROC_WAVES; ++q) S += s_f[1][q];
-    const float logS = logf(S);
-#pragma unroll
-    for (int c = 0; c < PROC_NPT; ++c) v[c] = (v[c] - M) - logS;
-  }
+  row_load(v, a.dtype, a.logits, (long)(r / a.row_div) * a.ld + j0, nv);
+  if (a.log_softmax) row_log_softmax(v, nv, s_f);
   __syncthreads();  // the history and the cleared bitmaps
   // 2. the penalty map and the ban map
   if (a.repetition_penalty != 1.f) {
@@ -126,20 +78,7 @@ __global__ __launch_bounds__(PROC_THREADS) void logits_process_rows_kernel(klab_
   }
   // 4. the dense row
   if (a.out) {
-    float* o = a.out + (long)r * a.ld_out + j0;
-    if (nv == PROC_NPT && ((uintptr_t)o % 16) == 0) {
-#pragma unroll
-      for (int c = 0; c < PROC_NPT; c += 4) {
-        f32x4 q;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) q[t] = v[c + t];
-        *reinterpret_cast<f32x4*>(o + c) = q;
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < PROC_NPT; ++c)
-        if (c < nv) o[c] = v[c];
-    }
+    row_store(v, a.out + (long)r * a.ld_out + j0, nv);
   }
   if (!a.pick) return;
   // arg-max: (value, id) ranks above when larger, or equal with the lower id; every thread starts from its own first token, so

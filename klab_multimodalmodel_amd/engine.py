@@ -122,6 +122,7 @@ ENGINE_SIGS = {
     "klab_engine_gen_set_forced": ([C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p], C.c_int),
     "klab_engine_gen_attn_bytes": ([C.c_void_p, C.POINTER(L.GenCfg)], C.c_size_t),
     "klab_engine_gen_set_attn": ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
+    "klab_engine_gen_set_constraint": ([C.c_void_p, C.POINTER(L.ConstraintCfg), C.c_void_p], C.c_int),
     "klab_engine_gen_workspace_bytes": ([C.c_void_p, C.POINTER(L.GenCfg)], C.c_size_t),
     "klab_engine_gen_begin": ([C.c_void_p, C.POINTER(L.GenCfg), C.c_void_p, C.c_void_p], C.c_int),
     "klab_engine_gen_step": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
@@ -420,10 +421,12 @@ class Engine:
 
     @classmethod
     def gen_cfg(cls, mode, n, max_length, eos_id, pad_id, temperature=1.0, top_k=0, top_p=1.0, seed=0, length_penalty=1.0,
-                early_stopping=False, procs=None, want_logprobs=False):
+                early_stopping=False, procs=None, want_logprobs=False, constraint=None):
         """the klab_gen_cfg of a session; procs: the logits processors' settings (logits_proc.logits_processor_settings), None =
-        none; want_logprobs: sampling and pick also keep every chosen token's log-probability (gen_scores).  The cfg keeps the C
-        arrays it points to alive."""
+        none; want_logprobs: sampling and pick also keep every chosen token's log-probability (gen_scores); constraint: (trie,
+        roots) -- a constrain.TokenTrie on the device and the int32 [B] device tensor of every image's start node -- None = none.
+        klab_gen_cfg itself has no field for it: gen_workspace_bytes and gen_begin arm it (gen_set_constraint) for a cfg that
+        carries one.  The cfg keeps the C arrays and tensors it points to alive."""
         cfg = L.GenCfg(cls.GEN_MODES[mode], int(n), int(max_length), int(eos_id), int(pad_id), float(temperature), int(top_k),
                        float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, float(length_penalty), cls.EARLY_STOPPING[early_stopping])
         if procs is not None:
@@ -438,11 +441,30 @@ class Engine:
                                                   int(procs["min_length"]), int(procs["min_new_tokens"]), len(words),
                                                   C.cast(off_a, C.POINTER(C.c_int)), C.cast(tok_a, C.POINTER(C.c_int))))
         cfg.want_logprobs = int(bool(want_logprobs))
+        cfg.constraint = None  # (a Python attribute, not a field)
+        if constraint is not None:
+            trie, roots = constraint
+            if roots.dtype != torch.int32 or not roots.is_contiguous() or roots.device != trie.child_off.device:
+                raise ValueError("the constraint's roots must be a contiguous int32 tensor on the trie's device")
+            cfg.constraint = L.ConstraintCfg(trie.child_off.data_ptr(), trie.child_tok.data_ptr(), trie.child_node.data_ptr(),
+                                             trie.n_nodes, trie.n_edges, roots.data_ptr())
+            cfg._constraint_keep = (trie.child_off, trie.child_tok, trie.child_node, roots)  # alive while the session runs
         return cfg
 
     def gen_workspace_bytes(self, cfg):
-        """bytes of the session's workspace; 0 = settings this binding does not support"""
-        return int(self._lib.klab_engine_gen_workspace_bytes(self._h, C.byref(cfg)))
+        """bytes of the session's workspace, with the buffers of the cfg's constraint when it carries one; 0 = settings this binding
+        does not support"""
+        self.gen_set_constraint(getattr(cfg, "constraint", None))
+        try:
+            return int(self._lib.klab_engine_gen_workspace_bytes(self._h, C.byref(cfg)))
+        finally:
+            self.gen_set_constraint(None)
+
+    def gen_set_constraint(self, k):
+        """arms the constraint (an _lib.ConstraintCfg, Engine.gen_cfg(constraint=) makes it) of the NEXT gen_begin, one-shot as the
+        forced table; None disarms.  While one is armed gen_workspace_bytes answers for that session."""
+        L.check(self._lib.klab_engine_gen_set_constraint(self._h, C.byref(k) if k is not None else None, L.stream_ptr()),
+                "klab_engine_gen_set_constraint")
 
     def gen_set_forced(self, tokens, n_forced):
         """arms the forced-token table of the NEXT gen_begin (one-shot; gen_begin takes it whether it succeeds or not): tokens int64
@@ -479,6 +501,7 @@ class Engine:
         """after an evaluation-mode forward (the prefill): the session's state, and position 1 from the prefill's position-0 logits"""
         self._forced, self._forced_armed = self._forced_armed, None  # (the session's table stays referenced)
         self._attn, self._attn_armed = self._attn_armed, None  # (... and its maps)
+        self.gen_set_constraint(getattr(cfg, "constraint", None))  # (the cfg, kept in self._gen, keeps the tables referenced)
         L.check(self._lib.klab_engine_gen_begin(self._h, C.byref(cfg), ws.data_ptr(), L.stream_ptr()), "klab_engine_gen_begin")
         self._gen = cfg
 
@@ -500,12 +523,13 @@ class Engine:
 
     def gen_buffer(self, ws, name):
         """a view into ws -- "logits": [B*n, vocab], the logits gen_step decoded last; "tokens": [B*n] int64, the next step's inputs;
-        "logprobs" (want_logprobs sessions): [B*n, max_length] f32, the log-probability of every token chosen so far"""
+        "logprobs" (want_logprobs sessions): [B*n, max_length] f32, the log-probability of every token chosen so far; "nodes"
+        (constrained sessions): [B*n, 1] int32, the trie node every row stood on when the last position was chosen"""
         rows, cols, dt = C.c_long(), C.c_long(), C.c_int()
         p = self._lib.klab_engine_gen_buffer(self._h, ws.data_ptr(), name.encode(), C.byref(rows), C.byref(cols), C.byref(dt))
         if not p:
             raise KeyError(name)
-        tdt = torch.int64 if name == "tokens" else torch.float32 if dt.value == L.F32 else torch.bfloat16
+        tdt = torch.int64 if name == "tokens" else torch.int32 if name == "nodes" else torch.float32 if dt.value == L.F32 else torch.bfloat16
         off = p - ws.data_ptr()
         v = ws[off:off + rows.value * cols.value * tdt.itemsize].view(tdt)
         return v if name == "tokens" else v.view(rows.value, cols.value)

@@ -558,7 +558,8 @@ class MyModel(nn.Module):
     def generate(self, pixels, src, max_length=20, kv_cache=True, num_beams=1, length_penalty=1.0, early_stopping=False,
                  num_return_sequences=1, return_scores=False, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=None, min_length=0, min_new_tokens=None,
-                 return_logprobs=False, best_of=None, decoder_input_ids=None, return_cross_attention=False):
+                 return_logprobs=False, best_of=None, decoder_input_ids=None, constraint=None, constraint_set=None,
+                 return_cross_attention=False):
         """greedy decoding with HF's default generation settings (ref/models/model.py:28: max_length 20, no sampling).
         Every kv_cache=True call is one decoding session on the device (_generate_on_device; SURVEY §8 row f-3, HF/t5:308-332):
         prefill = one evaluation-mode forward (Swin, both encoders, the cross K/V of all layers, decoder position 0), then every
@@ -598,7 +599,17 @@ class MyModel(nn.Module):
         and without it).  The Le encoder tokens are the info["image_tokens"] Swin tokens, an info["image_grid"] = (g, g) raster,
         followed by the source-text tokens (the reference's torch.cat order).  Column 0 (the start token) and everything after a
         row's EOS are 0; with best_of the rows are those of the sequences.  With return_logprobs as well the same info carries
-        both.  Not with num_beams > 1 (beam search re-parents its rows every step) or kv_cache=False."""
+        both.  Not with num_beams > 1 (beam search re-parents its rows every step) or kv_cache=False.
+        constraint (a constrain.TokenTrie on the model's device, built for this vocabulary and EOS): decoding into a closed set of
+        phrases, HF's `prefix_allowed_tokens_fn` without the callback -- every row may only choose a child of the trie node it
+        stands on, a finished phrase or a row off the trie only EOS (klab_constrain_rows, one launch more per position).  Greedy
+        decoding returns the arg-max phrase at every branch, num_beams > 1 the best phrases of a set of any size with their
+        scores.  Works with sampling, all processors, return_logprobs / best_of (the log-probabilities are those of the masked
+        scores, renormalised over the allowed tokens for greedy and sampling), return_cross_attention and decoder_input_ids (the
+        phrase starts behind the prompt; the prompt is not walked).  constraint_set (int [B] tensor or list, default 0): the
+        phrase set of every image for a trie of several (TokenTrie.from_sequence_sets).  Needs kv_cache=True and vocab_size <=
+        32768.  Not checked: processors that ban everything the trie allows leave a row of -inf, which picks token 0."""
+        roots = self._constraint_roots(constraint, constraint_set, src, kv_cache)
         if return_cross_attention:
             if num_beams > 1:
                 raise ValueError("return_cross_attention needs num_beams == 1 (beam search re-parents its rows every step and keeps no maps)")
@@ -648,19 +659,20 @@ class MyModel(nn.Module):
                 raise ValueError(f"`num_return_sequences` has to be a positive integer, but is {num_return_sequences}")
             return self._generate_sample(pixels, src, max_length, num_return_sequences, float(temperature), int(top_k), float(top_p),
                                          procs, return_logprobs=return_logprobs, best_of=best_of, length_penalty=length_penalty,
-                                         prompt=prompt, return_cross_attention=return_cross_attention)
+                                         prompt=prompt, return_cross_attention=return_cross_attention, constraint=roots)
         if num_return_sequences > num_beams:
             raise ValueError(f"`num_return_sequences` ({num_return_sequences}) has to be smaller or equal to `num_beams` ({num_beams}).")
         if num_beams > 1:
             if not kv_cache:
                 raise ValueError("beam search runs on the K/V cache only: kv_cache=False needs num_beams=1")
             return self._generate_beam(pixels, src, max_length, num_beams, length_penalty, early_stopping, num_return_sequences,
-                                       return_scores, procs)
+                                       return_scores, procs, constraint=roots)
         if return_scores:
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence scores)")
         if kv_cache:
             return self._generate_sample(pixels, src, max_length, 1, 1.0, 0, 1.0, procs, pick=True, return_logprobs=return_logprobs,
-                                         length_penalty=length_penalty, prompt=prompt, return_cross_attention=return_cross_attention)
+                                         length_penalty=length_penalty, prompt=prompt, return_cross_attention=return_cross_attention,
+                                         constraint=roots)
         if procs is not None:
             raise ValueError("logits processors run on the K/V cache only: repetition_penalty, no_repeat_ngram_size, bad_words_ids, "
                              "min_length and min_new_tokens need kv_cache=True")
@@ -688,6 +700,32 @@ class MyModel(nn.Module):
             self.transformer.train(was_training)
         start = torch.full((B, 1), cfg.decoder_start_token_id, dtype=torch.int64, device=src.device)
         return torch.cat([start, tgt], dim=1)
+
+    def _constraint_roots(self, constraint, constraint_set, src, kv_cache):
+        """generate's constraint, checked before anything touches the device: (trie, the start node of every image as a host int32
+        [B] tensor), or None without one"""
+        from ..constrain import TokenTrie
+        if constraint is None:
+            if constraint_set is not None:
+                raise ValueError("constraint_set names the phrase sets of a trie: it needs `constraint`")
+            return None
+        cfg = self.main_cfg
+        B = src.shape[0]
+        if not isinstance(constraint, TokenTrie):
+            raise ValueError(f"`constraint` has to be a constrain.TokenTrie, got {type(constraint).__name__}")
+        if constraint.vocab_size != cfg.vocab_size or constraint.eos_token_id != cfg.eos_token_id:
+            raise ValueError(f"the trie was built for vocab_size {constraint.vocab_size} / eos_token_id {constraint.eos_token_id}, the "
+                             f"model has {cfg.vocab_size} / {cfg.eos_token_id}")
+        if constraint.device != src.device:
+            raise ValueError(f"the trie is on {constraint.device}, the batch on {src.device}: move it with trie.to(device)")
+        if not kv_cache:
+            raise ValueError("constrained decoding runs on the K/V cache only: `constraint` needs kv_cache=True")
+        which = torch.zeros(B, dtype=torch.int64) if constraint_set is None else torch.as_tensor(constraint_set).cpu()
+        if which.dim() != 1 or which.shape[0] != B or which.dtype.is_floating_point or which.dtype == torch.bool:
+            raise ValueError(f"constraint_set has to be an integer tensor or list [{B}], got {which.dtype} {tuple(which.shape)}")
+        if int(which.min()) < 0 or int(which.max()) >= constraint.n_sets:
+            raise ValueError(f"constraint_set names sets outside the {constraint.n_sets} of the trie")
+        return constraint, constraint.roots.cpu()[which.long()].to(torch.int32)
 
     def _decoder_prompt(self, decoder_input_ids, B, max_length):
         """HF's decoder prompt [B, Lp] on the host, start token first, from generate's decoder_input_ids (checked before anything
@@ -773,7 +811,8 @@ class MyModel(nn.Module):
         return out
 
     def _generate_on_device(self, pixels, src, max_length, mode, n, procs=None, num_return_sequences=None, temperature=1.0, top_k=0,
-                            top_p=1.0, length_penalty=1.0, early_stopping=False, logprobs=False, prompt=None, maps=False):
+                            top_p=1.0, length_penalty=1.0, early_stopping=False, logprobs=False, prompt=None, maps=False,
+                            constraint=None):
         """One prefill at B rows (Swin, both encoders and the cross K/V run once per image, not per row), then a decoding session of
         B*n rows on the device (row b*n + j: beam / sample j of image b, HF's `_expand_inputs_for_generation`): every step is the
         decoder over B*n rows and the mode's choice of the next tokens (`klab_engine_gen_step`); the host reads one stop word per
@@ -789,7 +828,8 @@ class MyModel(nn.Module):
         prompt (sampling and pick): the decoder prompt [B, Lp] with its start token (_decoder_prompt); its Lp - 1 tokens after
         the start token are forced at positions 1 .. Lp - 1 of each image's n rows.
         maps (sampling and pick): the session also writes its cross-attention maps (Engine.gen_set_attn) and info carries
-        cross_attention [rows, n_dec_layers, L, Le], image_tokens and image_grid (see generate), for the rows returned."""
+        cross_attention [rows, n_dec_layers, L, Le], image_tokens and image_grid (see generate), for the rows returned.
+        constraint: (trie, host roots [B]) of _constraint_roots; the session walks and applies the trie itself."""
         if mode == "beam" and early_stopping not in (False, True, "never"):
             raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
         if max_length < 2:
@@ -808,8 +848,10 @@ class MyModel(nn.Module):
             self._token_losses_valid = self._token_kl_valid = self._logits_valid = False  # (this forward scores a pad target ...
             eng.set_loss_options()                # ... with the plain loss: the launches generate and score always issued)
             eng.forward(pixels, src, tgt, training=0, seed=self._seed_base, want_grad=False)
+            if constraint is not None:
+                constraint = (constraint[0], constraint[1].to(src.device).contiguous())
             gen = eng.gen_cfg(mode, n, max_length, cfg.eos_token_id, pad, temperature, top_k, top_p, seed, length_penalty, early_stopping,
-                              procs, want_logprobs=logprobs)
+                              procs, want_logprobs=logprobs, constraint=constraint)
             nbytes = eng.gen_workspace_bytes(gen)
             if nbytes == 0:
                 what = {"beam": f"beam search: unsupported num_beams={n}", "sample": f"sampling: unsupported num_return_sequences={n}",
@@ -861,14 +903,15 @@ class MyModel(nn.Module):
         return dict(cross_attention=att, image_tokens=n_img, image_grid=(g, g))
 
     def _generate_beam(self, pixels, src, max_length, num_beams, length_penalty, early_stopping, num_return_sequences, return_scores,
-                       procs=None):
+                       procs=None, constraint=None):
         """HF's `_beam_search` as a decoding session (_generate_on_device): the sequences, and their scores when return_scores"""
         seq, scores = self._generate_on_device(pixels, src, max_length, "beam", num_beams, procs, num_return_sequences,
-                                               length_penalty=length_penalty, early_stopping=early_stopping)
+                                               length_penalty=length_penalty, early_stopping=early_stopping, constraint=constraint)
         return (seq, scores) if return_scores else seq
 
     def _generate_sample(self, pixels, src, max_length, num_return_sequences, temperature, top_k, top_p, procs=None, pick=False,
-                         return_logprobs=False, best_of=None, length_penalty=1.0, prompt=None, return_cross_attention=False):
+                         return_logprobs=False, best_of=None, length_penalty=1.0, prompt=None, return_cross_attention=False,
+                         constraint=None):
         """HF's `_sample` as a decoding session (_generate_on_device); pick=True: greedy decoding, the processed arg-max.
         return_logprobs / return_cross_attention: (sequences, info); best_of: that many rows per image, the num_return_sequences
         best returned"""
@@ -876,7 +919,7 @@ class MyModel(nn.Module):
         seq, info = self._generate_on_device(pixels, src, max_length, "pick" if pick else "sample", n, procs,
                                              num_return_sequences=num_return_sequences, temperature=temperature, top_k=top_k, top_p=top_p,
                                              length_penalty=length_penalty, logprobs=return_logprobs or best_of is not None,
-                                             prompt=prompt, maps=return_cross_attention)
+                                             prompt=prompt, maps=return_cross_attention, constraint=constraint)
         if return_cross_attention and not return_logprobs:  # (best_of ranks by the scores; they were not asked for)
             info = {k: info[k] for k in ("cross_attention", "image_tokens", "image_grid")}
         return (seq, info) if return_logprobs or return_cross_attention else seq
