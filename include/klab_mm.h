@@ -990,6 +990,27 @@ int klab_ciderd_rewards(const long long* hyp, int rows, int n_h, int L, const lo
 int klab_scst_targets(const long long* seq, int rows, int n, int L, const float* rewards, const float* baseline, int mode, int eos, int Lt,
                       long long* labels, float* weights, float* advantages, void* stream);
 
+/* ---- caption metrics (csrc/metrics.hip) ----------------------------------------------------------------------------------------
+ * klab_caption_stats: stats (int32 [rows, 16]) = the integer sufficient statistics of BLEU-1..4 and ROUGE-L of hypothesis row r of
+ * hyp against the present references of image r / n_h.  hyp, rows, n_h, L, refs, R, Lr, eos, count_eos and the units rule are
+ * klab_ciderd_rewards' (hyp int64 [rows, L], column 0 the start token; refs int64 [B, R, Lr] in label format, a row whose first
+ * entry is negative is absent; units = the tokens through the first EOS, the EOS itself when count_eos; an id < 0 or >= 0xFFFF
+ * ends the sequence).  Columns:
+ *   0..3   match_n, n = 1..4: sum over the hypothesis' distinct n-grams g of min(count_h(g), max_j count_j(g)), j over the present
+ *          references (BLEU's clipped matches)
+ *   4..7   guess_n = max(0, len_h - n + 1)
+ *   8      len_h, the number of units            9  the present reference length closest to len_h, the shorter one on a tie
+ *   10     max_j LCS(h, r_j) (ROUGE-L's precision numerator)
+ *   11,12  the pair (lcs_j, len_j) with the largest lcs_j / len_j, decided by integer cross-multiplication: it starts as (0, 0); a
+ *          present reference with len_j >= 1 replaces it when its length is 0 or lcs_j * len_best > lcs_best * len_j (the lowest
+ *          index wins a tie, references without units are skipped)
+ *   13     the number of present references      14, 15  0
+ * A present reference without units counts in column 13 and takes part in column 9 with length 0; an image without present
+ * references gives a row of zeros.  No floating point, no atomics; every element is stored exactly once; one launch.
+ * KLAB_ERR_UNSUPPORTED (before anything is enqueued): L > 65, Lr > 64, R outside 1..16. */
+int klab_caption_stats(const long long* hyp, int rows, int n_h, int L, const long long* refs, int R, int Lr, int eos, int count_eos,
+                       int* stats, void* stream);
+
 /* ---- crash diagnostics (opt-in; csrc/diag.cpp) -------------------------------------------------------------------------
  * klab_segv_trace_install: on SIGSEGV / SIGBUS / SIGABRT / SIGFPE / SIGILL write the context string and the native backtrace
  * of the faulting thread to file descriptor fd (< 0: stderr), then re-raise with the default action.

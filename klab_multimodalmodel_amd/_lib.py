@@ -219,6 +219,7 @@ SIGNATURES = {
     "klab_engine_set_weight_norm": [vp, i32],
     "klab_ciderd_rewards": [vp, i32, i32, i32, vp, i32, i32, vp, vp, i64, f32, f32, i32, i32, vp, vp],
     "klab_scst_targets": [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+    "klab_caption_stats": [vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp],
     "klab_im2col_patch": [vp, vp, i32, i32, i32, i32, i32, vp],
     "klab_im2col_patch_ld": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "klab_merge_gather": [vp, vp, i32, i32, i32, i32, vp],

@@ -19,14 +19,11 @@
 
 #include "common.h"
 #include "klab_mm.h"
+#include "ngram.h"
 
 namespace klab {
 namespace {
 
-constexpr int SC_UNITS = 64;   // units of a sequence = lanes of a wave
-constexpr int SC_MAX_R = 16;
-constexpr int SC_ORDERS = 4;
-constexpr unsigned long long SC_EMPTY = ~0ull;
 constexpr unsigned long long SC_GOLDEN = 0x9E3779B97F4A7C15ull;
 
 struct IdfTable {
@@ -48,51 +45,6 @@ __device__ __forceinline__ float idf_probe(const IdfTable& t, unsigned long long
   return t.log_n;
 }
 
-// lane i holds token i of a row of `width` tokens (anything beyond `width` is not looked at); returns the number of units and
-// leaves 0xFFFF in the lanes that hold none
-__device__ __forceinline__ int seq_units(long long& tok, int lane, int width, int eos, int count_eos) {
-  const bool in = lane < width;
-  const bool bad = in && (tok < 0 || tok >= 0xFFFF);
-  const bool end = in && !bad && tok == eos;
-  const unsigned long long stops = __ballot(bad || end);
-  int len = width;
-  if (stops) {
-    const int p = __ffsll((long long)stops) - 1;
-    len = p + (((__ballot(end) >> p) & 1ull) && count_eos ? 1 : 0);
-  }
-  if (lane >= len) tok = 0xFFFF;
-  return len;
-}
-
-// the n-gram of order n that starts at this lane's unit: key, number of occurrences in the sequence and whether this lane is the
-// first of them.  valid: the n-gram lies inside the sequence
-struct Gram {
-  unsigned long long key;
-  float count;
-  bool valid, first;
-};
-__device__ __forceinline__ Gram wave_gram(long long tok, int lane, int len, int n) {
-  Gram g;
-  g.key = (unsigned long long)tok & 0xFFFFull;
-#pragma unroll
-  for (int k = 1; k < SC_ORDERS; ++k) {
-    const unsigned long long t = (unsigned long long)__shfl_down(tok, k, 64) & 0xFFFFull;  // (lanes it cannot reach are not valid)
-    g.key |= (k < n ? t : 0xFFFFull) << (16 * k);
-  }
-  const int grams = len - n + 1;
-  g.valid = lane < grams;
-  int c = 0;
-  bool first = true;
-  for (int k = 0; k < grams; ++k) {  // (grams is wave-uniform)
-    const bool same = __shfl(g.key, k, 64) == g.key;
-    c += same;
-    first = first && !(same && k < lane);
-  }
-  g.count = (float)c;
-  g.first = g.valid && first;
-  return g;
-}
-
 // count * idf of the lane's n-gram of each order (0 unless the lane is the n-gram's first occurrence).  A probe is two dependent
 // loads and a sequence has four of them: the home slots' keys AND values of all four orders are loaded first (eight independent
 // loads; the slot is masked, so the speculative value load is in bounds), and only a collision walks on -- at a load factor of
@@ -111,7 +63,7 @@ __device__ __forceinline__ void weigh(const IdfTable& t, const Gram (&g)[SC_ORDE
     v[n] = 0.f;
     if (g[n].first) {
       if (k[n] != g[n].key) w[n] = k[n] == SC_EMPTY ? t.log_n : idf_probe(t, g[n].key, (slot[n] + 1) & t.mask);
-      v[n] = g[n].count * w[n];
+      v[n] = (float)g[n].count * w[n];
     }
   }
 }

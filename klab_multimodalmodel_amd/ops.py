@@ -528,6 +528,18 @@ def scst_targets(seq, rewards, baseline, labels, weights, advantages, *, n, mode
             "klab_scst_targets")
 
 
+def caption_stats(hyp, refs, stats, *, n_h=1, eos=1, count_eos=False):
+    """stats (int32 [rows, 16]) = BLEU-1..4 / ROUGE-L sufficient statistics of row r of hyp (int64 [rows, L], start token first)
+    against the present references of image r // n_h in refs (int64 [B, R, Lr], label format); columns as in include/klab_mm.h"""
+    lib = L.load()
+    rows, Lh = hyp.shape
+    B, R, Lr = refs.shape
+    if rows != B * n_h or stats.numel() != rows * 16:
+        raise ValueError(f"hyp holds {rows} rows, refs {B} images of {n_h} hypotheses, stats {stats.numel()} elements")
+    L.check(lib.klab_caption_stats(hyp.data_ptr(), rows, int(n_h), Lh, refs.data_ptr(), R, Lr, int(eos), int(bool(count_eos)),
+                                   stats.data_ptr(), L.stream_ptr()), "klab_caption_stats")
+
+
 def embed_fwd(ids, table, out, *, shift_right=False, L_seq=1, start_id=0, pad_id=0, drop_p=0.0, seed=None, tag=0, err=None):
     lib = L.load()
     rows, d = out.shape

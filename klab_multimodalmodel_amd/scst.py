@@ -7,6 +7,8 @@ image's reference captions, train on -(reward - baseline) log p(sample) -- rewar
     loss, info = sc.loss(images, source_encoding, refs_tensor)                 # refs_tensor int64 [B, R, Lr], label format
     loss.backward(); opt.step()
 
+SelfCritical(..., reward_weights={"ciderd": 1.0, "bleu4": 0.5}) mixes the reward with the sentence BLEU-4 and ROUGE-L of metrics.py.
+
 CIDEr-D (Vedantam et al.; the CiderD scorer of the COCO caption tools) is computed over units = token ids, so it equals the COCO
 tools' number only on word-id sequences.  A sequence's units are its tokens through the first EOS -- the EOS itself is a unit when
 count_eos (the default: it rewards ending the caption) -- and an id < 0 or >= 0xFFFF ends it.  Id lists given to from_references
@@ -21,13 +23,14 @@ import math
 import numpy as np
 import torch
 
-from . import ops
+from . import metrics, ops
 
 MAX_UNITS = 64
 MAX_REFS = 16
 EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
 GOLDEN = np.uint64(0x9E3779B97F4A7C15)
 BASELINES = {"greedy": 0, "mean": 1, "none": 2}  # klab_scst_targets' modes
+REWARD_TERMS = ("ciderd", "bleu4", "rouge_l")     # SelfCritical's reward_weights, in the order the mixture adds them
 
 
 def _home_slots(keys, cap):
@@ -178,9 +181,15 @@ def ciderd(table, hyp, refs):
 
 class SelfCritical:
     """One self-critical step's loss for a MyModel.  baseline: "greedy" (the reward of the greedy caption, Rennie et al.), "mean" (the
-    mean reward of the image's other samples, leave-one-out) or "none"."""
+    mean reward of the image's other samples, leave-one-out) or "none".
 
-    def __init__(self, model, table, samples=5, baseline="greedy", max_length=20, temperature=1.0, top_k=0, top_p=1.0):
+    reward_weights: None (the reward is CIDEr-D, exactly the launches above) or a dict over "ciderd", "bleu4", "rouge_l" with
+    finite weights, at least one non-zero: the reward is (w_c * ciderd.double() + w_b * Bleu_4 + w_r * ROUGE_L).float(), the
+    sentence scores of metrics.sentence_scores under the table's eos_token_id and count_eos, added in that order; a term with
+    weight 0 (or left out) is not computed.  The greedy baseline is scored with the same mixture."""
+
+    def __init__(self, model, table, samples=5, baseline="greedy", max_length=20, temperature=1.0, top_k=0, top_p=1.0,
+                 reward_weights=None):
         if not isinstance(table, CiderD):
             raise ValueError(f"`table` has to be a scst.CiderD, got {type(table).__name__}")
         if baseline not in BASELINES:
@@ -199,12 +208,43 @@ class SelfCritical:
         self.model, self.table = model, table
         self.samples, self.baseline, self.max_length = samples, baseline, max_length
         self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
+        if reward_weights is not None:
+            if not isinstance(reward_weights, dict) or set(reward_weights) - set(REWARD_TERMS):
+                raise ValueError(f"`reward_weights` has to be None or a dict over {REWARD_TERMS}, but is {reward_weights!r}")
+            if not all(isinstance(w, (int, float)) and not isinstance(w, bool) and math.isfinite(w) for w in reward_weights.values()):
+                raise ValueError(f"`reward_weights` needs finite numbers, but is {reward_weights!r}")
+            if not any(w != 0 for w in reward_weights.values()):
+                raise ValueError("`reward_weights` needs at least one non-zero weight")
+            reward_weights = {k: float(reward_weights.get(k, 0.0)) for k in REWARD_TERMS}
+        self.reward_weights = reward_weights
+
+    def _mixture(self, seq, refs, n):
+        """(reward fp32 [B * n], {term: its unmixed [B, n] values}) of seq under reward_weights; no host read"""
+        table, w = self.table, self.reward_weights
+        B = refs.shape[0]
+        terms, mix = {}, None
+        if w["ciderd"] != 0:
+            c = torch.empty(B * n, dtype=torch.float32, device=seq.device)
+            ops.ciderd_rewards(seq, refs, table.keys, table.idf, table.log_n, c, n_h=n, sigma=table.sigma, eos=table.eos_token_id,
+                               count_eos=table.count_eos)
+            terms["ciderd"] = c.view(B, n)
+        if w["bleu4"] != 0 or w["rouge_l"] != 0:
+            scores = metrics.sentence_scores(metrics.caption_stats(seq, refs, table.eos_token_id, table.count_eos))
+            if w["bleu4"] != 0:
+                terms["bleu4"] = scores[..., 3]
+            if w["rouge_l"] != 0:
+                terms["rouge_l"] = scores[..., 4]
+        for k in REWARD_TERMS:
+            if k in terms:
+                part = w[k] * terms[k].double()
+                mix = part if mix is None else mix + part
+        return mix.float().reshape(-1).contiguous(), terms
 
     def loss(self, images, source_encoding, refs):
         """(loss, info): loss = sum_t A log-likelihood terms / N over the sampled captions' N scored tokens, i.e. the model's weighted
         forward on the samples as labels with the advantages as weights and weight_norm="count"; info = dict(rewards [B, n],
-        baseline [B] (greedy) or None, advantages [B, n], sequences [B * n, L]).  Nothing is read from the device beyond generate's
-        stop word per step."""
+        baseline [B] (greedy) or None, advantages [B, n], sequences [B * n, L]; with reward_weights also reward_terms, the unmixed
+        [B, n] terms of the samples' reward).  Nothing is read from the device beyond generate's stop word per step."""
         model, table, n = self.model, self.table, self.samples
         pixels, src = images["pixel_values"], source_encoding["input_ids"]
         B = src.shape[0]
@@ -223,14 +263,19 @@ class SelfCritical:
         finally:
             model.transformer.train(was_training)
         dev = seq.device
-        rewards = torch.empty(B * n, dtype=torch.float32, device=dev)
-        ops.ciderd_rewards(seq, refs, table.keys, table.idf, table.log_n, rewards, n_h=n, sigma=table.sigma, eos=eos,
-                           count_eos=table.count_eos)
-        base = None
-        if greedy is not None:
-            base = torch.empty(B, dtype=torch.float32, device=dev)
-            ops.ciderd_rewards(greedy, refs, table.keys, table.idf, table.log_n, base, n_h=1, sigma=table.sigma, eos=eos,
+        base, terms = None, None
+        if self.reward_weights is None:
+            rewards = torch.empty(B * n, dtype=torch.float32, device=dev)
+            ops.ciderd_rewards(seq, refs, table.keys, table.idf, table.log_n, rewards, n_h=n, sigma=table.sigma, eos=eos,
                                count_eos=table.count_eos)
+            if greedy is not None:
+                base = torch.empty(B, dtype=torch.float32, device=dev)
+                ops.ciderd_rewards(greedy, refs, table.keys, table.idf, table.log_n, base, n_h=1, sigma=table.sigma, eos=eos,
+                                   count_eos=table.count_eos)
+        else:
+            rewards, terms = self._mixture(seq, refs, n)
+            if greedy is not None:
+                base = self._mixture(greedy, refs, 1)[0]
         Lt = self.max_length - 1
         labels = torch.empty(B, n, Lt, dtype=torch.int64, device=dev)
         weights = torch.empty(B, n, Lt, dtype=torch.float32, device=dev)
@@ -242,4 +287,7 @@ class SelfCritical:
             loss = model(images, source_encoding, {"input_ids": labels, "loss_weights": weights})
         finally:
             model._weight_norm = saved
-        return loss, dict(rewards=rewards.view(B, n), baseline=base, advantages=adv, sequences=seq)
+        info = dict(rewards=rewards.view(B, n), baseline=base, advantages=adv, sequences=seq)
+        if terms is not None:
+            info["reward_terms"] = terms
+        return loss, info
