@@ -343,7 +343,7 @@ int klab_relbias_bwd(const float* dbias, const int* bucket, float* dtable, int h
 int klab_ce_count(const long long* labels, int rows, float* inv_n, void* stream);
 int klab_ce_fwd(void* logits, long ld, int dtype, const long long* labels, int rows, int V, float* inv_n, float* loss_row,
                 float* loss, int write_grad, void* stream);
-/* the same with options (csrc/ce_opts.hip): label smoothing eps in [0, 1), z-loss z >= 0 and per-row weights (f32 [rows], finite,
+/* the same with options (csrc/ce.hip): label smoothing eps in [0, 1), z-loss z >= 0 and per-row weights (f32 [rows], finite,
  * >= 0, NULL = all ones):
  *   l_i = lse - (1 - eps) x_y - (eps / V) sum_j x_j + z lse^2 (0 where the label is -100), loss = sum_i w_i l_i / W with
  *   W = sum of w_i over the rows with a label (loss 0 when W == 0), d l / d x_j = (w_i / W) [p_j (1 + 2 z lse) - (1 - eps) [j == y] - eps / V].
@@ -353,7 +353,7 @@ int klab_ce_fwd(void* logits, long ld, int dtype, const long long* labels, int r
 int klab_ce_wsum(const long long* labels, const float* weights, int rows, float* inv_w, void* stream);
 int klab_ce_fwd_opts(void* logits, long ld, int dtype, const long long* labels, const float* weights, int rows, int V, float eps, float z,
                      float* inv_w, float* loss_row, float* loss, int write_grad, void* stream);
-/* the same mixed with knowledge distillation (csrc/ce_distill.hip): teacher logits t [rows, V] (bf16 or f32 whatever the student's
+/* the same mixed with knowledge distillation (csrc/ce.hip): teacher logits t [rows, V] (bf16 or f32 whatever the student's
  * dtype, row stride ldt >= V, FINITE -- a precondition, not checked on the device), temperature T > 0, alpha in [0, 1]:
  *   kl_i = KL(softmax(t / T) || softmax(x / T)),  l_i = (1 - alpha) ce_i + alpha T^2 kl_i with ce_i the l_i above (0 where the label is -100),
  *   d l / d x_j = (w_i / W) [(1 - alpha) (the bracket above) + alpha T (softmax(x / T)_j - softmax(t / T)_j)].

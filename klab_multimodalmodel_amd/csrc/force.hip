@@ -4,7 +4,7 @@
 //                     (done, pad after EOS, tokens, seq, stop word) and optionally the token's log-probability under the raw row.
 //     logprob given : one FORCE_THREADS workgroup per row reads the row ONCE with 16-byte loads; every thread keeps an online
 //                     (max, sum exp) pair, rescaled once per vector, merged across the wave and then across the waves in LDS
-//                     (as ce_fwd_kernel and beam_topk_rows_kernel do); thread 0 gathers x[token] and writes
+//                     (as ce_kernel and beam_topk_rows_kernel do); thread 0 gathers x[token] and writes
 //                     (x[token] - M) - logf(S).  No register row, so no cap on V; no atomics.  A row finished on entry reads
 //                     nothing and writes 0.
 //     logprob NULL  : one thread per row, the logits are never touched (a prompt position needs none).

@@ -1,7 +1,7 @@
 // HBM-bound glue kernels of the path: weight cast/pack, embedding gather / scatter-add, relative
-// position bias gather / scatter, LM-head cross-entropy (+ d logits in place), patch im2col,
-// patch-merge gather / scatter, bias-gradient column sums.  All are coalesced 16-byte streams with
-// wave-shuffle reductions; none is reshaped into a GEMM.
+// position bias gather / scatter, patch im2col, patch-merge gather / scatter, bias-gradient column
+// sums (the LM-head cross-entropy is ce.hip).  All are coalesced 16-byte streams with wave-shuffle
+// reductions; none is reshaped into a GEMM.
 #include <math.h>
 
 #include <map>
@@ -121,152 +121,6 @@ __global__ void relbias_bwd_kernel(const float* __restrict__ dbias, const int* _
   for (int ij = threadIdx.x; ij < LL; ij += blockDim.x) atomicAdd(&acc[bucket[ij]], dbias[(long)h * LL + ij]);
   __syncthreads();
   for (int i = threadIdx.x; i < nb; i += blockDim.x) atomicAdd(dtable + i * H + h, acc[i]);
-}
-
-// ---- LM-head cross-entropy (HF/t5:1050-1054: CrossEntropyLoss(ignore_index=-100), mean over the
-//      non-ignored rows; pads (id 0) ARE scored) -------------------------------------
-__global__ void ce_count_kernel(const long long* __restrict__ labels, int rows, float* __restrict__ inv_n) {
-  __shared__ int red[4];
-  int c = 0;
-  for (int i = threadIdx.x; i < rows; i += blockDim.x) c += labels[i] != -100;
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int n = red[0] + red[1] + red[2] + red[3];
-    inv_n[0] = n > 0 ? 1.f / (float)n : 0.f;   // (reference would produce NaN for n == 0)
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void ce_fwd_kernel(T* __restrict__ logits, long ld, const long long* __restrict__ labels, int V,
-                                                     const float* __restrict__ inv_n, float* __restrict__ loss_row, int write_grad) {
-  constexpr int VEC = Vec16<T>::N;
-  using VT = typename Vec16<T>::type;
-  __shared__ float red[8];
-  const long row = blockIdx.x;
-  const int tid = threadIdx.x;
-  T* x = logits + row * ld;
-  const long long lab = labels[row];
-  float m = -INFINITY, s = 0.f;
-  for (int c = tid * VEC; c < V; c += 256 * VEC) {
-    VT v = *reinterpret_cast<const VT*>(x + c);
-    float mx = to_f32(v[0]);
-#pragma unroll
-    for (int u = 1; u < VEC; ++u) mx = fmaxf(mx, to_f32(v[u]));
-    const float mn = fmaxf(m, mx);
-    float a = 0.f;
-#pragma unroll
-    for (int u = 0; u < VEC; ++u) a += __expf(to_f32(v[u]) - mn);
-    s = s * __expf(m - mn) + a;
-    m = mn;
-  }
-  // block-wide (max, sum) merge
-  float wm = wave_max(m);
-  float ws = wave_sum(m == -INFINITY ? 0.f : s * __expf(m - wm));  // lanes/waves with no column contribute 0, not NaN
-  if ((tid & 63) == 0) { red[tid >> 6] = wm; red[4 + (tid >> 6)] = ws; }
-  __syncthreads();
-  const float bm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  float bs = 0.f;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) bs += red[w] == -INFINITY ? 0.f : red[4 + w] * __expf(red[w] - bm);
-  const float lse = bm + __logf(bs);
-  const bool valid = lab != -100;
-  if (tid == 0) loss_row[row] = valid ? (lse - to_f32(x[lab])) : 0.f;
-  if (!write_grad) return;
-  __syncthreads();  // x[lab] read above before it is overwritten below
-  const float g = valid ? inv_n[0] : 0.f;
-  for (int c = tid * VEC; c < V; c += 256 * VEC) {
-    VT v = *reinterpret_cast<const VT*>(x + c);
-    VT o;
-#pragma unroll
-    for (int u = 0; u < VEC; ++u) {
-      float pr = __expf(to_f32(v[u]) - lse);
-      if (c + u == lab) pr -= 1.f;
-      o[u] = from_f32<T>(pr * g);
-    }
-    *reinterpret_cast<VT*>(x + c) = o;
-  }
-}
-
-// One-pass form for rows that fit the workgroup's registers (V <= 256 * 16 bytes/lane * NIT: 32768 bf16 logits with NIT = 16,
-// the T5 vocabulary is 32128): the row is read ONCE -- every load of the row is issued before the first use -- and d logits are
-// written from the registers.  The two-pass kernel above re-read the row from HBM (4096 rows x 64 KB in flight do not fit the L2s):
-// 790 MB of traffic for 526 MB of algorithmic bytes.
-template <typename T, int NIT>
-__global__ __launch_bounds__(256) void ce_fwd_onepass_kernel(T* __restrict__ logits, long ld, const long long* __restrict__ labels, int V,
-                                                             const float* __restrict__ inv_n, float* __restrict__ loss_row, int write_grad) {
-  constexpr int VEC = Vec16<T>::N;
-  using VT = typename Vec16<T>::type;
-  __shared__ float red[8];
-  __shared__ float xlab;
-  const long row = blockIdx.x;
-  const int tid = threadIdx.x;
-  T* x = logits + row * ld;
-  const long long lab = labels[row];
-  VT v[NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int c = (it * 256 + tid) * VEC;
-    if (c < V) v[it] = *reinterpret_cast<const VT*>(x + c);
-  }
-  float m = -INFINITY;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int c = (it * 256 + tid) * VEC;
-    if (c < V) {
-#pragma unroll
-      for (int u = 0; u < VEC; ++u) m = fmaxf(m, to_f32(v[it][u]));
-    }
-  }
-  const float wm = wave_max(m);
-  if ((tid & 63) == 0) red[tid >> 6] = wm;
-  __syncthreads();
-  const float bm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  float sum = 0.f;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int c = (it * 256 + tid) * VEC;
-    if (c < V) {
-#pragma unroll
-      for (int u = 0; u < VEC; ++u) {
-        sum += __expf(to_f32(v[it][u]) - bm);
-        if (c + u == lab) xlab = to_f32(v[it][u]);
-      }
-    }
-  }
-  const float ws = wave_sum(sum);
-  if ((tid & 63) == 0) red[4 + (tid >> 6)] = ws;
-  __syncthreads();
-  const float lse = bm + __logf(red[4] + red[5] + red[6] + red[7]);
-  const bool valid = lab != -100;
-  if (tid == 0) loss_row[row] = valid ? (lse - xlab) : 0.f;
-  if (!write_grad) return;
-  const float g = valid ? inv_n[0] : 0.f;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int c = (it * 256 + tid) * VEC;
-    if (c < V) {
-      VT o;
-#pragma unroll
-      for (int u = 0; u < VEC; ++u) {
-        float pr = __expf(to_f32(v[it][u]) - lse);
-        if (c + u == lab) pr -= 1.f;
-        o[u] = from_f32<T>(pr * g);
-      }
-      *reinterpret_cast<VT*>(x + c) = o;
-    }
-  }
-}
-
-__global__ void ce_reduce_kernel(const float* __restrict__ loss_row, int rows, const float* __restrict__ inv_n, float* __restrict__ loss) {
-  __shared__ float red[4];
-  float a = 0.f;
-  for (int i = threadIdx.x; i < rows; i += blockDim.x) a += loss_row[i];  // fixed order => bit-reproducible
-  a = wave_sum(a);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) loss[0] = (red[0] + red[1] + red[2] + red[3]) * inv_n[0];
 }
 
 // ---- Swin patch embedding im2col (Conv2d k4 s4 == GEMM over 48-wide patches, HF/swinv2:281) ----
@@ -508,40 +362,6 @@ extern "C" int klab_relbias_bwd(const float* dbias, const int* bucket, float* dt
   if (!dbias || !bucket || !dtable) return KLAB_ERR_BADARG;
   if (nbuckets > 64) return KLAB_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(relbias_bwd_kernel, dim3(heads), dim3(256), 0, (hipStream_t)stream, dbias, bucket, dtable, heads, Lq * Lk, nbuckets);
-  KLAB_LAUNCH_CHECK();
-  return KLAB_OK;
-}
-
-// inv_n[0] = 1 / (number of labels != -100): the first launch of klab_ce_fwd on its own, for callers that know the labels long before
-// the logits exist (the engine runs it beside the Swin tower and passes write_grad | 2)
-extern "C" int klab_ce_count(const long long* labels, int rows, float* inv_n, void* stream) {
-  if (!labels || !inv_n || rows <= 0) return KLAB_ERR_BADARG;
-  hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, labels, rows, inv_n);
-  KLAB_LAUNCH_CHECK();
-  return KLAB_OK;
-}
-
-extern "C" int klab_ce_fwd(void* logits, long ld, int dtype, const long long* labels, int rows, int V, float* inv_n, float* loss_row,
-                           float* loss, int write_grad, void* stream) {
-  if (!logits || !labels || !inv_n || !loss_row || !loss) return KLAB_ERR_BADARG;
-  const int vec = dtype == KLAB_BF16 ? 8 : 4;
-  if (V % vec || ld % vec) return KLAB_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  if (!(write_grad & 2)) {  // bit 1: inv_n already holds 1 / n_valid of these labels (klab_ce_count ran ahead of the logits)
-    hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(256), 0, s, labels, rows, inv_n);
-    KLAB_LAUNCH_CHECK();
-  }
-  write_grad &= 1;
-  if (dtype == KLAB_BF16 && V <= 256 * 8 * 16 && V > 256 * 8 * 8)
-    hipLaunchKernelGGL((ce_fwd_onepass_kernel<bf16_t, 16>), dim3(rows), dim3(256), 0, s, (bf16_t*)logits, ld, labels, V, inv_n, loss_row, write_grad);
-  else if (dtype == KLAB_BF16 && V <= 256 * 8 * 8)
-    hipLaunchKernelGGL((ce_fwd_onepass_kernel<bf16_t, 8>), dim3(rows), dim3(256), 0, s, (bf16_t*)logits, ld, labels, V, inv_n, loss_row, write_grad);
-  else if (dtype == KLAB_BF16)
-    hipLaunchKernelGGL(ce_fwd_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, (bf16_t*)logits, ld, labels, V, inv_n, loss_row, write_grad);
-  else
-    hipLaunchKernelGGL(ce_fwd_kernel<float>, dim3(rows), dim3(256), 0, s, (float*)logits, ld, labels, V, inv_n, loss_row, write_grad);
-  KLAB_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, s, loss_row, rows, inv_n, loss);
   KLAB_LAUNCH_CHECK();
   return KLAB_OK;
 }

@@ -1,4 +1,4 @@
-"""fp64 reference, fixtures and per-element bounds of the cross-entropy with knowledge distillation (csrc/ce_distill.hip) for
+"""fp64 reference, fixtures and per-element bounds of the cross-entropy with knowledge distillation (csrc/ce.hip) for
 tests/test_distill_cpu.py and tests/test_distill_gpu.py.
 
     ce      = loss_opts_ref's l                                                              (label smoothing eps, z-loss z)
@@ -100,7 +100,7 @@ def teacher_for(rows, V, dt, tdt):
 
 
 def one_pass(V, dt):
-    """the dispatch of csrc/ce_distill.hip (ce_opts.hip's)"""
+    """the dispatch of csrc/ce.hip"""
     return dt == "bf16" and V <= 32768
 
 

@@ -1,4 +1,4 @@
-"""fp64 reference, fixtures and per-element bounds of the cross-entropy with options (csrc/ce_opts.hip) for
+"""fp64 reference, fixtures and per-element bounds of the cross-entropy with options (csrc/ce.hip) for
 tests/test_loss_opts_cpu.py and tests/test_loss_opts_gpu.py.
 
     l_i     = lse - (1 - eps) x_y - (eps / V) sum_j x_j + z lse^2          (0 where y == -100)

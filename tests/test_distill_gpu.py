@@ -1,4 +1,4 @@
-"""Knowledge distillation in the loss on the GPU: klab_ce_fwd_distill (csrc/ce_distill.hip) through `ops` against klab_ce_fwd_opts
+"""Knowledge distillation in the loss on the GPU: klab_ce_fwd_distill (csrc/ce.hip) through `ops` against klab_ce_fwd_opts
 (alpha = 0: bit for bit) and against the fp64 reference of tests/distill_ref.py (per-element bounds), and
 MyModel.set_loss_options(distill_alpha, distill_temperature) / target_encoding["teacher_logits"] / token_kl / logits /
 distill.teacher_logits on golden tiny_a against the oracle's logits put through the formula in torch.

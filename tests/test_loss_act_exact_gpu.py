@@ -1,4 +1,4 @@
-"""Per-element reference tests of the cross-entropy kernels and klab_gelu_fwd[_q8] (csrc/misc.hip) and of the gated-GELU gate
+"""Per-element reference tests of the cross-entropy kernels (csrc/ce.hip), of klab_gelu_fwd[_q8] (csrc/misc.hip) and of the gated-GELU gate
 (csrc/ffn_gated.hip) against fp64 (references and bounds: tests/rowops_ref.py).
 
 rule                                                                   -> shape

@@ -1,4 +1,4 @@
-"""The cross-entropy with options on the GPU: klab_ce_wsum / klab_ce_fwd_opts (csrc/ce_opts.hip) through `ops` against the plain
+"""The cross-entropy with options on the GPU: klab_ce_wsum / klab_ce_fwd_opts (csrc/ce.hip) through `ops` against the plain
 kernel (neutral options: bit for bit) and against the fp64 reference of tests/loss_opts_ref.py (per-element bounds), and
 MyModel.set_loss_options / target_encoding["loss_weights"] / token_losses on golden tiny_a against the oracle's logits put through
 the formula in torch.
